@@ -20,8 +20,15 @@ N > 1 : weak scaling (default).  The dd relation set grows with N (N x the pose0
         workload.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant
-kernel, HIP-event timed inside the timed region) and `cpu_baseline` (the oracle, i.e. a port
-of the reference's op sequence, timed on this box's host cores; N = 1 only).
+kernel, HIP-event timed inside the timed region).  A plain run does only what that line needs:
+set-up, warm-up, the K timed steps.  `--full` adds every side figure that takes runs of its own:
+`cpu_baseline` and `parity` (the oracle, i.e. a port of the reference's op sequence, timed on
+this box's host cores; N = 1 only), `spread`, `cold_start`, `roofline_fast`, `two_streams`,
+`sharded_path_n1` and `extra_workloads`.
+
+`--dump-outputs DIR` writes what the last timed step returned (`z`, the drug embeddings, and
+`score`, the decoder's scores of this rank's edge range) as DIR/z.npy and DIR/score.npy in
+float32; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -66,6 +73,15 @@ def spin_up(fn, seconds=0.12):
         for _ in range(4):
             fn()
     torch.cuda.synchronize()
+
+
+def dump_outputs(path, tensors):
+    """Each tensor as path/<name>.npy in float32, whole: the largest workload, pose2-syn, writes 34 MB (8.4 M scores), pose0-syn 8 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in tensors.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
 
 def algorithmic_bytes(data, n_dd_edges_local, n_dd_edges_global):
     """Compulsory HBM bytes with the reference's data types: int64 indices, fp32
@@ -685,11 +701,18 @@ def main():
                          "recorded: the step's entry-point calls written down once and made again from one loop "
                          "(gripnet_amd.pipeline.Recorded: ordinary launches, no graph); auto: whichever of the three runs "
                          "the step fastest on this box, measured before the timed region")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra workloads (pose2-syn, aminer-syn, freebase-c-syn)")
-    ap.add_argument("--extra-seconds", type=float, default=90.0, help="time budget of the extra workloads")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side figures (CPU baseline and parity, spread, cold start, fast arithmetic, two streams, "
+                         "the N > 1 code path at N = 1, extra workloads); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (z, score) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra workloads (pose2-syn, aminer-syn, freebase-c-syn)")
+    ap.add_argument("--extra-seconds", type=float, default=90.0, help="with --full: time budget of the extra workloads")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: time budget of the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=16)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload is None:
         args.workload = "pose2-syn" if args.scaling == "strong" else "pose0-syn"
 
@@ -762,33 +785,34 @@ def main():
             fence()
             plan_build_ms = 1e3 * max(0.0, t_plan - (time.perf_counter() - t_steady))
             per_call0, breakdown = per_entry_us(eager.step, 5)
-            cold = cold_start_entry(model, data, fence)
-            # the two lanes of the two-stream side figure (below the timed region) are made HERE, before any hipGraph is
-            # captured: streams created behind captured graphs came to share a hardware queue and the lanes serialised.
-            # (A second model with the same parameters: the plans' scratch - the gene layers' tables, the split planes of x -
-            # belongs to a model's modules, and two steps in flight must not share it.)
-            lanes = None
-            if args.launch in ("auto", "recorded"):
-                twin = PoseModel(data.n_g_node, data.n_d_node, data.n_dd_edge_type).to(dev)
-                twin.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
-                lanes = []
-                for m in (model, twin):
-                    st = torch.cuda.Stream()
-                    st.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(st):
-                        lanes.append(PoseStages(m, data, recorded=True))
-                fence()
-            # side figure: the same step with the dense products on two-term bf16 splits (GN_RGCN_ARITH_FAST /
-            # GN_GEMM_ARITH_FAST, flags of the C ABI set per layer): narrower than the reference's fp32, never the headline
-            from gripnet_amd.utils import set_arithmetic
-            set_arithmetic(model, "fast")
-            fast_stages = PoseStages(model, data, graphs=False)
-            for _ in range(3):
-                fast_stages.step()
-            fast_call, fast_breakdown = per_entry_us(fast_stages.step, 5)
-            set_arithmetic(model, "fp32")
-            for _ in range(2):
-                eager.step()
+            cold, lanes, fast_call, fast_breakdown = None, None, {}, {}
+            if args.full:
+                cold = cold_start_entry(model, data, fence)
+                # the two lanes of the two-stream side figure (below the timed region) are made HERE, before any hipGraph is
+                # captured: streams created behind captured graphs came to share a hardware queue and the lanes serialised.
+                # (A second model with the same parameters: the plans' scratch - the gene layers' tables, the split planes of x -
+                # belongs to a model's modules, and two steps in flight must not share it.)
+                if args.launch in ("auto", "recorded"):
+                    twin = PoseModel(data.n_g_node, data.n_d_node, data.n_dd_edge_type).to(dev)
+                    twin.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
+                    lanes = []
+                    for m in (model, twin):
+                        st = torch.cuda.Stream()
+                        st.wait_stream(torch.cuda.current_stream())
+                        with torch.cuda.stream(st):
+                            lanes.append(PoseStages(m, data, recorded=True))
+                    fence()
+                # side figure: the same step with the dense products on two-term bf16 splits (GN_RGCN_ARITH_FAST /
+                # GN_GEMM_ARITH_FAST, flags of the C ABI set per layer): narrower than the reference's fp32, never the headline
+                from gripnet_amd.utils import set_arithmetic
+                set_arithmetic(model, "fast")
+                fast_stages = PoseStages(model, data, graphs=False)
+                for _ in range(3):
+                    fast_stages.step()
+                fast_call, fast_breakdown = per_entry_us(fast_stages.step, 5)
+                set_arithmetic(model, "fp32")
+                for _ in range(2):
+                    eager.step()
             # the entry point timed inside the timed region: the longest single launch.  (A gene layer is two launches
             # behind one entry point since the LDS-staged path; it is listed in roofline_all with the others.)
             dom = max((k for k in CANDIDATES if k != "gn_graph_aggregate_f32[gcn]"), key=lambda k: per_call0.get(k, 0.0))
@@ -866,16 +890,17 @@ def main():
         # minute - tools/step_only.py).  The steady state is what is quoted: `spin_up_steps` un-timed steps bring the clocks up, then
         # the W warm-up steps and the K timed ones follow without a pause.
         spin_up_steps = int(os.environ.get("GN_BENCH_SPIN_UP", "4000"))
-        # (for the record: the same W + K steps WITHOUT the spin-up first - what the line would say with the clocks where the
-        # host-side work left them; a side figure in `spread`, never `value`)
-        for _ in range(max(args.warmup, 1)):
-            step()
-        fence()
-        t_cold = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        fence()
-        cold_ms = 1e3 * (time.perf_counter() - t_cold) / max(args.steps, 1)
+        if args.full:
+            # (for the record: the same W + K steps WITHOUT the spin-up first - what the line would say with the clocks where the
+            # host-side work left them; a side figure in `spread`, never `value`)
+            for _ in range(max(args.warmup, 1)):
+                step()
+            fence()
+            t_cold = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            fence()
+            cold_ms = 1e3 * (time.perf_counter() - t_cold) / args.steps
         for _ in range(spin_up_steps):
             step()
         fence()
@@ -890,15 +915,19 @@ def main():
                 z, score = step()
         fence()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            # host copies now: a recorded step returns its recording's buffers, which every later step writes again
+            dump_outputs(args.dump_outputs, {"z": z, "score": score})
         # two more repeats of the same K steps, for the spread only (`value` and `ms_per_step` are the region above)
         repeats = [elapsed]
-        for _ in range(2):
-            fence()
-            t1 = time.perf_counter()
-            for _ in range(args.steps):
-                step()
-            fence()
-            repeats.append(time.perf_counter() - t1)
+        if args.full:
+            for _ in range(2):
+                fence()
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    step()
+                fence()
+                repeats.append(time.perf_counter() - t1)
     # side figure (never `value`): INDEPENDENT steps on two streams, each a recording with its own buffers - what the device
     # sustains when forwards do not wait for each other (serving); a step's own latency is `ms_per_step` above
     two_streams = None
@@ -923,7 +952,7 @@ def main():
     # side figure (never `value`): the N > 1 code path (ShardedPoseForward.record(): partial sums of my edge range, the exchange
     # hook, finalisation, my range's scores) rehearsed on this one GPU - what the step costs before any communication
     sharded_n1 = None
-    if sharded is None:
+    if sharded is None and args.full:
         with torch.no_grad():
             from gripnet_amd.sharded import ShardedPoseForward
             fwd1 = ShardedPoseForward(model, data, 0, 1)
@@ -949,13 +978,6 @@ def main():
 
     A = pose_edges_aggregated(data)                    # replicated gg/gd counted once, dd over all ranks
     ms_per_step = 1e3 * elapsed / args.steps
-    rep_ms = sorted(1e3 * r / args.steps for r in repeats)
-    spread = {"ms_per_step_min": round(rep_ms[0], 5), "ms_per_step_median": round(rep_ms[len(rep_ms) // 2], 5),
-              "ms_per_step_max": round(rep_ms[-1], 5), "repeats": len(rep_ms),
-              "ms_per_step_before_spin_up": round(cold_ms, 5),
-              "note": "K steps each, rank-local clocks; the first repeat is the timed region `value` is computed from; "
-                      "ms_per_step_before_spin_up: W + K steps timed the same way BEFORE the spin_up_steps un-timed steps (the device's clocks "
-                      "where the host-side set-up left them: not the steady state)"}
     value = A * args.steps / elapsed
 
     # ---- roofline of the dominant entry point (HIP events on its stream, inside the timed region) ----
@@ -983,7 +1005,7 @@ def main():
     # the same average with event RECORDS around every fourth launch (the method of rounds 1-4: comparable across rounds; a record
     # in front of and behind the launch reads ~2 us more than the kernel's own dispatch stamps), outside the timed region
     records_us = None
-    if dom in _hip._STAMPED:
+    if dom in _hip._STAMPED and args.full:
         with torch.no_grad(), _hip.KernelTimer(only=(dom,), pool=2 * args.steps + 8, every=timed_every, records_only=True) as rt:
             for _ in range(args.steps):
                 step()
@@ -1049,16 +1071,8 @@ def main():
                    "parallelism": "single GPU" if world == 1 else "dd edge-range (relation) shards x{} + {}".format(
                        world, "one-shot direct exchange (peer-mapped buffers)" if getattr(sharded, "one_shot", None) is not None else "RCCL all-reduce"),
                    "launch": launch_note},
-        "ms_per_step_min": spread["ms_per_step_min"],
-        # the same step with nothing kept on the decoder's side (the reference's decoder has no set-up; cold_start has the plans' build times)
-        "ms_per_step_decoder_uncached": None if not cold else cold.get("forward_ms_decoder_uncached"),
-        "spread": spread,
         "launch_modes_ms_per_step": launch_ms if sharded is None else None,
-        "two_streams": two_streams,
-        "sharded_path_n1": sharded_n1,
-        "cold_start": cold,
         "roofline": roofline,
-        "roofline_fast": roofline_fast,
         "roofline_all": roofline_all,
         "mfma_util": mfma,
         "mfma_util_source": "profiles/mfma_util.json (SQ_VALU_MFMA_BUSY_CYCLES pass of tools/prof.sh step r06, same command as the traffic passes; not a counter of this run)" if mfma else None,
@@ -1067,9 +1081,27 @@ def main():
         "edges_scored_per_sec": (hi - lo) / (per_call0.get("gn_distmult_plan_forward_f32",
                                                            per_call0.get("gn_distmult_forward_f32", float("nan"))) * 1e-6),
     }
+    if args.full:
+        rep_ms = sorted(1e3 * r / args.steps for r in repeats)
+        spread = {"ms_per_step_min": round(rep_ms[0], 5), "ms_per_step_median": round(rep_ms[len(rep_ms) // 2], 5),
+                  "ms_per_step_max": round(rep_ms[-1], 5), "repeats": len(rep_ms),
+                  "ms_per_step_before_spin_up": round(cold_ms, 5),
+                  "note": "K steps each, rank-local clocks; the first repeat is the timed region `value` is computed from; "
+                          "ms_per_step_before_spin_up: W + K steps timed the same way BEFORE the spin_up_steps un-timed steps (the device's clocks "
+                          "where the host-side set-up left them: not the steady state)"}
+        result.update({
+            "ms_per_step_min": spread["ms_per_step_min"],
+            # the same step with nothing kept on the decoder's side (the reference's decoder has no set-up; cold_start has the plans' build times)
+            "ms_per_step_decoder_uncached": None if not cold else cold.get("forward_ms_decoder_uncached"),
+            "spread": spread,
+            "two_streams": two_streams,
+            "sharded_path_n1": sharded_n1,
+            "cold_start": cold,
+            "roofline_fast": roofline_fast,
+        })
 
     # ---- CPU baseline + parity in the same run (rank 0, N = 1) ---------------------------------
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import gripnet_oracle as orc        # checker / baseline only, never the product path
         # 16 threads is the fastest setting for this op mix on the 2x64-core host of the GPU box
         # (measured: 8 -> 1.05 s, 16 -> 0.92 s, 32 -> 0.94 s, 64 -> 1.2 s, 128 -> 3-6 s per forward)
@@ -1102,7 +1134,7 @@ def main():
                             "ok": bool(max(err_z, err_s) <= 1e-4)}
         assert max(err_z, err_s) <= 1e-4, "GPU result differs from the CPU oracle: {}".format(result["parity"])
 
-    if world == 1 and not args.no_extra:
+    if world == 1 and args.full and not args.no_extra:
         del model, data
         torch.cuda.empty_cache()
         result["extra_workloads"] = extra_workloads(dev, args.extra_seconds, not args.no_cpu_baseline)
