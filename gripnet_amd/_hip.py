@@ -25,7 +25,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 154                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 155                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -98,6 +98,10 @@ SIGNATURES = {
     "gn_negative_sampler_sample": (_int, [_p, C.c_uint64, _p, _p, _p, _p]),
     "gn_negative_sampler_sample_packed": (_int, [_p, C.c_uint64, _p, _p, _p, _p, _p]),
     "gn_negative_sampler_sample_stepped": (_int, [_p, C.c_uint64, _p, _p, _p, _p, _p, _p]),
+    "gn_known_pairs_create": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, C.POINTER(_p)]),
+    "gn_known_pairs_destroy": (None, [_p]),
+    "gn_distmult_rank_f32": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "gn_distmult_topk_f32": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
     "gn_rgcn_weight_grad_workspace_bytes": (_sz, [_p, _i64, _i64]),
     "gn_rgcn_weight_grad_supported": (_int, [_p, _i64, _i64]),
     "gn_rgcn_weight_grad_f32": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _sz, _p]),
@@ -1330,6 +1334,88 @@ class NegativeSampler:
         h, self._h = getattr(self, "_h", None), None
         if h and _lib is not None:
             _lib.gn_negative_sampler_destroy(h)
+
+
+class KnownPairs:
+    """Owner of a gn_known_pairs handle: the union of one or more (edge_index [2,E], edge_type [E]) int64 lists on the GPU
+    (train + test, typically) as the filter of filtered ranking (multiRelaInnerProductDecoder.rank / top_k).  Duplicates
+    are allowed (set semantics); ids are validated here (IndexError).  One sorted partner row per (relation, u): O(E + R n)
+    memory, whatever n.  Built once; the ranking calls that use it neither synchronise nor allocate.
+
+        known = KnownPairs([(data.train_idx, data.train_et), (data.test_idx, data.test_et)], n_d, num_et)
+    """
+
+    def __init__(self, lists, num_nodes, num_et):
+        lib = load()
+        if isinstance(lists, tuple) and len(lists) == 2 and torch.is_tensor(lists[0]):
+            lists = [lists]
+        lists = list(lists)
+        if not lists:
+            raise ValueError("KnownPairs needs at least one (edge_index, edge_type) list")
+        rows, types = [], []
+        for edge_index, edge_type in lists:
+            require_gpu(edge_index, edge_type)
+            if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+                raise ValueError("edge_index must have shape [2, E], got {}".format(tuple(edge_index.shape)))
+            if edge_type.dim() != 1 or edge_type.shape[0] != edge_index.shape[1]:
+                raise ValueError("edge_type has {} entries for {} edges".format(edge_type.numel(), edge_index.shape[1]))
+            rows.append(i64_vec(edge_index))
+            types.append(i64_vec(edge_type))
+        device = rows[0].device
+        if any(t.device != device for t in rows + types):
+            raise ValueError("KnownPairs: every list must be on one device")
+        ei = torch.cat(rows, dim=1).contiguous() if len(rows) > 1 else rows[0].contiguous()
+        et = torch.cat(types).contiguous() if len(types) > 1 else types[0]
+        e = int(ei.shape[1])
+        h = _p()
+        with torch.cuda.device(device):
+            check(lib.gn_known_pairs_create(ei.data_ptr(), ei.data_ptr() + 8 * e, et.data_ptr(), e, int(num_nodes),
+                                            int(num_et), stream_ptr(device), C.byref(h)))
+        self._h, self.device, self.num_edges, self.num_nodes, self.num_et = h, device, e, int(num_nodes), int(num_et)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h and _lib is not None:
+            _lib.gn_known_pairs_destroy(h)
+
+
+def _known_handle(known, z, weight):
+    if known is None:
+        return None
+    if not isinstance(known, KnownPairs):
+        raise TypeError("`known` must be a KnownPairs, got {}".format(type(known).__name__))
+    if known.num_nodes != z.shape[0] or known.num_et != weight.shape[0] or known.device != z.device:
+        raise ValueError("KnownPairs was built for {} nodes / {} relations on {}; the call has {} / {} on {}".format(
+            known.num_nodes, known.num_et, known.device, z.shape[0], weight.shape[0], z.device))
+    return known._h
+
+
+def distmult_rank(z, edge_index, edge_type, weight, known=None):
+    """(greater, ties) int32 [E]: per pair (u, v, r) the non-known candidates v' != v scored above / equal to (u, v, r)
+    (gn_distmult_rank_f32).  `z` rows contiguous fp32."""
+    ei, u, v, e = edge_rows(edge_index)
+    et = i64_vec(edge_type)
+    if et.numel() != e:
+        raise ValueError("edge_type has {} entries for {} edges".format(et.numel(), e))
+    greater = torch.empty((e,), dtype=torch.int32, device=z.device)
+    ties = torch.empty((e,), dtype=torch.int32, device=z.device)
+    _call("gn_distmult_rank_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], u, v,
+          ptr(et), e, _known_handle(known, z, weight), ptr(greater), ptr(ties), ptr(error_flag(z.device)), stream_ptr(z.device))
+    return greater, ties
+
+
+def distmult_topk(z, nodes, edge_type, weight, k, known=None):
+    """(scores fp32 [Q, k], partners int64 [Q, k]) of the queries (nodes[q], edge_type[q]) (gn_distmult_topk_f32)."""
+    nodes, et = i64_vec(nodes), i64_vec(edge_type)
+    if nodes.dim() != 1 or et.dim() != 1 or nodes.numel() != et.numel():
+        raise ValueError("nodes and edge_type must be 1-D of one length, got {} and {}".format(tuple(nodes.shape), tuple(et.shape)))
+    q = int(nodes.numel())
+    scores = torch.empty((q, k), dtype=torch.float32, device=z.device)
+    ids = torch.empty((q, k), dtype=torch.int64, device=z.device)
+    _call("gn_distmult_topk_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], ptr(nodes),
+          ptr(et), q, int(k), _known_handle(known, z, weight), ptr(scores), ptr(ids), ptr(error_flag(z.device)),
+          stream_ptr(z.device))
+    return scores, ids
 
 
 class MetricsPlan:

@@ -239,3 +239,12 @@ struct gn_rgcn_plan {
     int64_t pair_blocks = 0;
     int pair_ok = 0;
 };
+
+// Known (relation, u, v) pairs of the filtered ranking kernels (negsample.hip builds it, distmult_rank.hip reads it): the
+// union of the caller's lists, sorted on the sampler's (relation << 40 | u * n + v) keys, as one row per (relation, u) of
+// sorted partner ids.  Duplicates stay (the kernels set bits: set semantics).  O(E + R * n) words.
+struct gn_known_pairs {
+    int64_t num_edges = 0, num_nodes = 0, num_relations = 0;
+    gn::DevBuf<int32_t> rowptr;     // [R * n + 1] first partner of row r * n + u
+    gn::DevBuf<int32_t> partners;   // [E] v, sorted inside a row
+};

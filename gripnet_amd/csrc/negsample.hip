@@ -69,6 +69,49 @@ __global__ void k_pair_keys(const int64_t* __restrict__ u, const int64_t* __rest
     }
 }
 
+// The radix sort of (relation << 40 | u * n + v) pair keys, shared by the sampler and the known-pair set of the ranking
+// kernels: `end_bit` bounds the key bits that can differ; `*scratch` is the caller's to free once the stream has passed.
+hipError_t sort_pair_keys(uint64_t* raw, uint64_t* sorted, int64_t E, int end_bit, void** scratch, hipStream_t st) {
+    size_t bytes = 0;
+    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, raw, sorted, (size_t)E, 0, end_bit, st);
+    if (e == hipSuccess) e = hipMalloc(scratch, bytes ? bytes : 1);
+    if (e == hipSuccess) e = rocprim::radix_sort_keys(*scratch, bytes, raw, sorted, (size_t)E, 0, end_bit, st);
+    return e;
+}
+
+// Known pairs: the relation comes with every edge (any order, duplicates allowed) instead of from a range list.
+__global__ void k_known_keys(const int64_t* __restrict__ u, const int64_t* __restrict__ v, const int64_t* __restrict__ et,
+                             int64_t E, int64_t n, int64_t R, uint64_t* __restrict__ keys, int32_t* __restrict__ err) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t uu = u[e], vv = v[e], rr = et[e];
+        if ((uint64_t)uu >= (uint64_t)n || (uint64_t)vv >= (uint64_t)n || (uint64_t)rr >= (uint64_t)R) {
+            atomicOr(err, 1);
+            keys[e] = ~0ull;
+            continue;
+        }
+        keys[e] = ((uint64_t)rr << 40) | (uint64_t)(uu * n + vv);
+    }
+}
+
+// rowptr[t] of row t = r * n + u: the first sorted key of (r, u), i.e. the first key >= (r << 40 | u * n); rowptr[R * n] = E
+__global__ void k_known_rows(const uint64_t* __restrict__ keys, int64_t E, int64_t n, int64_t rows, int32_t* __restrict__ rowptr) {
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t <= rows; t += (int64_t)gridDim.x * blockDim.x) {
+        if (t == rows) { rowptr[t] = (int32_t)E; continue; }
+        const uint64_t target = ((uint64_t)(t / n) << 40) | (uint64_t)((t % n) * n);
+        int64_t lo = 0, hi = E;
+        while (lo < hi) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (keys[mid] < target) lo = mid + 1; else hi = mid;
+        }
+        rowptr[t] = (int32_t)lo;
+    }
+}
+
+__global__ void k_known_partners(const uint64_t* __restrict__ keys, int64_t E, int64_t n, int32_t* __restrict__ partners) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x)
+        partners[e] = (int32_t)((keys[e] & ((1ull << 40) - 1)) % (uint64_t)n);
+}
+
 __global__ void k_sample_negatives(const uint64_t* __restrict__ keys, const int64_t* __restrict__ starts, int R,
                                    int64_t E, int64_t n, uint64_t seed, const uint64_t* __restrict__ seed_step, int64_t* __restrict__ out_u,
                                    int64_t* __restrict__ out_v, uint32_t* __restrict__ packed, int32_t* __restrict__ err) {
@@ -355,10 +398,7 @@ gn_status gn_negative_sampler_create(const int64_t* u, const int64_t* v, const i
         if (e2 != hipSuccess) { (void)hipFree(raw); return bail(gn::fail(GN_ERR_HIP, "hipMalloc failed")); }
         (void)hipMemsetAsync(err, 0, sizeof(int32_t), st);
         k_pair_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(u, v, s->starts.p, (int)R, E, N, raw, err);
-        size_t bytes = 0;
-        hipError_t e3 = rocprim::radix_sort_keys(nullptr, bytes, raw, s->keys.p, (size_t)E, 0, 64, st);
-        if (e3 == hipSuccess) e3 = hipMalloc(&scratch, bytes ? bytes : 1);
-        if (e3 == hipSuccess) e3 = rocprim::radix_sort_keys(scratch, bytes, raw, s->keys.p, (size_t)E, 0, 64, st);
+        hipError_t e3 = sort_pair_keys(raw, s->keys.p, E, 64, &scratch, st);
         if (e3 == hipSuccess && N < (1ll << 16) && R < (1ll << 16) && E < (1ll << 31) && !gn::fast_paths_disabled()) {
             e3 = s->keys32.alloc(E + 8);                     // (the task kernel stages whole 16-byte words)
             if (e3 == hipSuccess) e3 = s->rel16.alloc(E);
@@ -453,6 +493,72 @@ gn_status gn_negative_sampler_sample_stepped(const gn_negative_sampler* s, uint6
     GN_REQUIRE(out_u && out_v, "output pointers are null");
     if (packed_uv && s->num_nodes > 65535) return gn::fail(GN_ERR_UNSUPPORTED, "packed pairs hold node ids of 16 bits");
     return launch_sample(s, seed, out_u, out_v, packed_uv, error_flag, gn::as_stream(stream), step);
+}
+
+gn_status gn_known_pairs_create(const int64_t* u, const int64_t* v, const int64_t* edge_type, int64_t E, int64_t N, int64_t R,
+                                void* stream, gn_known_pairs** out) {
+    GN_REQUIRE(out != nullptr, "known-pairs output pointer is null");
+    *out = nullptr;
+    GN_REQUIRE(R >= 1 && E >= 0 && N >= 1, "bad size (R=%lld, E=%lld, N=%lld)", (long long)R, (long long)E, (long long)N);
+    GN_REQUIRE(E == 0 || (u && v && edge_type), "edge pointers are null");
+    if (N >= (1ll << 20) || R >= (1ll << 23) || R * N >= (1ll << 31) || E >= (1ll << 31))
+        return gn::fail(GN_ERR_UNSUPPORTED, "known pairs hold 2^20 nodes, 2^23 relations, 2^31 rows (R * n) and 2^31 pairs at most");
+    hipStream_t st = gn::as_stream(stream);
+    gn_known_pairs* k = new gn_known_pairs();
+    k->num_edges = E; k->num_nodes = N; k->num_relations = R;
+    const int64_t rows = R * N;
+    uint64_t *raw = nullptr, *keys = nullptr;
+    int32_t* err = nullptr;
+    void* scratch = nullptr;
+    int32_t bad = 0;
+    hipError_t e = k->rowptr.alloc(rows + 1);
+    if (e == hipSuccess) e = k->partners.alloc(E);
+    if (e == hipSuccess && E > 0) {
+        int end_bit = 40;                                     // the bits a valid key can set
+        while ((1ll << (end_bit - 40)) < R) ++end_bit;
+        e = hipMalloc(reinterpret_cast<void**>(&raw), E * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&keys), E * sizeof(uint64_t));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&err), sizeof(int32_t));
+        if (e == hipSuccess) e = hipMemsetAsync(err, 0, sizeof(int32_t), st);
+        if (e == hipSuccess) {
+            k_known_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(u, v, edge_type, E, N, R, raw, err);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = sort_pair_keys(raw, keys, E, end_bit, &scratch, st);
+        if (e == hipSuccess) {
+            k_known_partners<<<gn::stream_grid(E, 256), 256, 0, st>>>(keys, E, N, k->partners.p);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    }
+    if (e == hipSuccess) {
+        if (E > 0) k_known_rows<<<gn::stream_grid(rows + 1, 256), 256, 0, st>>>(keys, E, N, rows, k->rowptr.p);
+        else k_known_rows<<<gn::stream_grid(rows + 1, 256), 256, 0, st>>>(nullptr, 0, N, rows, k->rowptr.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (raw) (void)hipFree(raw);
+    if (keys) (void)hipFree(keys);
+    if (err) (void)hipFree(err);
+    if (scratch) (void)hipFree(scratch);
+    if (e != hipSuccess) {
+        gn_known_pairs_destroy(k);
+        return gn::fail(GN_ERR_HIP, "known-pairs construction failed: %s", hipGetErrorString(e));
+    }
+    if (bad) {
+        gn_known_pairs_destroy(k);
+        return gn::fail(GN_ERR_INDEX_RANGE, "known pairs: a node id outside [0,%lld) or a relation id outside [0,%lld)",
+                        (long long)N, (long long)R);
+    }
+    *out = k;
+    return GN_OK;
+}
+
+void gn_known_pairs_destroy(gn_known_pairs* k) {
+    if (!k) return;
+    k->rowptr.release();
+    k->partners.release();
+    delete k;
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@ import torch
 from torch.nn import Module, Parameter
 
 from . import _hip
+from ._hip import KnownPairs
 from .autograd import ClassLogitsFn, DistMultFn, SoftmaxRowsFn, recording
 
 
@@ -180,6 +181,37 @@ class multiRelaInnerProductDecoder(Module):
                     raise
                 self._find(edge_index, edge_type).plan = False
         return _hip.distmult_any(z, edge_index, edge_type, self.weight, sigmoid, out)
+
+    def _eval_operands(self, z, *index):
+        _hip.require_gpu(z, *index, self.weight)
+        if z.dim() != 2 or z.shape[1] != self.in_dim:
+            raise ValueError("expected {} features, got shape {}".format(self.in_dim, tuple(z.shape)))
+        return _hip.f32_rows(z.detach()), self.weight.detach()
+
+    def rank(self, z, edge_index, edge_type, known=None):
+        """Filtered ranking of the pairs (u, v, r) = (edge_index[0], edge_index[1], edge_type) against every candidate
+        partner: ``(greater, ties)``, int32 [E] each, the candidates v' != v whose (r, u, v') is not in `known` (a
+        KnownPairs, None: no filter) with logit s(u, v', r) > s(u, v, r) and == s(u, v, r).  Logits, not sigmoids (fp32
+        sigmoid saturates to 1.0 above ~17 and would manufacture ties).  The true pair's logit is the scan's own value for
+        column v.  Tail side; DistMult is symmetric, so the head-side ranks of a list are the tail-side ranks of the
+        flipped list (``edge_index.flip(0)``) - with the bidirectional pose lists, both sides are already in the list.
+        No autograd, no host synchronisation: an id out of range gives -1 / -1 and the IndexError at the next check
+        (``utils.ranking_metrics`` / ``_hip.raise_if_index_errors``).  ``utils.ranking_metrics`` turns the counts into
+        MRR and Hits@k."""
+        z, w = self._eval_operands(z, edge_index, edge_type)
+        with torch.no_grad():
+            return _hip.distmult_rank(z, edge_index, edge_type, w, known)
+
+    def top_k(self, z, nodes, edge_type, k, known=None):
+        """The `k` (1..64) best partners v of every query (u, r) = (nodes[q], edge_type[q]) that are not in `known`:
+        ``(scores, partners)``, fp32 logits [Q, k] and int64 ids [Q, k], by logit descending then id ascending, padded
+        with -inf / -1 when fewer than k candidates remain.  No autograd, no host synchronisation (ids out of range:
+        NaN / -1 and the IndexError at the next check)."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("k must be an integer in [1, 64], got {!r}".format(k))
+        z, w = self._eval_operands(z, nodes, edge_type)
+        with torch.no_grad():
+            return _hip.distmult_topk(z, nodes, edge_type, w, int(k), known)
 
     def reset_parameters(self):
         self.weight.data.normal_(std=1 / np.sqrt(self.in_dim))                   # decoder.py:25-26

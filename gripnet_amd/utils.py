@@ -237,6 +237,32 @@ def relation_metrics(pos_score: torch.Tensor, neg_score: torch.Tensor, range_lis
     return link_metrics(pos_score, neg_score, range_list)
 
 
+def ranking_metrics(greater: torch.Tensor, ties: torch.Tensor, edge_type: torch.Tensor, num_et: int, hits=(1, 3, 10)):
+    """Filtered MRR and Hits@k from the counts of ``multiRelaInnerProductDecoder.rank``, with the realistic rank
+    ``1 + greater + ties / 2`` (ties share the mean of their places).  Returns a dict of float64 tensors: ``mrr`` and
+    ``hits@k`` per relation ([num_et]; NaN for a relation without queries) and ``mrr_all`` / ``hits@k_all`` over every
+    query (micro average).  Plain torch on [E] vectors (works on CPU tensors too); on GPU tensors it is the synchronising
+    point where an out-of-range id seen by the ranking kernels becomes an IndexError (as in relation_metrics)."""
+    if greater.is_cuda:
+        from ._hip import raise_if_index_errors
+        raise_if_index_errors(greater.device)
+    if greater.shape != ties.shape or greater.dim() != 1 or edge_type.shape != greater.shape:
+        raise ValueError("greater, ties and edge_type must be [E] vectors of one length")
+    rank = 1.0 + greater.to(torch.float64) + 0.5 * ties.to(torch.float64)
+    et = edge_type.to(device=rank.device, dtype=torch.int64)
+    count = torch.zeros(num_et, dtype=torch.float64, device=rank.device).index_add_(0, et, torch.ones_like(rank))
+
+    def per_relation(x):
+        return torch.zeros(num_et, dtype=torch.float64, device=rank.device).index_add_(0, et, x) / count
+
+    out = {"mrr": per_relation(1.0 / rank), "mrr_all": (1.0 / rank).mean()}
+    for k in hits:
+        hit = (rank <= k).to(torch.float64)
+        out["hits@{}".format(k)] = per_relation(hit)
+        out["hits@{}_all".format(k)] = hit.mean()
+    return out
+
+
 def link_loss(pos_score: torch.Tensor, neg_score: torch.Tensor, eps: float = EPS) -> torch.Tensor:
     """``-log(pos + EPS).mean() - log(1 - neg + EPS).mean()``: the training loss of GripNet-pose.py:140-142 as one launch
     forward and one backward (gn_link_loss_*), differentiable.  The reference spells the expression out with torch ops

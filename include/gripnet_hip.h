@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 154 /* 0.1.48 */
+#define GN_VERSION 155 /* 0.1.49 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -547,6 +547,36 @@ GN_API gn_status gn_negative_sampler_sample_packed(const gn_negative_sampler* sa
  * one sampler per stream. */
 GN_API gn_status gn_negative_sampler_sample_stepped(const gn_negative_sampler* sampler, uint64_t seed, uint64_t* step, int64_t* out_u,
                                              int64_t* out_v, uint32_t* packed_uv, int32_t* error_flag, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Filtered ranking and top-k partner retrieval for the DistMult decoder (link-prediction evaluation: filtered MRR / Hits@k).
+ * A query is a row (u, r); its candidate scores are the logits s(v) = sum_k z[u,k] D[r,k] z[v,k] for every v in [0, n).
+ *
+ * gn_known_pairs: the union of one or more (u, v, relation) lists (train + test, typically), validated and sorted once on
+ * the negative sampler's (relation, u * n + v) keys: a row of sorted partners per (relation, u), O(E + R * n) words.
+ * Duplicates are allowed (set semantics).  Ids outside [0, n) / [0, R): GN_ERR_INDEX_RANGE.  Synchronises `stream`.
+ * Holds n < 2^20, R < 2^23, R * n < 2^31 and E < 2^31 (GN_ERR_UNSUPPORTED beyond). */
+typedef struct gn_known_pairs gn_known_pairs;
+GN_API gn_status gn_known_pairs_create(const int64_t* u, const int64_t* v, const int64_t* edge_type, int64_t num_edges,
+                                int64_t num_nodes, int64_t num_relations, void* stream, gn_known_pairs** known);
+GN_API void gn_known_pairs_destroy(gn_known_pairs* known);
+/* Per query e = (u[e], v[e], edge_type[e]): greater[e] / ties[e] = the candidates v' != v[e] whose (r, u, v') is not a
+ * known pair (known may be NULL: no filter) with s(v') > s(v[e]) / s(v') == s(v[e]).  The true score is the scan's own
+ * value for column v[e] (same operands, same fp32 FMA order on the matrix cores).  No [Q, n] buffer, no float atomics,
+ * no host synchronisation.  A query with an id out of range gets -1 / -1 and sets bit 0 of *error_flag.  num_features
+ * <= 128; `known` must have been built for the same num_nodes and num_relations. */
+GN_API gn_status gn_distmult_rank_f32(const float* z, int64_t ld_z, int64_t num_nodes, int64_t num_features, const float* d,
+                               int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* v, const int64_t* edge_type,
+                               int64_t num_queries, const gn_known_pairs* known /* nullable */, int32_t* greater, int32_t* ties,
+                               int32_t* error_flag, void* stream);
+/* Per query e = (u[e], edge_type[e]): the k (1..64) best candidates that are not known pairs, by logit descending then id
+ * ascending: scores[e * k + j] (fp32 logits) and ids[e * k + j]; padded with -inf / -1 when fewer than k candidates with a
+ * score above -inf remain (NaN scores never enter).  A query with an id out of range gets NaN / -1 and sets bit 0 of
+ * *error_flag. */
+GN_API gn_status gn_distmult_topk_f32(const float* z, int64_t ld_z, int64_t num_nodes, int64_t num_features, const float* d,
+                               int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* edge_type, int64_t num_queries,
+                               int64_t k, const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids,
+                               int32_t* error_flag, void* stream);
 
 /* Independent small products in ONE launch.  Between gn_dense_batch_begin() and gn_dense_batch_end(stream) (per host thread,
  * not nested) the calls that carry GN_GEMM_JOIN_BATCH / GN_XTG_JOIN_BATCH - those of gn_gemm_f32 that take the deep-and-narrow kernel (a single product with at most 64 rows or 32 columns
