@@ -25,7 +25,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 156                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 157                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -50,6 +50,7 @@ SIGNATURES = {
     "gn_graph_transform_fusable": (_int, [_p, _i64, _i64]),
     "gn_graph_plan_build_blocked": (_int, [_p, _i64, _p]),
     "gn_graph_plan_blocked_cols": (_i64, [_p]),
+    "gn_graph_blocked_applicable": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _i64]),
     "gn_graph_plan_build_transpose": (_int, [_p, _p]),
     "gn_graph_aggregate_t_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p]),
     "gn_xtg_wide_supported": (_int, [_i64, _i64, _i64]),
@@ -65,6 +66,7 @@ SIGNATURES = {
     "gn_rgcn_plan_input_edges": (_i64, [_p]),
     "gn_rgcn_workspace_bytes": (_sz, [_p, _i64, _i64, _i64, _int]),
     "gn_rgcn_forward_path": (_int, [_p, _i64, _i64, _i64, _int]),
+    "gn_rgcn_forward_choice": (_int, [_p, _p, _i64, _i64, _i64, _i64, _int, C.POINTER(_sz)]),
     "gn_cast_bf16": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p]),
     "gn_graph_aggregate_bf16": (_int, [_p, _p, _i64, _i64, _p, _int, _p, _i64, _p, _p]),
     "gn_rgcn_forward_f32": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _int, _int, _p, _i64, _p, _p, _p, _sz, _p]),
@@ -716,10 +718,11 @@ class GraphPlan:
     def blocked_cols(self) -> int:
         return int(load().gn_graph_plan_blocked_cols(self._h))
 
-    def blocked_ok(self, fin: int, fout: int, x: torch.Tensor) -> bool:
-        """True when gn_graph_aggregate_f32(weight=W) runs on the source-blocked kernels for this input."""
-        return (fout in (16, 32) and fout <= self.blocked_cols and fin in (16, 32, 64) and ld(x) % 4 == 0
-                and x.data_ptr() % 16 == 0)
+    def blocked_ok(self, x: torch.Tensor, weight: torch.Tensor, bias, out: torch.Tensor) -> bool:
+        """True when gn_graph_aggregate_f32(x, weight=W, bias, out) runs on the source-blocked kernels (the library's own
+        answer: it sees the alignment of out and bias as well as of x)."""
+        return bool(load().gn_graph_blocked_applicable(self._h, x.data_ptr(), ld(x), x.shape[1], weight.data_ptr(), weight.shape[1],
+                                                       None if bias is None else bias.data_ptr(), out.data_ptr(), ld(out)))
 
     def transform_ok(self, fin: int, fout: int, x: torch.Tensor) -> bool:
         """True when gn_graph_aggregate_f32(weight=W) contracts with W in the gather's launch for this plan and input."""
@@ -860,8 +863,10 @@ class RgcnPlan:
             _recorder.keep.append(ei)
         return dw
 
-    def _workspace(self, fin, fout, bases, flags=0):
-        need = int(load().gn_rgcn_workspace_bytes(self._h, fin, fout, bases, flags))
+    def _workspace(self, x, fin, fout, bases, flags=0):
+        need = C.c_size_t(0)
+        load().gn_rgcn_forward_choice(self._h, x.data_ptr(), ld(x), fin, fout, bases, flags, C.byref(need))   # (x: its alignment picks the kernel)
+        need = int(need.value)
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
         return self._ws, need
@@ -871,9 +876,12 @@ class RgcnPlan:
         """Arithmetic and kernel-choice bits of gn_rgcn_forward_f32."""
         return (GN_RGCN_ARITH_FAST if fast else 0) | (RGCN_PATHS[path] << GN_RGCN_PATH_SHIFT)
 
-    def path(self, fin, fout, bases, fast=False, path="auto"):
-        """Name of the kernel a forward with these shapes and flags takes."""
-        code = int(load().gn_rgcn_forward_path(self._h, fin, fout, bases, self.mode_flags(fast, path)))
+    def path(self, fin, fout, bases, fast=False, path="auto", x=None):
+        """Name of the kernel a forward with these shapes and flags takes (on `x` when given, else on an aligned input)."""
+        if x is not None:
+            code = int(load().gn_rgcn_forward_choice(self._h, x.data_ptr(), ld(x), fin, fout, bases, self.mode_flags(fast, path), None))
+        else:
+            code = int(load().gn_rgcn_forward_path(self._h, fin, fout, bases, self.mode_flags(fast, path)))
         return {v: k for k, v in RGCN_PATHS.items()}.get(code, "?")
 
     def forward(self, x, basis, att, root, bias, relu, out, partial=False, side=None, fast=False, path="auto", x_planes=None,
@@ -884,7 +892,7 @@ class RgcnPlan:
         mode = self.mode_flags(fast, path)
         if basis_transposed:
             fout = basis.shape[1]
-            ws, need = self._workspace(x.shape[1], fout, basis.shape[0], mode)
+            ws, need = self._workspace(x, x.shape[1], fout, basis.shape[0], mode)
             sc = side_copy(side)
             flags = (GN_RGCN_PARTIAL if partial else 0) | mode | GN_RGCN_BASIS_TRANSPOSED
             _call("gn_rgcn_forward_f32", self._h, ptr(x), ld(x), x.shape[1], ptr(basis), ptr(att), basis.shape[0],
@@ -892,7 +900,7 @@ class RgcnPlan:
                   ptr(out), ld(out), _ref(sc), None if x_planes is None else x_planes.buf.data_ptr(), ptr(ws), need,
                   stream_ptr(x.device))
             return out
-        ws, need = self._workspace(x.shape[1], basis.shape[2], basis.shape[0], mode)
+        ws, need = self._workspace(x, x.shape[1], basis.shape[2], basis.shape[0], mode)
         sc = side_copy(side)
         flags = (GN_RGCN_PARTIAL if partial else 0) | mode
         _call("gn_rgcn_forward_f32", self._h, ptr(x), ld(x), x.shape[1], ptr(basis), ptr(att), basis.shape[0],

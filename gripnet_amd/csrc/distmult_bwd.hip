@@ -1140,9 +1140,12 @@ extern "C" gn_status gn_distmult_backward_loss_packed_f32(const float* z, int64_
                                                           const float* dz_add, int64_t ld_dz_add, const float* dd_add, int64_t ld_dd_add,
                                                           void* workspace, size_t workspace_bytes, void* stream) {
     GN_REQUIRE(loss != nullptr && (e == 0 || sigmoid_scores), "the loss source and the forward's probabilities are required");
-    GN_REQUIRE((!dz_add || (ld_dz_add >= f && ld_dz_add % 4 == 0 && (reinterpret_cast<uintptr_t>(dz_add) & 15) == 0)) &&
-               (!dd_add || (ld_dd_add >= f && ld_dd_add % 4 == 0 && (reinterpret_cast<uintptr_t>(dd_add) & 15) == 0)) && (e > 0 || (!dz_add && !dd_add)),
-               "addends: 16-byte aligned rows of at least num_features floats, and a non-empty list");
+    GN_REQUIRE((!dz_add || ld_dz_add >= f) && (!dd_add || ld_dd_add >= f) && (e > 0 || (!dz_add && !dd_add)),
+               "addends: rows of at least num_features floats, and a non-empty list");
+    // a legal layout the combine launch cannot read (its 16-byte accesses): the caller adds the sums itself
+    if ((dz_add && (ld_dz_add % 4 != 0 || (reinterpret_cast<uintptr_t>(dz_add) & 15) != 0)) ||
+        (dd_add && (ld_dd_add % 4 != 0 || (reinterpret_cast<uintptr_t>(dd_add) & 15) != 0)))
+        return gn::fail(GN_ERR_UNSUPPORTED, "addends: the combine launch reads 16-byte aligned rows with ld %% 4 == 0 (call without addends and add)");
     GN_REQUIRE(e == 0 || (packed_uv && rel16), "packed pairs or relation ids are null");
     GN_REQUIRE(n <= 65536 && r <= 65536, "packed pairs hold ids of 16 bits");
     return backward_impl(z, ld_z, n, f, EdgeSrc{nullptr, nullptr, nullptr, packed_uv, rel16}, d, ld_d, r, e, nullptr, dz, ld_dz, dd,

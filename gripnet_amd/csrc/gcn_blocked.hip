@@ -299,9 +299,15 @@ void launch_transform(const TransArgs& t, int cw, hipStream_t st) {
 
 }  // namespace
 
-// True when gn_graph_aggregate_f32 takes the LDS-staged path for these shapes.
-bool gn_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout) {
+// True when gn_graph_aggregate_f32 takes the LDS-staged path for these shapes and operands: the gather writes out (and
+// reads bias) in column groups of blk_cw floats, so an output slice at an odd column or with an odd stride keeps the
+// wave-per-row kernels.
+bool gn_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout,
+                           const float* bias, const float* out, int64_t ld_out) {
     if (!plan->blk_ok || blocked_disabled()) return false;
+    const int cw = plan->blk_cw;
+    if ((ld_out % cw) != 0 || (reinterpret_cast<uintptr_t>(out) % (4 * cw)) != 0 ||
+        (bias && (reinterpret_cast<uintptr_t>(bias) % (4 * cw)) != 0)) return false;
     if (!(fout == 16 || fout == 32) || fout > plan->blk_cols) return false;
     if (w) {
         if (!(fin == 16 || fin == 32 || fin == 64)) return false;
@@ -359,6 +365,12 @@ gn_status gn_blocked_aggregate(const gn_graph_plan* plan, const float* x, int64_
 // Adds the LDS-staged encoding to a GCN plan whose stored weights are all 1 (self loops included), for layers of up to
 // `cols` output features (16 or 32).  Not an error when the graph does not qualify: the plan then keeps using the
 // wave-per-row kernels (gn_graph_plan_blocked_cols returns 0).  Copies the CSR to the host and synchronises.
+extern "C" int gn_graph_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,
+                                           const float* weight, int64_t out_features, const float* bias, const float* out,
+                                           int64_t ld_out) {
+    return plan && gn_blocked_applicable(plan, x, ld_x, num_features, weight, out_features, bias, out, ld_out) ? 1 : 0;
+}
+
 extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t cols, void* stream) {
     GN_REQUIRE(plan != nullptr, "plan is null");
     GN_REQUIRE(cols == 16 || cols == 32, "LDS-staged plans are built for layers of 16 or 32 output features, got %lld", (long long)cols);

@@ -3,7 +3,8 @@
 #include "aggregate.cuh"
 
 // gcn_blocked.hip: the LDS-staged, source-blocked path
-bool gn_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout);
+bool gn_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout,
+                           const float* bias, const float* out, int64_t ld_out);
 gn_status gn_blocked_aggregate(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w,
                                int64_t fout, const float* bias, int relu, float* out, int64_t ld_out,
                                const gn_side_copy& side, hipStream_t st);
@@ -52,7 +53,7 @@ extern "C" gn_status gn_graph_aggregate_f32(const gn_graph_plan* plan, const flo
             s = gn_split_planes_f32(a.side.dst, a.side.ld_dst, a.side.rows, a.side.cols, planes->col_side, planes, stream);
         return s;
     };
-    if (gn_blocked_applicable(plan, xw, ld_xw, num_features, weight, width))
+    if (gn_blocked_applicable(plan, xw, ld_xw, num_features, weight, width, bias, out, ld_out))
         return then_split(gn_blocked_aggregate(plan, xw, ld_xw, num_features, weight, width, bias, relu, out, ld_out, a.side,
                                                gn::as_stream(stream)));
     if (weight && gn::mfma_fusable(num_features, out_features, plan->rows, plan->nnz) && (ld_xw % 4) == 0 && gn::aligned16(xw))

@@ -44,11 +44,13 @@ size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
 // Which kernel serves these shapes under these flags (GN_RGCN_PATH_*): the destination-major kernel (three-term bf16
 // splits by default, two-term under GN_RGCN_ARITH_FAST), else the LDS-accumulator / general kernels on the fp32 matrix
-// instruction.  A forced kernel that does not cover the shapes is not taken.
-int select_path(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases, int flags, const void* basis) {
+// instruction.  A forced kernel that does not cover the shapes is not taken.  x == NULL: an aligned x (the queries).
+int select_path(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases, int flags, const void* basis,
+                const float* x = nullptr, int64_t ld_x = 0) {
     const int forced = (flags >> GN_RGCN_PATH_SHIFT) & 7;
     const bool pair_ok = gn_rgcn_pair_applicable(plan, fin, fout, bases) && (reinterpret_cast<uintptr_t>(basis) & 15) == 0;
-    const bool lds_ok = gn_rgcn_fast_applicable(plan, fin, fout, bases);
+    const bool lds_ok = gn_rgcn_fast_applicable(plan, fin, fout, bases) &&
+                        (!x || (ld_x % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0));    // (16-byte row loads)
     if (forced == GN_RGCN_PATH_PAIR && pair_ok) return GN_RGCN_PATH_PAIR;
     if (forced == GN_RGCN_PATH_LDS && lds_ok) return GN_RGCN_PATH_LDS;
     const bool basis_ok = gn_rgcn_basis_applicable(plan, fin, fout, bases);
@@ -117,6 +119,15 @@ int gn_rgcn_forward_path(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, in
     return select_path(plan, fin, fout, bases, flags, nullptr);
 }
 
+int gn_rgcn_forward_choice(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin, int64_t fout, int64_t bases,
+                           int flags, size_t* workspace_bytes) {
+    if (workspace_bytes) *workspace_bytes = 0;
+    if (!plan || fin <= 0 || fout <= 0 || bases <= 0) return -1;
+    const int path = select_path(plan, fin, fout, bases, flags, nullptr, x, ld_x);
+    if (workspace_bytes) *workspace_bytes = path_workspace_bytes(plan, fin, fout, bases, path);
+    return path;
+}
+
 gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin,
                               const float* basis, const float* att, int64_t bases, const float* root,
                               const float* bias, int64_t fout, int relu, int flags, float* out, int64_t ld_out,
@@ -134,7 +145,7 @@ gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, int64_t 
     // the workspace is checked against the kernel THIS call takes (a forced general or table path, or a basis pointer the
     // destination-major kernel cannot use, needs its own scratch whatever gn_rgcn_workspace_bytes said for the
     // default choice)
-    const int path = select_path(plan, fin, fout, bases, flags, basis);
+    const int path = select_path(plan, fin, fout, bases, flags, basis, x, ld_x);
     if ((flags & GN_RGCN_BASIS_TRANSPOSED) && path != GN_RGCN_PATH_PAIR)
         return gn::fail(GN_ERR_UNSUPPORTED, "GN_RGCN_BASIS_TRANSPOSED: only the destination-major kernel reads a transposed basis (pass a transposed copy)");
     const size_t need = path_workspace_bytes(plan, fin, fout, bases, path);

@@ -114,7 +114,7 @@ class myGCN(Module):
                 xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.float32, device=x.device)
                 _hip.gemm(x, self.weight, xw, fast=self.arithmetic == "fast")
             return plan.aggregate_bf16(xw, self.bias, relu, out, side)
-        if self.weight.is_contiguous() and (plan.blocked_ok(self.in_channels, self.out_channels, x) or
+        if self.weight.is_contiguous() and (plan.blocked_ok(x, self.weight, self.bias, out) or
                                             plan.transform_ok(self.in_channels, self.out_channels, x)):
             # A_norm (x W) = (A_norm x) W: the contraction of layers.py:73 runs on the aggregated row
             y = plan.aggregate(x, self.bias, relu, out, side, weight=self.weight, planes=planes)

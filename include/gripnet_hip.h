@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 156 /* 0.1.50 */
+#define GN_VERSION 157 /* 0.1.51 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -146,13 +146,19 @@ GN_API int gn_graph_transform_fusable(const gn_graph_plan* plan, int64_t in_feat
  * owns its destination rows outright - no partial sums, no combine pass.  gn_graph_aggregate_f32 takes this path (two
  * launches: the exact-fp32 transform writing T column-group-major into scratch the PLAN owns, then the gather from
  * LDS; fixed summation order) when the plan has the encoding and the shapes are covered: out_features 16 or 32 <= cols,
- * with `weight` num_features in {16,32,64}, x 16-byte aligned with ld % 4 == 0.  Calls on one plan must be
+ * with `weight` num_features in {16,32,64}, x 16-byte aligned with ld % 4 == 0, out and bias aligned to the gather's column
+ * groups (gn_graph_blocked_applicable).  Calls on one plan must be
  * stream-ordered (the scratch table).  Graphs that do not qualify (weighted, `improved`, fewer than 4,096 nodes or
  * fewer than 16 stored edges per node, too many nodes for one column in LDS) keep the wave-per-row kernels and the call
  * returns GN_OK; gn_graph_plan_blocked_cols tells (0 = not built).  Copies the CSR to the host once, schedules it there
  * and synchronises `stream`: meant for graphs that are kept (the Python layer builds it only for `cached=True`). */
 GN_API gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t cols, void* stream);
 GN_API int64_t gn_graph_plan_blocked_cols(const gn_graph_plan* plan);
+/* Whether gn_graph_aggregate_f32 with these operands takes the LDS-staged path (it also needs `out`, `ld_out` and `bias`
+ * aligned to the gather's column groups; other operands keep the wave-per-row kernels).  Launches nothing. */
+GN_API int gn_graph_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,
+                                       const float* weight, int64_t out_features, const float* bias, const float* out,
+                                       int64_t ld_out);
 
 /* bf16 STORAGE of the gathered table (the reference is fp32 throughout, this is the build's own
  * reduced-traffic variant for the node-classification suite): gn_cast_bf16 rounds x W to bf16 once,
@@ -292,9 +298,15 @@ GN_API size_t gn_host_scratch_release(void);
 
 /* Bytes of caller-provided scratch a gn_rgcn_forward_f32 call with these shapes and flags needs: none on the
  * destination-major kernel, W_r and the slabs of the LDS-accumulator kernel, a slab of rows (<= 256 MB) and the stacked
- * weights on the general path (independent of R and N), the [R, N, out] table on the table path.  (The forward checks the workspace against the kernel IT takes and refuses a smaller one.) */
+ * weights on the general path (independent of R and N), the [R, N, out] table on the table path.  (The forward checks the workspace against the kernel IT takes and refuses a smaller one.)
+ * The answer is for an x that is 16-byte aligned with ld % 4 == 0; gn_rgcn_forward_choice answers for a given x (the
+ * LDS-accumulator kernel reads aligned rows only: a column slice of a concat at an odd offset takes the general kernel). */
 GN_API size_t gn_rgcn_workspace_bytes(const gn_rgcn_plan* plan, int64_t in_features, int64_t out_features,
                                int64_t num_bases, int flags);
+/* The kernel (GN_RGCN_PATH_*) a gn_rgcn_forward_f32 call on this x takes, and (workspace_bytes, nullable) the scratch it needs;
+ * -1 for a null plan or non-positive sizes. */
+GN_API int gn_rgcn_forward_choice(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t in_features,
+                                  int64_t out_features, int64_t num_bases, int flags, size_t* workspace_bytes);
 
 #define GN_RGCN_PARTIAL 1        /* flags of gn_rgcn_forward_f32 */
 #define GN_RGCN_ARITH_FAST 4     /* dense products on two-term bf16 splits (<= 2^-16 relative per product) instead of the
@@ -485,7 +497,9 @@ GN_API gn_status gn_distmult_backward_planned_f32(const gn_distmult_bwd_plan* pl
  * trip through memory disappear.  upstream: the loss's one upstream gradient on the device (NULL: 1).
  * dz_addend / dd_addend (packed form): the gradients of the SAME z and D from the step's other list (the positives' call): added
  * where this call stores its sums (dz = sums + dz_addend, may alias dz), so that the two lists' gradients need no adding launch;
- * GN_ERR_UNSUPPORTED where the two reductions do not share their combine launch (call without addends and add). */
+ * GN_ERR_UNSUPPORTED where the two reductions do not share their combine launch, or where an addend's rows are not 16-byte
+ * aligned with a leading dimension % 4 == 0 (call without addends and add); GN_ERR_INVALID_ARG for an addend's leading
+ * dimension below num_features or addends with an empty list. */
 typedef struct gn_link_loss_grad {
     const float* upstream;
     float eps;

@@ -23,7 +23,7 @@ def _rel_err(y, ref):
 
 # ---- GCN-style layer (myGCN, gripnet/layers.py:52-100) -----------------------------------------------------------------
 GCN_EDGE_CASES = [(4095, 16, 16, 16), (4096, 16, 16, 16), (4096, 32, 16, 17), (5000, 64, 32, 20), (1, 16, 8, 0),
-                  (700, 24, 20, 3), (20000, 32, 16, 70), (33000, 16, 16, 8)]
+                  (700, 24, 20, 3), (20000, 32, 16, 70), (33000, 16, 16, 8), (4100, 64, 17, 20), (700, 15, 16, 24), (300, 33, 17, 5)]
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -55,7 +55,8 @@ def test_fuzz_gcn_layer(gpu, seed):
 
 # ---- relational layer (myRGCN, gripnet/layers.py:165-197) --------------------------------------------------------------
 RGCN_EDGE_CASES = [(768, 48, 32, 32, 8), (769, 48, 32, 32, 8), (645, 64, 32, 17, 3), (645, 64, 32, 16, 3), (256, 16, 4, 1, 1),
-                   (257, 32, 44, 32, 40), (1, 16, 8, 1, 1), (1000, 48, 64, 5, 8)]
+                   (257, 32, 44, 32, 40), (1, 16, 8, 1, 1), (1000, 48, 64, 5, 8), (900, 17, 33, 33, 6), (900, 13, 32, 40, 5),
+                   (900, 112, 17, 17, 3)]
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
@@ -90,7 +91,8 @@ def test_fuzz_relational_layer(gpu, seed):
 
 
 # ---- decoders (gripnet/decoder.py:19-23,38-45) -------------------------------------------------------------------------
-DEC_EDGE_CASES = [(645, 80, 50), (480, 80, 7), (481, 80, 7), (9000, 16, 2), (12, 128, 1), (2, 4, 1), (1000, 96, 50), (300, 20, 7)]
+DEC_EDGE_CASES = [(645, 80, 50), (480, 80, 7), (481, 80, 7), (9000, 16, 2), (12, 128, 1), (2, 4, 1), (1000, 96, 50), (300, 20, 7),
+                  (645, 45, 7), (4100, 127, 5), (37, 1, 3)]
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])
