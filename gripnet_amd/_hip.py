@@ -7,6 +7,7 @@ library is missing or a tensor is not on the GPU the call raises.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import os
 import threading
 
@@ -25,7 +26,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 157                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 158                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -127,6 +128,8 @@ SIGNATURES = {
     "gn_link_metrics_planned_f32": (_int, [_p, _p, _p, _p, _p, _sz, _p]),
     "gn_link_metrics_workspace_bytes": (_sz, [_i64, _i64]),
     "gn_link_metrics_f32": (_int, [_p, _p, _p, _i64, _i64, _p, _p, _sz, _p]),
+    "gn_class_metrics_workspace_bytes": (_sz, [_i64, _i64]),
+    "gn_class_metrics_f32": (_int, [_p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 
@@ -933,8 +936,8 @@ def error_flag(device) -> torch.Tensor:
 
 
 def raise_if_index_errors(device=None):
-    """Synchronising check of the decoder error word; raises IndexError like the reference's
-    advanced indexing would (gripnet/decoder.py:20)."""
+    """Synchronising check of the error word; raises IndexError like the reference's advanced indexing would
+    (gripnet/decoder.py:20; for class ids, the loss line score[range(n), classes] of the NC drivers)."""
     for key, flag in list(_error_flags.items()):
         if device is not None and (device.type, device.index) != key:
             continue
@@ -945,7 +948,12 @@ def raise_if_index_errors(device=None):
                 raise RuntimeError("one-shot exchange: a peer's partial sums did not arrive within the timeout")
             if bits & 2:
                 raise RuntimeError("negative sampler: a relation's positive pairs leave no pair to draw")
-            raise IndexError("DistMult decoder saw an edge endpoint or relation id outside its table")
+            found = []
+            if bits & 1:
+                found.append("DistMult decoder saw an edge endpoint or relation id outside its table")
+            if bits & 8:
+                found.append("class metrics saw a class id outside [0, num_class) (true or predicted)")
+            raise IndexError("; ".join(found))
 
 
 def distmult(z, u_v, edge_type, weight, sigmoid, out):
@@ -1437,6 +1445,76 @@ def link_metrics(pos_score, neg_score, range_list):
     ws = plan.workspace()
     _call("gn_link_metrics_planned_f32", plan._h, ptr(pos), ptr(neg), ptr(out), ptr(ws), ws.numel(), stream_ptr(pos.device))
     return out[0], out[1], out[2]
+
+
+MAX_CLASSES = 1024                                      # num_class limit of gn_class_metrics_f32
+
+
+def _class_metrics_args(score_or_pred, classes, num_class=None):
+    """(score mode?, num_class) of a class_metrics call, checked without touching a device: a 2-D fp32 score matrix
+    (num_class defaults to its width and must equal it) or a 1-D int64 vector of predicted ids (num_class required),
+    and int64 class ids of the same length."""
+    x = score_or_pred
+    if num_class is not None and not isinstance(num_class, bool):
+        try:
+            num_class = operator.index(num_class)                  # (numpy and torch integers too; a float is refused below)
+        except TypeError:
+            pass
+    if not isinstance(x, torch.Tensor) or not isinstance(classes, torch.Tensor):
+        raise TypeError("class_metrics takes tensors, got {} and {}".format(type(x).__name__, type(classes).__name__))
+    if x.dim() == 2:
+        if x.dtype != torch.float32:
+            raise TypeError("class scores must be fp32, got {}".format(x.dtype))
+        width = int(x.shape[1])
+        if num_class is None:
+            num_class = width
+        elif num_class != width:
+            raise ValueError("num_class {!r} differs from the score matrix's width {}".format(num_class, width))
+        score_mode = True
+    elif x.dim() == 1:
+        if x.dtype != torch.int64:
+            raise TypeError("predicted class ids must be int64 (torch.long), got {}".format(x.dtype))
+        if num_class is None:
+            raise ValueError("num_class is required with predicted class ids")
+        score_mode = False
+    else:
+        raise ValueError("expected a [n, C] score matrix or [n] predicted ids, got shape {}".format(tuple(x.shape)))
+    if not isinstance(num_class, int) or isinstance(num_class, bool) or not 1 <= num_class <= MAX_CLASSES:
+        raise ValueError("num_class must be an int in [1, {}], got {!r}".format(MAX_CLASSES, num_class))
+    if classes.dtype != torch.int64:
+        raise TypeError("class ids must be int64 (torch.long), got {}".format(classes.dtype))
+    if classes.dim() != 1 or classes.shape[0] != x.shape[0]:
+        raise ValueError("classes must be a [{}] vector, got shape {}".format(int(x.shape[0]), tuple(classes.shape)))
+    return score_mode, num_class
+
+
+def class_metrics(score_or_pred, classes, num_class=None):
+    """(pred int64 [n] or None, counts int64 [3, C], per_class float64 [3, C], summary float64 [3]) on the GPU
+    (gn_class_metrics_f32): argmax of a score matrix (or given predicted ids), per-class support / predicted / correct,
+    precision / recall / F1, and micro-F1 / macro-F1 / accuracy.  Asynchronous and capturable: an out-of-range class id
+    sets bit 3 (value 8) of the error word (raise_if_index_errors) and makes every float64 output NaN."""
+    score_mode, C = _class_metrics_args(score_or_pred, classes, num_class)
+    require_gpu(score_or_pred, classes)
+    dev = score_or_pred.device
+    if classes.device != dev:
+        raise ValueError("scores and classes are on different devices: {} and {}".format(dev, classes.device))
+    y = i64_vec(classes)
+    n = int(y.shape[0])
+    if score_mode:
+        x = f32_rows(score_or_pred.detach())
+        pred = torch.empty((n,), dtype=torch.int64, device=dev)
+        args = (ptr(x), ld(x), None)
+    else:
+        x = i64_vec(score_or_pred)
+        pred = None
+        args = (None, 0, ptr(x))
+    counts = torch.empty((3, C), dtype=torch.int64, device=dev)
+    per_class = torch.empty((3, C), dtype=torch.float64, device=dev)
+    summary = torch.empty((3,), dtype=torch.float64, device=dev)
+    ws = torch.empty((int(load().gn_class_metrics_workspace_bytes(n, C)),), dtype=torch.uint8, device=dev)
+    _call("gn_class_metrics_f32", *args, ptr(y), n, C, ptr(pred), ptr(counts), ptr(per_class), ptr(summary),
+          ptr(error_flag(dev)), ptr(ws), ws.numel(), stream_ptr(dev))
+    return pred, counts, per_class, summary
 
 
 def class_scores(z, weight, nodes, out, softmax=True):

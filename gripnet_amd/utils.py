@@ -237,6 +237,28 @@ def relation_metrics(pos_score: torch.Tensor, neg_score: torch.Tensor, range_lis
     return link_metrics(pos_score, neg_score, range_list)
 
 
+def class_metrics(score_or_pred: torch.Tensor, classes: torch.Tensor, num_class: Optional[int] = None):
+    """Node-classification metrics on the GPU: what the NC drivers compute with ``pred = torch.argmax(score, dim=1)`` and
+    ``micro_macro(classes, pred)`` (GripNet-aminer.py:130-137,153-156), without the host round trip.
+
+    ``score_or_pred`` is a 2-D fp32 score matrix [n, C] (probabilities or logits, any row stride; ``num_class`` defaults
+    to its width and must equal it when given) or a 1-D int64 vector of predicted class ids (``num_class`` required).
+    Returns a dict of device tensors: ``pred`` (int64 [n], ``torch.argmax(score, 1)`` bit for bit; None with given ids),
+    ``support``, ``predicted``, ``correct`` (int64 [C]), ``precision``, ``recall``, ``f1`` (float64 [C]) and
+    ``micro_f1``, ``macro_f1``, ``accuracy`` (0-d float64): scikit-learn's definitions and bits (f1_score micro / macro,
+    accuracy_score; precision_recall_fscore_support(labels=range(C), zero_division=0) per class).
+
+    The launch is asynchronous; this then synchronises on the error word, as relation_metrics does (the epoch reads the
+    numbers anyway), so a class id outside [0, C) raises IndexError here.  Argument errors raise before any device work;
+    CPU tensors are refused."""
+    from ._hip import class_metrics as launch, raise_if_index_errors
+    pred, counts, per_class, summary = launch(score_or_pred, classes, num_class)
+    raise_if_index_errors(counts.device)
+    return {"pred": pred, "support": counts[0], "predicted": counts[1], "correct": counts[2],
+            "precision": per_class[0], "recall": per_class[1], "f1": per_class[2],
+            "micro_f1": summary[0], "macro_f1": summary[1], "accuracy": summary[2]}
+
+
 def ranking_metrics(greater: torch.Tensor, ties: torch.Tensor, edge_type: torch.Tensor, num_et: int, hits=(1, 3, 10)):
     """Filtered MRR and Hits@k from the counts of ``multiRelaInnerProductDecoder.rank``, with the realistic rank
     ``1 + greater + ties / 2`` (ties share the mean of their places).  Returns a dict of float64 tensors: ``mrr`` and

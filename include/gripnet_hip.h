@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 157 /* 0.1.51 */
+#define GN_VERSION 158 /* 0.1.52 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -664,6 +664,31 @@ GN_API size_t gn_link_metrics_workspace_bytes(int64_t num_relations, int64_t num
 GN_API gn_status gn_link_metrics_f32(const float* pos_score, const float* neg_score, const int64_t* range_list_host,
                               int64_t num_relations, int64_t num_edges, double* out, void* workspace,
                               size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Node-classification metrics (replaces `pred = torch.argmax(score, dim=1)` and the device -> host copies and two
+ * scikit-learn f1_score calls of micro_macro, gripnet/utils.py:38-52, twice per epoch of the node-classification drivers:
+ * GripNet-aminer.py:130-137,153-156, GripNet-freebase-c.py:165-172,188-191).
+ * Input: EXACTLY ONE of score (fp32 [n, num_class], row stride ld_score >= num_class, unit column stride, any alignment)
+ * and pred_in (int64 [n] predicted class ids); classes: int64 [n] true class ids.  Outputs (device):
+ *   pred_out  int64 [n] (score mode; nullable): torch.argmax(score, 1) - NaN above every number (the first NaN wins),
+ *             otherwise the larger value, equal values (+0.0 == -0.0) by the lower index; an all -inf row gives 0;
+ *   counts    int64 [3][num_class]: support (true count), predicted count, correct count (tp) per class;
+ *   per_class float64 [3][num_class]: precision tp / predicted, recall tp / support, F1 2 tp / (support + predicted),
+ *             each one division of exact integers, 0.0 where the denominator is 0 (scikit-learn's zero_division = 0);
+ *   summary   float64 [3]: micro-F1 (= accuracy = sum tp / n), macro-F1 (the mean of F1 over the classes present in the
+ *             labels or the predictions, summed in numpy's pairwise order: scikit-learn's bits), accuracy; n = 0 gives
+ *             0.0, NaN, NaN as scikit-learn does.
+ * A class id (or pred_in id) outside [0, num_class) ORs bit 3 (value 8) into *error_flag (nullable): every float64
+ * output is then NaN and counts cover the rows whose ids are both in range.  Two launches, integer counts only (the same
+ * bits every run), no host synchronisation, no allocation: graph-capturable.  workspace: at least
+ * gn_class_metrics_workspace_bytes(n, num_class) bytes, 4-byte aligned, no initial contents.  1 <= num_class <= 1024
+ * and n < 2^31, GN_ERR_UNSUPPORTED otherwise. */
+GN_API size_t gn_class_metrics_workspace_bytes(int64_t n, int64_t num_class);
+GN_API gn_status gn_class_metrics_f32(const float* score, int64_t ld_score, const int64_t* pred_in, const int64_t* classes,
+                                      int64_t n, int64_t num_class, int64_t* pred_out, int64_t* counts, double* per_class,
+                                      double* summary, int32_t* error_flag, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * One-shot direct exchange: the all-reduce of the sharded relational layer's partial sums ([n_d, 32] floats,
