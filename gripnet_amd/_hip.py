@@ -13,6 +13,8 @@ import threading
 
 import torch
 
+from ._cache import MISS, VersionedCache
+
 # GN_HIP_LIBRARY selects another build of the same library (the diagnostic `make STAMPS=1` one)
 _LIB_PATH = os.environ.get("GN_HIP_LIBRARY") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib",
                                                             "libgripnet_hip.so")
@@ -188,6 +190,11 @@ class SplitPlanes:
         """Remember on `x` that these planes hold its current contents."""
         x._gn_planes = (self, self.generation, x._version)
         return x
+
+    def rewritten_for(self, x: torch.Tensor):
+        """A launch rewrote the planes with the contents of `x`: they describe `x` (and nothing tagged before) now."""
+        self.generation += 1
+        return self.tag(x)
 
     @staticmethod
     def of(x: torch.Tensor, nt: int):
@@ -396,7 +403,8 @@ class CallMemo:
     a loop's outputs cycle through one or two addresses.  A key is recorded the second time in a row it is seen (one-shot
     inputs - fresh negative samples - never fill the table).  An entry keeps alive what its calls read besides the
     caller's input and the output (plans' scratch, temporaries the slow path allocated, the by-reference structures), and
-    the objects whose `id` is part of the key."""
+    what the module's `hold` names: every object whose `id` is part of the key, so that no id is reused under a live
+    recording."""
 
     DEPTH = 8
 
@@ -404,23 +412,33 @@ class CallMemo:
         self.entries = {}                    # key -> (calls, keep, post)
         self.last = None
 
-    def get(self, key):
-        return self.entries.get(key)
+    @classmethod
+    def of(cls, module):
+        """The memo of `module` (`module.__dict__["_memo"]`: not a submodule, not in the state dict), made at first use."""
+        memo = module.__dict__.get("_memo")
+        if memo is None:
+            memo = module.__dict__["_memo"] = cls()
+        return memo
 
-    def second_sighting(self, guard):
+    def run(self, guard, out, run, drop, hold, post=None):
+        """One forward whose calls are a function of `guard` and the address of `out`.  Recorded already: the calls again,
+        then what the recording's `post()` gave (None, or a callable) with `out`.  Else `run()`, and when `guard` was also
+        the previous call's, with every entry-point call written down and stored; `drop`: tensors (the caller's input, the
+        fresh output) the entry must NOT keep alive; `hold()`: objects it must, asked AFTER the run (a plan may only exist then)."""
+        key = guard + (out.data_ptr(),)
+        hit = self.entries.get(key)
+        if hit is not None:
+            replay(hit[0])
+            if hit[2] is not None:
+                hit[2](out)
+            return out
         seen, self.last = self.last == guard, guard
-        return seen
-
-    def record(self, key, run, drop, hold=(), post=None):
-        """Run `run()` with every entry-point call written down, store the recording under `key`; `drop`: tensors (the
-        caller's input, the fresh output) the entry must NOT keep alive; `hold`: objects it must."""
-        global _recorder
-        if _recorder is not None:
+        if not seen or _recorder is not None:
             return run()
         drop_ptrs = {t.untyped_storage().data_ptr() for t in drop if t is not None}
         with Recorder() as rec:
             result = run()
-        keep = list(hold)
+        keep = list(hold())
         for item in rec.keep:
             if torch.is_tensor(item):
                 if item.untyped_storage().data_ptr() not in drop_ptrs:
@@ -438,7 +456,7 @@ class CallMemo:
             keep.append(item)
         while len(self.entries) >= self.DEPTH:
             self.entries.pop(next(iter(self.entries)))
-        self.entries[key] = (rec.calls, keep, post)
+        self.entries[key] = (rec.calls, keep, None if post is None else post())
         return result
 
 
@@ -967,18 +985,15 @@ def distmult(z, u_v, edge_type, weight, sigmoid, out):
     return out
 
 
-_relation_ids = []          # (edge_type tensor, _version, int16 copy) of the last few edge_type tensors asked about
+_ids16 = VersionedCache(4)         # edge_type tensor -> its int16 copy
 
 
 def relation_ids16(et):
     """The relation ids of a (static) edge_type tensor as 16-bit values, narrowed once per tensor and version."""
-    for t, ver, r16 in _relation_ids:
-        if t is et and ver == et._version:
-            return r16
-    r16 = et.to(torch.int16)
-    _relation_ids.append((et, et._version, r16))
-    del _relation_ids[:-4]
-    return r16
+    if et.dtype == torch.int16:                         # (`to` would return `et` itself: a value that keeps its own key alive)
+        return et
+    r16 = _ids16.get(et)
+    return _ids16.put(et, et.to(torch.int16)) if r16 is MISS else r16
 
 
 def packed_pairs(edge_index):
@@ -1117,7 +1132,7 @@ class DistMultBwdPlan:
             _lib.gn_distmult_bwd_plan_destroy(h)
 
 
-_sorted_types = []          # (tensor, _version, relations, offsets or None) of the last few edge_type tensors asked about
+_type_offsets = VersionedCache(4)           # (edge_type tensor, relations) -> offsets + task list, or None: not sorted
 
 
 _batch_tls = threading.local()      # the open batch of THIS thread: the library's queue is thread_local too (autograd runs a
@@ -1157,9 +1172,9 @@ def type_offsets(et, num_relations):
     """[R + 1] int32 offsets of the relations in a non-decreasing edge_type tensor, or None if it is not sorted.  One
     device reduction and host read per tensor (and version): the reference passes the same `train_et` with the
     positive and the negative edges of every epoch."""
-    for t, ver, r, off in _sorted_types:
-        if t is et and ver == et._version and r == num_relations:
-            return off
+    off = _type_offsets.get(et, num_relations)
+    if off is not MISS:
+        return off
     off = None
     if et.numel() < 2 or bool((et[1:] >= et[:-1]).all()):
         bounds = torch.arange(num_relations + 1, device=et.device, dtype=et.dtype)
@@ -1170,9 +1185,7 @@ def type_offsets(et, num_relations):
         off = torch.empty((need // 4,), dtype=torch.int32, device=et.device)
         with torch.cuda.device(et.device):
             _call("gn_distmult_type_tasks", ptr(first), num_relations, et.numel(), ptr(off), need, stream_ptr(et.device))
-    _sorted_types.append((et, et._version, num_relations, off))
-    del _sorted_types[:-4]
-    return off
+    return _type_offsets.put(et, off, num_relations)
 
 
 class LinkLossGrad:
@@ -1413,21 +1426,15 @@ class MetricsPlan:
             _lib.gn_link_metrics_plan_destroy(h)
 
 
-_metric_plans = []          # (range_list object, _version, device, MetricsPlan) of the last few range lists
+_range_plans = VersionedCache(4)      # (range_list tensor, device) -> MetricsPlan
 
 
 def metrics_plan(range_list, device):
-    """The MetricsPlan of a range list, kept while the same tensor (unmodified) keeps coming: an epoch loop's train / test ranges."""
-    ver = getattr(range_list, "_version", None)
+    """The MetricsPlan of a range list, kept while the same tensor (unmodified) keeps coming: an epoch loop's train / test
+    ranges (a list / array has no version to watch: not kept)."""
     dev = torch.device(device)
-    for rl, v, d, plan in _metric_plans:
-        if rl is range_list and v == ver and d == dev:
-            return plan
-    plan = MetricsPlan(range_list, dev)
-    if ver is not None:                                  # (a list / array has no version to watch: not kept)
-        _metric_plans.insert(0, (range_list, ver, dev, plan))
-        del _metric_plans[4:]
-    return plan
+    plan = _range_plans.get(range_list, dev)
+    return _range_plans.put(range_list, MetricsPlan(range_list, dev), dev) if plan is MISS else plan
 
 
 def link_metrics(pos_score, neg_score, range_list):

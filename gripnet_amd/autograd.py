@@ -19,6 +19,7 @@ import threading
 import torch
 
 from . import _hip
+from ._cache import MISS, VersionedCache
 
 
 def recording(*tensors) -> bool:
@@ -454,9 +455,9 @@ class LinkPredictionLossFn(torch.autograd.Function):
         return (dz if ctx.needs_input_grad[0] else None), (dd if ctx.needs_input_grad[1] else None), None, None, None, None, None
 
 
-_node_plans = []            # [node_list tensor of the caller, _version, rows of z, plan or None]: the row-gather plans of the last few node lists
-_node_plans_lock = threading.Lock()
-_node_plan_misses = 0       # lists in a row that were not in the cache
+_gather_plans = VersionedCache(4)       # (node_list tensor of the caller, rows of z) -> its row-gather plan, or None: none built yet
+_gather_misses = 0                      # lists in a row that were not in the cache
+_gather_misses_lock = threading.Lock()  # (autograd runs a device's backward on its own thread)
 
 
 def node_gather_plan(key: torch.Tensor, nodes: torch.Tensor, num_rows: int):
@@ -469,32 +470,18 @@ def node_gather_plan(key: torch.Tensor, nodes: torch.Tensor, num_rows: int):
     build synchronises the stream and walks the list on the host - every step) or a stream that is being captured (a build
     cannot be captured); the caller then gathers and scatters without a plan, and a list that does come back gets its plan
     at its second sighting."""
-    global _node_plan_misses
-    capturing = torch.cuda.is_current_stream_capturing()
-    with _node_plans_lock:                                     # (autograd runs a device's backward on its own thread)
-        entry = None
-        for e in _node_plans:
-            if e[0] is key and e[1] == key._version and e[2] == num_rows:
-                entry = e
-                break
-        if entry is not None:
-            _node_plan_misses = 0
-            if entry[3] is not None or capturing:
-                return entry[3]
-        else:
-            _node_plan_misses += 1
-            if _node_plan_misses > 2 or capturing:
-                _node_plans.append([key, key._version, num_rows, None])
-                del _node_plans[:-4]
-                return None
-    ei = torch.stack([nodes, torch.arange(nodes.shape[0], dtype=torch.int64, device=nodes.device)])
-    plan = _hip.GraphPlan.plain_sum(ei, num_rows, nodes.shape[0])
-    with _node_plans_lock:
-        if entry is not None:
-            entry[3] = plan
-        else:
-            _node_plans.append([key, key._version, num_rows, plan])
-            del _node_plans[:-4]
+    global _gather_misses
+    plan = _gather_plans.get(key, num_rows)
+    with _gather_misses_lock:
+        _gather_misses = _gather_misses + 1 if plan is MISS else 0
+        new_every_step = _gather_misses > 2
+    if plan is None or plan is MISS:
+        if new_every_step or torch.cuda.is_current_stream_capturing():
+            if plan is MISS:
+                _gather_plans.put(key, None, num_rows)
+            return None
+        ei = torch.stack([nodes, torch.arange(nodes.shape[0], dtype=torch.int64, device=nodes.device)])
+        plan = _gather_plans.put(key, _hip.GraphPlan.plain_sum(ei, num_rows, nodes.shape[0]), num_rows)
     return plan
 
 

@@ -154,22 +154,11 @@ class multiRelaInnerProductDecoder(Module):
         w = self.weight
         guard = (z.data_ptr(), z.shape[0], z.stride(0), id(edge_index), edge_index._version, id(edge_type), edge_type._version,
                  bool(sigmoid), w.data_ptr(), self.auto_static, _hip.launch_context(z.device), _hip.env_stamp())
-        memo = self.__dict__.get("_memo")
-        if memo is None:
-            memo = self.__dict__["_memo"] = _hip.CallMemo()
-        key = guard + (out.data_ptr(),)
-        hit = memo.get(key)
-        if hit is not None:
-            _hip.replay(hit[0])
-            return out
-        run = lambda: self._infer(z, edge_index, edge_type, sigmoid, out)
-        if not memo.second_sighting(guard):
-            return run()
-        result = memo.record(key, run, drop=(z, out), hold=(edge_index, edge_type))
-        entry = self._find(edge_index, edge_type)
-        if entry is not None and entry.plan:
-            memo.entries[key][1].append(entry.plan)          # (the call names the plan's handle)
-        return result
+        def hold():
+            entry = self._find(edge_index, edge_type)
+            return (edge_index, edge_type, entry.plan if entry is not None and entry.plan else None)   # (the call names the plan's handle)
+        return _hip.CallMemo.of(self).run(guard, out, lambda: self._infer(z, edge_index, edge_type, sigmoid, out),
+                                          drop=(z, out), hold=hold)
 
     def _infer(self, z, edge_index, edge_type, sigmoid, out):
         plan = self.plan_for(z, edge_index, edge_type)

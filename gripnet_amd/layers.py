@@ -303,21 +303,11 @@ class homoGraph(Module):
                          c.kernel if self.multi_relational else c.table_storage) +
                         tuple([0 if p is None else p.data_ptr() for p in c._parameters.values()]) for c in convs]),
                  _hip.launch_context(x.device), _hip.env_stamp())
-        memo = self.__dict__.get("_memo")
-        if memo is None:
-            memo = self.__dict__["_memo"] = _hip.CallMemo()
-        key = guard + (out.data_ptr(),)
-        hit = memo.get(key)
-        if hit is not None:
-            _hip.replay(hit[0])
-            return out
-        run = lambda: self._infer(x, homo_edge_index, edge_weight, edge_type, range_list, if_catout, widths, out)
-        if not memo.second_sighting(guard):
-            return run()
-        result = memo.record(key, run, drop=(x, out), hold=(homo_edge_index, edge_weight, range_list, planes))
-        # (the key names the plans the recording ran on by id: the entry holds them, so that an id cannot be reused)
-        memo.entries[key][1].extend([c._plan if self.multi_relational else c.cached_result for c in convs])
-        return result
+        # (the key names the graph tensors and the plans the recording ran on by id: the entry holds them)
+        return _hip.CallMemo.of(self).run(
+            guard, out, lambda: self._infer(x, homo_edge_index, edge_weight, edge_type, range_list, if_catout, widths, out),
+            drop=(x, out), hold=lambda: [homo_edge_index, edge_weight, range_list, planes] +
+            [c._plan if self.multi_relational else c.cached_result for c in convs])
 
     def _infer(self, x, homo_edge_index, edge_weight, edge_type, range_list, if_catout, widths, out):
         """The inference launches: conv + ReLU fused, every layer; the last layer (every layer and the input, with
@@ -406,27 +396,12 @@ class interGraph(Module):
                      id(conv.cached_result), conv.table_storage, conv.arithmetic, tf.data_ptr(),
                      tuple([0 if p is None else p.data_ptr() for p in conv._parameters.values()]),
                      _hip.launch_context(dev), _hip.env_stamp())
-            memo = self.__dict__.get("_memo")
-            if memo is None:
-                memo = self.__dict__["_memo"] = _hip.CallMemo()
-            key = guard + (out.data_ptr(),)
-            hit = memo.get(key)
-            if hit is not None:
-                _hip.replay(hit[0])
-                planes = hit[2]
-                if planes is not None:                       # the launch rewrote the split planes: they describe THIS output now
-                    planes.generation += 1
-                    planes.tag(out)
-                return out
-            run = lambda: self._infer_cat(x, inter_edge_index, edge_weight, if_relu, out)
-            if not memo.second_sighting(guard):
-                return run()
-            result = memo.record(key, run, drop=(x, out), hold=(inter_edge_index, edge_weight))
-            entry = memo.entries[key]
-            entry[1].append(conv.cached_result)
-            memo.entries[key] = (entry[0], entry[1], _hip.SplitPlanes.of(out, (self.target_dim + self.target_feat_dim) // 16)
-                                 if (self.target_dim + self.target_feat_dim) % 16 == 0 else None)
-            return result
+            def retag():                # the launch leaves the output's split planes: on a hit they describe THAT output
+                planes = _hip.SplitPlanes.of(out, out.shape[1] // 16) if out.shape[1] % 16 == 0 else None
+                return None if planes is None else planes.rewritten_for
+            return _hip.CallMemo.of(self).run(
+                guard, out, lambda: self._infer_cat(x, inter_edge_index, edge_weight, if_relu, out), drop=(x, out),
+                hold=lambda: (inter_edge_index, edge_weight, conv.cached_result), post=retag)
         y = self.conv.forward_bipartite(x, inter_edge_index, self.n_target, edge_weight, _relu=if_relu)
         if y.shape[1] == self.target_feat.shape[1]:                              # layers.py:378-379
             return _hip.merge(y, self.target_feat, 2)

@@ -15,12 +15,11 @@ from __future__ import annotations
 
 from typing import Iterable, List, Optional, Sequence, Tuple
 
-import weakref
-
 import numpy as np
 import torch
 
 from . import _hip
+from ._cache import MISS, VersionedCache
 
 EPS = 1e-13  # reference: gripnet/utils.py:10
 
@@ -176,7 +175,8 @@ def negative_sampling(pos_edge_index: torch.Tensor, num_nodes: int,
     return out.to(pos_edge_index.device)
 
 
-_samplers = []          # (weak reference to pos_edge_index, _version, range_list contents, num_nodes, NegativeSampler) of the last few positive lists
+# (positive list, range_list contents, num_nodes) -> NegativeSampler: a list that is gone takes its sampler (and bitmaps) with it
+_sampler_cache = VersionedCache(3)
 
 
 def typed_negative_sampling(pos_edge_index: torch.Tensor, num_nodes: int, range_list,
@@ -201,19 +201,11 @@ def typed_negative_sampling(pos_edge_index: torch.Tensor, num_nodes: int, range_
             parts = [NegativeSampler(pos_edge_index[:, s:e].contiguous(), num_nodes).sample(
                 seed=int((rng or np.random).randint(0, 2 ** 31 - 1))) for s, e in blocks]
             return torch.cat(parts, dim=1) if parts else pos_edge_index[:, :0].clone()
-        hit = None
-        for entry in _samplers:
-            if entry[0]() is pos_edge_index and entry[1] == pos_edge_index._version and entry[2] == blocks and entry[3] == num_nodes:
-                hit = entry
-                break
-        _samplers[:] = [en for en in _samplers if en[0]() is not None]     # lists that are gone take their samplers (and bitmaps) with them
-        if hit is None:
-            hit = (weakref.ref(pos_edge_index), pos_edge_index._version, blocks, num_nodes,
-                   NegativeSampler(pos_edge_index, num_nodes, range_list))
-            _samplers.insert(0, hit)
-            del _samplers[3:]
+        sampler = _sampler_cache.get(pos_edge_index, blocks, num_nodes)
+        if sampler is MISS:
+            sampler = _sampler_cache.put(pos_edge_index, NegativeSampler(pos_edge_index, num_nodes, range_list), blocks, num_nodes)
         seed = int((rng or np.random).randint(0, 2 ** 31 - 1))
-        return hit[4].sample(seed=seed)
+        return sampler.sample(seed=seed)
     parts = [negative_sampling(pos_edge_index[:, int(s):int(e)], num_nodes, rng) for s, e in range_list]
     return torch.cat(parts, dim=1)
 

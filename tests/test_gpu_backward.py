@@ -182,9 +182,8 @@ def test_multiclass_decoder_node_lists_that_change_every_step(gpu):
         return real(cls, *args, **kw)
     _hip.GraphPlan.plain_sum = classmethod(counting)
     try:
-        with ag._node_plans_lock:
-            ag._node_plans.clear()
-            ag._node_plan_misses = 0
+        ag._gather_plans.clear()
+        ag._gather_misses = 0
         def grads(node_list, nodes_cpu):
             mc.zero_grad()
             zg = leaf(z.to(gpu))
@@ -208,9 +207,8 @@ def test_multiclass_decoder_node_lists_that_change_every_step(gpu):
         grads(same32, same)                                    # (dropped from the four remembered lists meanwhile: a plan again or not - right either way)
     finally:
         _hip.GraphPlan.plain_sum = classmethod(real)
-        with ag._node_plans_lock:
-            ag._node_plans.clear()
-            ag._node_plan_misses = 0
+        ag._gather_plans.clear()
+        ag._gather_misses = 0
 
 
 def _nll(pred, labels):
