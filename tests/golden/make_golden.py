@@ -3,7 +3,8 @@
 
 Run only in the build container (needs /root/reference, which never travels):
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py            # the forward fixtures (re-drawn from the unseeded global RNG: they move)
+    python tests/golden/make_golden.py --grads    # the gradient fixtures only: reads the forward fixtures, writes new files
 
 The reference's hot path (gripnet/layers.py, gripnet/decoder.py) imports three third-party
 symbols that are not installed here (torch_geometric.utils.add_remaining_self_loops,
@@ -479,5 +480,355 @@ def main():
     print("wrote", os.path.relpath(path, REPO))
 
 
+# --------------------------------------------------------------------------------------
+# gradient fixtures: the reference's own loss.backward(), in fp32 and after .double()
+# --------------------------------------------------------------------------------------
+# The self-check holds the reference's fp32 gradients to 1e-5 of float64 at the gradient's largest entry, a tenth of the
+# bar of the GPU tests.  One gradient cannot meet it: the reference adds the 8,878 triples of pose_small's largest relation
+# one after the other in fp32, twice (positives 0.198, negatives -0.186 at the largest entry, 0.049 left after they cancel);
+# measured 1.0e-5 ... 1.9e-5 over several negative lists and runs (the threaded sums differ from run to run).  It is held to
+# 3e-5; the GPU tests' bar against float64 stays 1e-4.
+FP32_DISTANCE = {("pose_small_grad", "dmt.weight"): 3e-5}
+ROW_TABLES = ("embedding", "target_feat", "aa_embeddings", "x", "z")   # 2-D per-node tables: checked per row as well
+
+
+def is_row_table(key, grad):
+    return grad.dim() == 2 and key.split(".")[-1] in ROW_TABLES
+
+
+def grads_main():
+    """`--grads`: writes <name>_grad.npz next to the forward fixtures and decoder_saturated.npz, and nothing else.  The
+    modules are the reference's, built fresh per precision and loaded from the stored state dicts; inputs come from the
+    stored fixtures; everything drawn here (negative lists, labels, projections, the saturated case) comes from one
+    seeded generator and is stored.  Every case is run in fp32 and again in float64."""
+    _install_standins()
+    from gripnet.layers import myGCN, myRGCN, homoGraph, interGraph  # the reference, unmodified
+    from gripnet.decoder import multiRelaInnerProductDecoder, multiClassInnerProductDecoder
+    from gripnet.utils import EPS
+
+    gen = torch.Generator().manual_seed(20261016)
+
+    def load(name):
+        with np.load(os.path.join(HERE, name + ".npz")) as f:
+            return {k: torch.from_numpy(f[k]) for k in f.files if k != "meta"}, json.loads(str(f["meta"]))
+
+    def loaded(module, arrays, prefix):
+        full = "sd." + prefix
+        module.load_state_dict({k[len(full):]: v for k, v in arrays.items() if k.startswith(full)})
+        return module
+
+    def run_both(c, tag, build, forward, leaves=None, check=True, keep32=True):
+        """build() -> {key prefix: module} (made under the current default dtype); forward(mods, leaves, cast) -> loss.
+        Stores <tag>loss32/64 and <tag>grad32/64.<key>; returns the fp32 run's (loss, grads)."""
+        runs = {}
+        for bits, dtype in ((32, torch.float32), (64, torch.float64)):
+            torch.set_default_dtype(dtype)
+            try:
+                mods = build()
+                lv = {k: v.to(dtype).clone().requires_grad_(True) for k, v in (leaves or {}).items()}
+                loss = forward(mods, lv, lambda t: t.to(dtype))
+                loss.backward()
+            finally:
+                torch.set_default_dtype(torch.float32)
+            grads = {p + k: q.grad for p, m in mods.items() for k, q in
+                     ([("", m)] if isinstance(m, torch.nn.Parameter) else m.named_parameters())}
+            grads.update({k: v.grad for k, v in lv.items()})
+            assert loss.dtype == dtype and all(g is None or g.dtype == dtype for g in grads.values())
+            runs[bits] = (loss.detach(), grads)
+        (l32, g32), (l64, g64) = runs[32], runs[64]
+        assert torch.isfinite(l32) and torch.isfinite(l64)
+        worst = (0.0, "-")
+        if check:
+            assert abs(float(l32) - float(l64)) <= 1e-6 * abs(float(l64)), (c.name, tag, float(l32), float(l64))
+        c.put(tag + "loss32", l32)
+        c.put(tag + "loss64", l64)
+        for k in g64:
+            if g64[k] is None:
+                assert g32[k] is None
+                c.meta.setdefault("no_grad", []).append(tag + k)
+                continue
+            a, b = g32[k].double(), g64[k]
+            assert torch.isfinite(a).all() and torch.isfinite(b).all()
+            scale = float(b.abs().max())
+            if check:
+                err = float((a - b).abs().max())
+                bar = FP32_DISTANCE.get((c.name, tag + k), 1e-5)
+                assert err <= bar * scale, (c.name, tag, k, err, scale)
+                if bar != 1e-5:
+                    c.meta.setdefault("fp32_distance", {})[tag + k] = bar
+                worst = max(worst, (err / scale if scale else 0.0, k))
+                if is_row_table(k, b):
+                    rows = b.abs().amax(dim=1)
+                    assert ((a - b).abs().amax(dim=1) <= 1e-5 * rows + 1e-6 * scale).all(), (c.name, tag, k, "per row")
+            if keep32:
+                c.put(tag + "grad32." + k, g32[k])
+            else:                                   # 40 of the 52 mantissa bits (2^-41 relative; the tests ask 1e-9): the zeros compress
+                b = torch.from_numpy(((b.numpy().view(np.int64) + (1 << 11)) & ~np.int64((1 << 12) - 1)).view(np.float64))
+            c.put(tag + "grad64." + k, b)
+        print("  {}{}: loss {:.6g}, worst fp32 distance {:.2e} ({})".format(c.name, " " + tag if tag else "", float(l64), *worst))
+        return runs[32]
+
+    # ---- callers: the loss the driver spells out ------------------------------------------------------------------
+    for scale in ("tiny", "small"):
+        a, meta = load("pose_" + scale)
+        c = Case("pose_{}_grad".format(scale), forward="pose_" + scale)
+        neg = torch.randint(0, meta["n_d"], tuple(a["train_idx"].shape), generator=gen)
+        c.put("neg_index", neg.to(torch.int16 if meta["n_d"] < 2 ** 15 else torch.int64))
+
+        def build():
+            dd_nhids = meta["dd_nhids"]
+            return {"gg.": loaded(homoGraph(meta["gg_nhids"], start_graph=True, in_dim=meta["n_g"]), a, "gg."),
+                    "gd.": loaded(interGraph(sum(meta["gg_nhids"]), meta["gd_out"][0], meta["n_d"],
+                                             target_feat_dim=meta["gd_out"][-1]), a, "gd."),
+                    "dd.": loaded(homoGraph(dd_nhids, multi_relational=True, n_rela=meta["R"]), a, "dd."),
+                    "dmt.": loaded(multiRelaInnerProductDecoder(sum(dd_nhids), meta["R"]), a, "dmt.")}
+
+        def forward(m, lv, cast):                                       # GripNet-pose.py:117-142
+            z = m["gg."](torch.zeros(1), a["gg_edge_index"], edge_weight=cast(a["edge_weight"]), if_catout=True)
+            z = m["gd."](z, a["gd_edge_index"], mod="cat", if_relu=True)
+            z = m["dd."](z, a["train_idx"], edge_type=a["train_et"], range_list=a["train_range"], if_catout=True)
+            pos_score = m["dmt."](z, a["train_idx"], a["train_et"])
+            neg_score = m["dmt."](z, neg, a["train_et"])
+            return -torch.log(pos_score + EPS).mean() - torch.log(1 - neg_score + EPS).mean()
+
+        run_both(c, "", build, forward, keep32=scale == "tiny")       # (small: 130 k gradients; grad64 alone, see keep32)
+        c.save()
+
+    def nc_case(name, build, forward):
+        a, meta = load(name)
+        c = Case(name + "_grad", forward=name)
+        labels = torch.randint(0, meta["n_class"], tuple(a["node_list"].shape), generator=gen)
+        c.put("labels", labels)
+
+        def loss(m, lv, cast):                                          # GripNet-aminer.py:133
+            score = forward(a, m, cast)
+            return -torch.log(score[range(score.shape[0]), labels] + EPS).mean()
+
+        run_both(c, "", lambda: build(a, meta), loss)
+        c.save()
+
+    def aminer_build(a, meta):
+        return {"pp.": loaded(homoGraph(meta["pp_nhids"], start_graph=True, in_dim=meta["n_p"]), a, "pp."),
+                "pa.": loaded(interGraph(sum(meta["pp_nhids"]), meta["pa_out"][0], meta["n_a"],
+                                         target_feat_dim=meta["pa_out"][-1]), a, "pa."),
+                "aa.": loaded(homoGraph(meta["aa_nhids"]), a, "aa."),
+                "mcip.": loaded(multiClassInnerProductDecoder(sum(meta["aa_nhids"]), meta["n_class"]), a, "mcip.")}
+
+    def aminer_forward(a, m, cast):                                     # GripNet-aminer.py:124-130
+        z = m["pp."](torch.zeros(1), a["pp_edge_idx"], edge_weight=cast(a["pp_edge_weight"]), if_catout=True)
+        z = m["pa."](z, a["pa_edge_idx"], if_relu=True, mod="cat")
+        z = m["aa."](z, a["aa_edge_idx"], edge_weight=cast(a["aa_edge_weight"]), if_catout=True)
+        return m["mcip."](z, a["node_list"])
+
+    nc_case("aminer_tiny", aminer_build, aminer_forward)
+    nc_case("freebase_b_tiny", aminer_build, aminer_forward)
+
+    def fa_build(a, meta):
+        return {"pp.": loaded(homoGraph(meta["pp_nhids"], start_graph=True, in_dim=meta["n_a"]), a, "pp."),
+                "mcip.": loaded(multiClassInnerProductDecoder(meta["pp_nhids"][-1], meta["n_class"]), a, "mcip.")}
+
+    def fa_forward(a, m, cast):                                         # GripNet-freebase-a.py:120-122
+        z = m["pp."](torch.zeros(1), a["aa_edge_idx"], edge_weight=cast(a["aa_edge_weight"]))
+        return m["mcip."](z, a["node_list"])
+
+    nc_case("freebase_a_tiny", fa_build, fa_forward)
+
+    def fc_build(a, meta):
+        pa_out = meta["pa_out"]
+        return {"pp.": loaded(homoGraph(meta["pp_nhids"], start_graph=True, in_dim=meta["n_p"]), a, "pp."),
+                "pa.": loaded(interGraph(sum(meta["pp_nhids"]), pa_out[0], meta["n_a"], target_feat_dim=pa_out[-1],
+                                         if_one_external=False), a, "pa."),
+                "qq.": loaded(homoGraph(meta["qq_nhids"], start_graph=True, in_dim=meta["n_q"]), a, "qq."),
+                "qa.": loaded(interGraph(sum(meta["qq_nhids"]), pa_out[0], meta["n_a"], target_feat_dim=pa_out[-1],
+                                         if_one_external=False), a, "qa."),
+                "aa_embeddings": torch.nn.Parameter(a["aa_embeddings"].to(torch.get_default_dtype()).clone()),
+                "aa.": loaded(homoGraph(meta["aa_nhids"]), a, "aa."),
+                "mcip.": loaded(multiClassInnerProductDecoder(meta["aa_nhids"][-1], meta["n_class"]), a, "mcip.")}
+
+    def fc_forward(a, m, cast):                                         # GripNet-freebase-c.py:150-165
+        z = m["pa."](m["pp."](torch.zeros(1), a["pp_edge_idx"], edge_weight=cast(a["pp_edge_weight"]), if_catout=True),
+                     a["pa_edge_idx"], mod="add", if_relu=True)
+        z1 = m["qa."](m["qq."](torch.zeros(1), a["qq_edge_idx"], edge_weight=cast(a["qq_edge_weight"]), if_catout=True),
+                      a["qa_edge_idx"], mod="add", if_relu=True)
+        z = m["aa."]((z + z1 + m["aa_embeddings"]) / 3, a["aa_edge_idx"], edge_weight=cast(a["aa_edge_weight"]))
+        return m["mcip."](z, a["node_list"])
+
+    nc_case("freebase_c_tiny", fc_build, fc_forward)
+
+    # ---- layers: loss = (y * P).sum() with a stored random P, every variant of the forward fixtures -----------------
+    def layer_case(c, tag, build, call, leaves, info):
+        """call(mods, leaves, cast) -> y.  The projection is drawn at y's shape on the first (fp32) run and given the signs
+        of that y: every element still carries its own random weight, and the loss is a sum of non-negative terms, so
+        that `loss32 == loss64` to 1e-6 relative is a statement about the layer and not about how much of a signed sum
+        cancels (with free signs the sums of these ~200 ... 600 terms cancel to a tenth and miss that bar by chance)."""
+        proj = {}
+
+        def forward(m, lv, cast):
+            y = call(m, lv, cast)
+            if "p" not in proj:
+                sign = torch.where(y.detach() < 0, -1.0, 1.0).float()
+                proj["p"] = sign * (0.25 + torch.randn(tuple(y.shape), generator=gen).abs())
+            return (y * cast(proj["p"])).sum()
+
+        run_both(c, tag + ".", build, forward, leaves)
+        c.put(tag + ".proj", proj["p"])
+        c.meta.setdefault("cases", []).append(dict(tag=tag, **info))
+
+    a, meta = load("gcn_forward")
+    c = Case("gcn_forward_grad", forward="gcn_forward")
+    def build_wb():
+        m = myGCN(meta["fin"], meta["fout"], cached=True)
+        m.load_state_dict({"weight": a["sd.weight"], "bias": a["sd.bias"]})
+        return {"": m}
+
+    layer_case(c, "wb", build_wb,
+               lambda m, lv, cast: m[""](lv["x"], a["edge_index"], cast(a["edge_weight"])), {"x": a["x0"]},
+               dict(state="", fout=meta["fout"], bias=True, weighted=True))
+    nb_state = {k[len("sd.nb."):]: v for k, v in a.items() if k.startswith("sd.nb.")}
+
+    def build_nb():
+        m = myGCN(meta["fin"], 20, cached=False, bias=False)
+        m.load_state_dict(nb_state)
+        return {"": m}
+
+    layer_case(c, "nb", build_nb, lambda m, lv, cast: m[""](lv["x"], a["edge_index"]), {"x": a["x0"]},
+               dict(state="nb.", fout=20, bias=False, weighted=False))
+    c.save()
+
+    a, meta = load("inter_cases")
+    c = Case("inter_cases_grad", forward="inter_cases")
+    for v in meta["variants"]:
+        def build(v=v):
+            return {"": loaded(interGraph(meta["source_dim"], v["target_dim"], meta["n_target"],
+                                          target_feat_dim=v["target_feat_dim"], if_one_external=v["if_one_external"]),
+                               a, v["tag"] + ".")}
+
+        def call(m, lv, cast, v=v):
+            return m[""](lv["x"], a["edge_index"], cast(a["edge_weight"]) if v["weighted"] else None,
+                         if_relu=v["if_relu"], mod=v["mod"])
+
+        layer_case(c, v["tag"], build, call, {"x": a["x"]}, dict(state=v["tag"] + "."))
+    assert "add_down.grad64.target_feat_down" in c.arrays               # the only place it gets a gradient
+    c.save()
+
+    a, meta = load("rgcn_cases")
+    c = Case("rgcn_cases_grad", forward="rgcn_cases")
+    for v in meta["variants"]:
+        layer_case(c, v["tag"],
+                   lambda v=v: {"": loaded(myRGCN(meta["fin"], meta["fout"], meta["R"], meta["B"], v["after_relu"],
+                                                  bias=v["bias"]), a, v["tag"] + ".")},
+                   lambda m, lv, cast: m[""](lv["x"], a["edge_index"], a["edge_type"], a["range_list"]),
+                   {"x": a["x"]}, dict(state=v["tag"] + "."))
+    c.save()
+
+    a, meta = load("homo_cases")
+    c = Case("homo_cases_grad", forward="homo_cases")
+    for tag, catout in (("gcn2_cat", True), ("gcn2_nocat", False)):
+        layer_case(c, tag, lambda: {"": loaded(homoGraph([12, 8, 8]), a, "gcn2.")},
+                   lambda m, lv, cast, catout=catout: m[""](lv["x"], a["edge_index"], cast(a["edge_weight"]), if_catout=catout),
+                   {"x": a["x"]}, dict(state="gcn2.", if_catout=catout))
+    layer_case(c, "start1", lambda: {"": loaded(homoGraph([10, 16], start_graph=True, in_dim=meta["n"]), a, "start1.")},
+               lambda m, lv, cast: m[""](torch.zeros(1), a["edge_index"], None, if_catout=True), {},
+               dict(state="start1.", if_catout=True))
+    layer_case(c, "rgcn2",
+               lambda: {"": loaded(homoGraph([12, 8, 6], multi_relational=True, n_rela=3, n_base=5), a, "rgcn2.")},
+               lambda m, lv, cast: m[""](lv["x"], a["rel.edge_index"], edge_type=a["rel.edge_type"],
+                                         range_list=a["rel.range_list"], if_catout=True),
+               {"x": a["x"]}, dict(state="rgcn2.", if_catout=True))
+    c.save()
+
+    a, meta = load("decoder_cases")
+    c = Case("decoder_cases_grad", forward="decoder_cases")
+    for tag, sig in (("dmt_sigmoid", True), ("dmt_logits", False)):
+        layer_case(c, tag, lambda: {"": loaded(multiRelaInnerProductDecoder(meta["F"], meta["R"]), a, "dmt.")},
+                   lambda m, lv, cast, sig=sig: m[""](lv["z"], a["edge_index"], a["edge_type"], sigmoid=sig),
+                   {"z": a["z"]}, dict(state="dmt.", sigmoid=sig))
+    for tag, soft in (("mcip_softmax", True), ("mcip_logits", False)):
+        layer_case(c, tag, lambda: {"": loaded(multiClassInnerProductDecoder(meta["F"], meta["n_class"]), a, "mcip.")},
+                   lambda m, lv, cast, soft=soft: m[""](lv["z"], a["node_list"], softmax=soft),
+                   {"z": a["z"]}, dict(state="mcip.", softmax=soft))
+    c.save()
+
+    # ---- saturated scores: DistMult + link loss where fp32 and float64 part ways ----------------------------------
+    # Every triple of a relation lies in one band of the float64 logit: z = (row scale in [0.8, 1.2)) x (entries in [0.5, 1))
+    # is non-negative, so a relation whose D entries have one sign has logits of that sign, about 18 x (0.64 ... 1.44) x
+    # mean |D| with F = 32.  The asserts below are what holds the bands, not this estimate.
+    c = Case("decoder_saturated")
+    n, F, hot_only = 40, 32, [36, 37, 38, 39]
+    bands = {"ordinary": [0, 1, 2], "hot": [3], "cold": [4], "frozen": [5]}
+    sizes = [50, 40, 60, 50, 50, 40]
+    R = len(sizes)
+    z = (0.8 + 0.4 * torch.rand(n, 1, generator=gen)) * (0.5 + 0.5 * torch.rand(n, F, generator=gen))
+    D = torch.empty(R, F)
+    D[:3] = torch.randn(3, F, generator=gen) * torch.tensor([[0.3], [0.6], [0.9]])
+    D[3] = 1.8 + torch.rand(F, generator=gen) * 0.4                     # about 22 ... 50: fp32 is at 1.0, float64 mostly is not
+    D[4] = -(1.8 + torch.rand(F, generator=gen) * 0.4)                  # about -50 ... -22: s against EPS = 1e-13 matters
+    D[5] = -(14 + torch.rand(F, generator=gen))                         # below -160: exp overflows, s == 0
+    et = torch.cat([torch.full((s,), r, dtype=torch.long) for r, s in enumerate(sizes)])
+    lists = []
+    for _ in range(2):                                                  # positives, negatives
+        ei = torch.randint(0, n - len(hot_only), (2, int(et.numel())), generator=gen)
+        hot = (et == 3).nonzero().view(-1)
+        ei[:, hot] = torch.randint(0, n, (2, int(hot.numel())), generator=gen)
+        ei[0, hot[:4]] = torch.tensor(hot_only)                         # every hot-only node is in the list
+        ei[1, hot[4:8]] = torch.tensor(hot_only)
+        lists.append(ei)
+    pos_index, neg_index = lists
+    pos_index[:, 3] = pos_index[:, 2]                                   # a repeated triple
+    pos_index[1, 10] = pos_index[0, 10]                                 # u == v
+    for ei in lists:
+        assert not torch.isin(ei[:, et != 3], torch.tensor(hot_only)).any()
+    for k, v in (("z", z), ("sd.dmt.weight", D), ("pos_index", pos_index), ("neg_index", neg_index), ("edge_type", et)):
+        c.put(k, v)
+    logit64 = {}
+    for name, ei in (("pos", pos_index), ("neg", neg_index)):
+        lg = (z.double()[ei[0]] * z.double()[ei[1]] * D.double()[et]).sum(dim=1)
+        sel = lambda band: torch.isin(et, torch.tensor(bands[band]))
+        assert (lg[sel("ordinary")].abs() <= 4).all(), float(lg[sel("ordinary")].abs().max())
+        assert (lg[sel("hot")] >= 20).all() and (lg[sel("cold")] <= -20).all() and (lg[sel("frozen")] <= -110).all()
+        assert (lg[sel("cold")] > -110).all() and (lg[sel("cold")] > -80).any()
+        assert not (((lg > 4) & (lg < 20)) | ((lg < -4) & (lg > -20))).any()
+        logit64[name] = lg
+        c.put(name + "_logit64", lg)
+    kept = {}
+
+    def build():
+        dm = multiRelaInnerProductDecoder(F, R)
+        dm.weight.data.copy_(D)
+        return {"dmt.": dm}
+
+    def forward(m, lv, cast):
+        pos_score = m["dmt."](lv["z"], pos_index, et)
+        neg_score = m["dmt."](lv["z"], neg_index, et)
+        pos_score.retain_grad()
+        neg_score.retain_grad()
+        kept[pos_score.dtype] = (pos_score, neg_score)
+        return -torch.log(pos_score + EPS).mean() - torch.log(1 - neg_score + EPS).mean()
+
+    l32, g32 = run_both(c, "", build, forward, {"z": z}, check=False)
+    ps, ns = kept[torch.float32]
+    hot = et == 3
+    assert (ps[hot] == 1).all() and (ns[hot] == 1).all()
+    assert (ps >= 0).all() and (ps <= 1).all() and (ns >= 0).all() and (ns <= 1).all()
+    assert (g32["dmt.weight"][3] == 0).all() and (g32["z"][hot_only] == 0).all()
+    assert torch.isfinite(ps.grad).all() and torch.isfinite(ns.grad).all()
+    assert float(ns.grad[hot].min()) > 1e10                              # 1 / (1 - 1 + EPS) / E
+    for k, v in (("pos_score", ps), ("neg_score", ns), ("pos_score.grad", ps.grad), ("neg_score.grad", ns.grad)):
+        c.put(k, v)
+    c.meta.update(n=n, F=F, R=R, bands=bands, hot_only_nodes=hot_only, eps=EPS,
+                  loss_differs_from_float64=abs(float(l32) - float(c.arrays["loss64"])))
+    c.save()
+
+    limit = 1 << 20
+    for name in sorted(os.listdir(HERE)):
+        if name.endswith("_grad.npz") or name == "decoder_saturated.npz":
+            assert os.path.getsize(os.path.join(HERE, name)) < limit, name
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--grads"]:
+        grads_main()
+    elif sys.argv[1:]:
+        sys.exit("usage: make_golden.py [--grads]")
+    else:
+        main()

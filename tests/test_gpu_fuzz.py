@@ -21,6 +21,16 @@ def _rel_err(y, ref):
     return (y - ref).abs().max().item() / max(1.0, ref.abs().max().item())
 
 
+def _grad_err(g, ref):
+    """A gradient's error at its own scale (`_rel_err` divides by max(1, max|ref|): blind to a gradient whose largest entry
+    is far below 1); zero against zero exactly."""
+    scale = ref.abs().max().item() if ref.numel() else 0.0
+    err = (g - ref).abs().max().item() if ref.numel() else 0.0
+    if scale == 0.0:
+        return 0.0 if err == 0.0 else float("inf")
+    return err / scale
+
+
 # ---- GCN-style layer (myGCN, gripnet/layers.py:52-100) -----------------------------------------------------------------
 GCN_EDGE_CASES = [(4095, 16, 16, 16), (4096, 16, 16, 16), (4096, 32, 16, 17), (5000, 64, 32, 20), (1, 16, 8, 0),
                   (700, 24, 20, 3), (20000, 32, 16, 70), (33000, 16, 16, 8), (4100, 64, 17, 20), (700, 15, 16, 24), (300, 33, 17, 5)]
@@ -166,4 +176,6 @@ def test_fuzz_relational_gradients(gpu, seed):
         (yr * wgt.double()).sum().backward()
         for name, g, r in (("x", xg.grad, xr.grad), ("basis", rg.basis.grad, sd["basis"].grad), ("att", rg.att.grad, sd["att"].grad),
                            ("root", rg.root.grad, sd["root"].grad), ("bias", rg.bias.grad, sd["bias"].grad)):
-            assert _rel_err(g.cpu().double(), r) <= 5e-5, (name, seed, case, n, fin, fout, bases, R)
+            err = _grad_err(g.cpu().double(), r)
+            print("case {} {}: {:.2e} of the largest entry {:.3e}".format(case, name, err, r.abs().max().item()))
+            assert err <= 5e-5, (name, seed, case, n, fin, fout, bases, R, err)
