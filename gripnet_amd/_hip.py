@@ -218,6 +218,10 @@ class GripNetHipError(RuntimeError):
         self.status = status
 
 
+class Unsupported(GripNetHipError):
+    """GN_ERR_UNSUPPORTED: the library refused this path for these shapes or alignments - the caller takes the next one."""
+
+
 def library_path() -> str:
     return _LIB_PATH
 
@@ -251,6 +255,8 @@ def check(status: int):
         raise IndexError(msg)
     if status == GN_ERR_INVALID_ARG:
         raise ValueError(msg)
+    if status == GN_ERR_UNSUPPORTED:
+        raise Unsupported(status, msg)
     raise GripNetHipError(status, msg)
 
 
@@ -570,8 +576,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, bias=None, relu=Fa
     `b_transposed`: b is [n, k] (out = a b^T); `a_transposed`: a is [k, m] (out = a^T b; m <= 64 or n <= 32 only);
     `accumulate`: out += a b; `addend`: an [m, n] fp32 matrix (rows contiguous, any row stride) added to what is stored
     (gn_gemm_addend_f32) - the other gradient of a tensor with two consumers, see `addend_ok`.  `out_bf16`: `out` is a bf16
-    table, every value rounded once where it is stored (GN_GEMM_OUT_BF16; raises GripNetHipError with GN_ERR_UNSUPPORTED for
-    shapes outside the tall-skinny kernel)."""
+    table, every value rounded once where it is stored (GN_GEMM_OUT_BF16; raises Unsupported for shapes outside the
+    tall-skinny kernel)."""
     if a_transposed:
         m = a.shape[1] if m is None else m
         k = a.shape[0] if k is None else k
@@ -602,7 +608,19 @@ def addend_ok(t, m, n) -> bool:
             (n == 1 or t.stride(1) == 1) and (m == 1 or t.stride(0) >= n))
 
 
-_xtg_ws = {}
+_zeroed = {}        # (device type, device index, what) -> a buffer filled with zeros when it was made
+
+
+def zeroed_once(device, what, numel, dtype=torch.uint8):
+    """The buffer `what` of `device`, zeroed once: scratch whose kernels leave it ready for the next launch, and the error
+    words.  `numel`: its length, or a function that is asked for it when the buffer is made."""
+    key = (device.type, device.index, what)
+    buf = _zeroed.get(key)
+    if buf is None:
+        buf = _zeroed[key] = torch.zeros((int(numel() if callable(numel) else numel),), dtype=dtype, device=device)
+    return buf
+
+
 GN_XTG_TICKET_ZEROED, GN_XTG_JOIN_BATCH = 1, 2
 
 
@@ -633,19 +651,13 @@ def xtg(x: torch.Tensor, g: torch.Tensor, join_batch=False):
     batched = join_batch and getattr(_batch_tls, 'open', None) is not None
     for t, (c0, w1, d0, w2) in enumerate(tiles):
         need = int(load().gn_xtg_workspace_bytes(w1, w2))
-        key = (x.device.index, need, t)
-        ws = _xtg_ws.get(key)
-        if ws is None:                                         # one zeroed workspace per device, size and tile: its last 64 bytes are the kernel's ticket
-            ws = _xtg_ws[key] = torch.zeros((need,), dtype=torch.uint8, device=x.device)
+        ws = zeroed_once(x.device, ("xtg", need, t), need)     # one zeroed workspace per device, size and tile: its last 64 bytes are the kernel's ticket
         xs, gs, os_ = (x, g, out) if len(tiles) == 1 else (x[:, c0:c0 + w1], g[:, d0:d0 + w2], out[c0:c0 + w1, d0:d0 + w2])
         if batched:
             _batch_tls.open.keep.extend((xs, gs, os_))
         _call("gn_xtg_f32", ptr(xs), ld(xs), ptr(gs), ld(gs), x.shape[0], w1, w2, ptr(os_), ld(os_), ptr(ws), need,
               GN_XTG_TICKET_ZEROED | (GN_XTG_JOIN_BATCH if batched else 0), stream_ptr(x.device))
     return out
-
-
-_prologue_ws = {}
 
 
 def grad_prologue(g, saved_out=None, rowdiv=None, want_masked=True, want_colsum=False):
@@ -657,12 +669,7 @@ def grad_prologue(g, saved_out=None, rowdiv=None, want_masked=True, want_colsum=
     gm = torch.empty((rows, cols), dtype=torch.float32, device=dev) if want_masked else None
     gd = torch.empty((rows, cols), dtype=torch.float32, device=dev) if rowdiv is not None else None
     cs = torch.empty((cols,), dtype=torch.float32, device=dev) if want_colsum else None
-    ws = None
-    if want_colsum:
-        key = dev.index
-        if key not in _prologue_ws:
-            _prologue_ws[key] = torch.zeros((int(load().gn_grad_prologue_workspace_bytes()),), dtype=torch.uint8, device=dev)
-        ws = _prologue_ws[key]
+    ws = zeroed_once(dev, "grad prologue", load().gn_grad_prologue_workspace_bytes) if want_colsum else None
     _call("gn_grad_prologue_f32", ptr(g), ld(g), ptr(saved_out), 0 if saved_out is None else ld(saved_out), ptr(rowdiv), rows, cols,
           ptr(gm), cols, ptr(gd), cols, ptr(cs), ptr(ws), 0 if ws is None else ws.numel(), stream_ptr(dev))
     return gm, gd, cs
@@ -674,58 +681,62 @@ def merge(dst: torch.Tensor, src: torch.Tensor, mode: int, src2=None):
     return dst
 
 
-class GraphPlan:
+class Handle:
+    """Owner of one handle of the library (`_h`): made by `_create`, given back by the entry point `_destroy` names when
+    the object goes - once, never after the module has let go of the library, and never for an object whose creation raised
+    (its `_h` is still the class's None)."""
+    _h = None
+    _destroy = None
+
+    def _create(self, name, device, *args):
+        """`_h` = the handle that entry point `name` makes of `args` (then the stream and the handle's address, as every
+        create entry point ends), with `device` current."""
+        h = _p()
+        with torch.cuda.device(device):
+            check(getattr(load(), name)(*args, stream_ptr(device), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h, self._h = self._h, None
+        if h and _lib is not None:
+            getattr(_lib, self._destroy)(h)
+
+
+class GraphPlan(Handle):
     """Owner of a gn_graph_plan handle (the cached normalised graph of one GCN-style layer)."""
+    _destroy = "gn_graph_plan_destroy"
 
     def __init__(self, handle, device, kind):
         self._h, self.device, self.kind = handle, device, kind
         self._export = None
 
     @classmethod
-    def gcn(cls, edge_index, num_nodes, edge_weight=None, improved=False):
-        lib = load()
+    def _build(cls, kind, create, edge_index, edge_weight, n_table, n_rows, size_a, size_b):
+        """The plan `create` makes of (sources, destinations, weights or None, E, size_a, size_b)."""
+        load()
         require_gpu(edge_index, edge_weight)
         ei, src, dst, e = edge_rows(edge_index)
         w = None if edge_weight is None else edge_weight.to(torch.float32).contiguous()
         if w is not None and w.numel() != e:
             raise ValueError("edge_weight has {} entries for {} edges".format(w.numel(), e))
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_gcn_plan_create(src, dst, ptr(w), e, int(num_nodes), int(bool(improved)),
-                                         stream_ptr(ei.device), C.byref(h)))
-        plan = cls(h, ei.device, "gcn")
-        plan.n_rows = plan.n_table = int(num_nodes)
+        plan = cls(None, ei.device, kind)
+        plan._create(create, ei.device, src, dst, ptr(w), e, int(size_a), int(size_b))
+        plan.n_rows, plan.n_table = int(n_rows), int(n_table)
         return plan
 
     @classmethod
+    def gcn(cls, edge_index, num_nodes, edge_weight=None, improved=False):
+        return cls._build("gcn", "gn_gcn_plan_create", edge_index, edge_weight, num_nodes, num_nodes, num_nodes, bool(improved))
+
+    @classmethod
     def bipartite(cls, edge_index, num_sources, num_targets, edge_weight=None):
-        lib = load()
-        require_gpu(edge_index, edge_weight)
-        ei, src, dst, e = edge_rows(edge_index)
-        w = None if edge_weight is None else edge_weight.to(torch.float32).contiguous()
-        if w is not None and w.numel() != e:
-            raise ValueError("edge_weight has {} entries for {} edges".format(w.numel(), e))
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_bipartite_plan_create(src, dst, ptr(w), e, int(num_sources), int(num_targets),
-                                               stream_ptr(ei.device), C.byref(h)))
-        plan = cls(h, ei.device, "bipartite")
-        plan.n_rows, plan.n_table = int(num_targets), int(num_sources)
-        return plan
+        return cls._build("bipartite", "gn_bipartite_plan_create", edge_index, edge_weight, num_sources, num_targets,
+                          num_sources, num_targets)
 
     @classmethod
     def plain_sum(cls, edge_index, num_sources, num_targets):
         """out[t] = sum of table[s] over the edges s -> t (no normalisation)."""
-        lib = load()
-        require_gpu(edge_index)
-        ei, src, dst, e = edge_rows(edge_index)
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_sum_plan_create(src, dst, None, e, int(num_sources), int(num_targets),
-                                         stream_ptr(ei.device), C.byref(h)))
-        plan = cls(h, ei.device, "sum")
-        plan.n_rows, plan.n_table = int(num_targets), int(num_sources)
-        return plan
+        return cls._build("sum", "gn_sum_plan_create", edge_index, None, num_sources, num_targets, num_sources, num_targets)
 
     def build_blocked(self, cols: int):
         """Add the source-blocked encoding (LDS-staged gathers) for rows of up to `cols` floats; a no-op for
@@ -807,19 +818,15 @@ class GraphPlan:
         _call("gn_graph_aggregate_t_f32", self._h, ptr(g), ld(g), g.shape[1], ptr(out), ld(out), stream_ptr(g.device))
         return out
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_graph_plan_destroy(h)
 
-
-class RgcnPlan:
+class RgcnPlan(Handle):
     """Owner of a gn_rgcn_plan handle (static multi-relational graph of one supervertex)."""
+    _destroy = "gn_rgcn_plan_destroy"
 
     def __init__(self, edge_index, range_list, num_nodes, edge_lo=None, edge_hi=None, light=False):
         """`light`: only what the general O(E) kernel reads (GN_RGCN_PLAN_LIGHT) - no host-built schedules: the plan of an edge
         list that will not be seen again."""
-        lib = load()
+        load()
         require_gpu(edge_index)
         ei, src, dst, e = edge_rows(edge_index)
         rl = torch.as_tensor(range_list).to("cpu", torch.int64).contiguous()   # tiny; host copy once
@@ -827,12 +834,10 @@ class RgcnPlan:
             raise ValueError("range_list must have shape [R, 2], got {}".format(tuple(rl.shape)))
         lo = 0 if edge_lo is None else int(edge_lo)
         hi = e if edge_hi is None else int(edge_hi)
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_rgcn_plan_create_ex(src, dst, rl.data_ptr(), 1, rl.shape[0], e, int(num_nodes), lo, hi, 1 if light else 0,
-                                             stream_ptr(ei.device), C.byref(h)))
+        self._create("gn_rgcn_plan_create_ex", ei.device, src, dst, rl.data_ptr(), 1, rl.shape[0], e, int(num_nodes), lo, hi,
+                     1 if light else 0)
         self.light = bool(light)
-        self._h, self.device = h, ei.device
+        self.device = ei.device
         self.num_nodes, self.num_relations, self.num_edges = int(num_nodes), int(rl.shape[0]), e
         self.edge_lo, self.edge_hi = lo, hi
         self._ws = None
@@ -860,9 +865,7 @@ class RgcnPlan:
         if self._wgrad is None:
             try:
                 self._wgrad = RelGradPlan(self.grad_plans()[1], self.num_nodes, self.num_relations)
-            except GripNetHipError as err:
-                if err.status != GN_ERR_UNSUPPORTED:
-                    raise
+            except Unsupported:
                 self._wgrad = False
         return self._wgrad or None
 
@@ -911,21 +914,12 @@ class RgcnPlan:
         the other kernels ignore them).  `basis_transposed`: `basis` is [bases, out, in] (the forward's parameter seen from
         the reversed layer of its backward; destination-major kernel only: GN_RGCN_BASIS_TRANSPOSED)."""
         mode = self.mode_flags(fast, path)
-        if basis_transposed:
-            fout = basis.shape[1]
-            ws, need = self._workspace(x, x.shape[1], fout, basis.shape[0], mode)
-            sc = side_copy(side)
-            flags = (GN_RGCN_PARTIAL if partial else 0) | mode | GN_RGCN_BASIS_TRANSPOSED
-            _call("gn_rgcn_forward_f32", self._h, ptr(x), ld(x), x.shape[1], ptr(basis), ptr(att), basis.shape[0],
-                  ptr(root), ptr(bias), fout, int(bool(relu)), flags,
-                  ptr(out), ld(out), _ref(sc), None if x_planes is None else x_planes.buf.data_ptr(), ptr(ws), need,
-                  stream_ptr(x.device))
-            return out
-        ws, need = self._workspace(x, x.shape[1], basis.shape[2], basis.shape[0], mode)
+        fout = basis.shape[1] if basis_transposed else basis.shape[2]
+        ws, need = self._workspace(x, x.shape[1], fout, basis.shape[0], mode)
         sc = side_copy(side)
-        flags = (GN_RGCN_PARTIAL if partial else 0) | mode
+        flags = (GN_RGCN_PARTIAL if partial else 0) | mode | (GN_RGCN_BASIS_TRANSPOSED if basis_transposed else 0)
         _call("gn_rgcn_forward_f32", self._h, ptr(x), ld(x), x.shape[1], ptr(basis), ptr(att), basis.shape[0],
-              ptr(root), ptr(bias), basis.shape[2], int(bool(relu)), flags,
+              ptr(root), ptr(bias), fout, int(bool(relu)), flags,
               ptr(out), ld(out), _ref(sc), None if x_planes is None else x_planes.buf.data_ptr(), ptr(ws), need,
               stream_ptr(x.device))
         return out
@@ -936,28 +930,17 @@ class RgcnPlan:
               ptr(bias), root.shape[1], int(bool(relu)), ptr(out), ld(out), _ref(sc), stream_ptr(x.device))
         return out
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_rgcn_plan_destroy(h)
-
-
-_error_flags = {}
-
 
 def error_flag(device) -> torch.Tensor:
     """Per-device int32 word the decoder kernels OR index-range errors into (checked lazily)."""
-    key = (device.type, device.index)
-    if key not in _error_flags:
-        _error_flags[key] = torch.zeros(1, dtype=torch.int32, device=device)
-    return _error_flags[key]
+    return zeroed_once(device, "errors", 1, torch.int32)
 
 
 def raise_if_index_errors(device=None):
     """Synchronising check of the error word; raises IndexError like the reference's advanced indexing would
     (gripnet/decoder.py:20; for class ids, the loss line score[range(n), classes] of the NC drivers)."""
-    for key, flag in list(_error_flags.items()):
-        if device is not None and (device.type, device.index) != key:
+    for (kind, index, what), flag in list(_zeroed.items()):
+        if what != "errors" or (device is not None and (device.type, device.index) != (kind, index)):
             continue
         bits = int(flag.item())
         if bits != 0:
@@ -1022,31 +1005,53 @@ def distmult_any(z, u_v, edge_type, weight, sigmoid, out):
     if packed is not None and z.shape[0] <= 65535 and weight.shape[0] <= 32767:
         try:
             return distmult_packed(z, packed, edge_type, weight, sigmoid, out)
-        except GripNetHipError as err:                     # node table too large for the LDS: the general kernels
-            if err.status != GN_ERR_UNSUPPORTED:
-                raise
+        except Unsupported:                     # node table too large for the LDS: the general kernels
+            pass
     return distmult(z, u_v, edge_type, weight, sigmoid, out)
 
 
-class DistMultPlan:
+def distmult_forward(z, u_v, edge_type, weight, sigmoid, out, plan=None):
+    """The decoder's forward ladder: the DistMultPlan of a static list (the positives: same bits, fewer bytes) when there is
+    one and it takes this call, else `distmult_any`.  Returns (out, served): served is False when `plan` did not carry the
+    call (none given, or it refused: node table too large for the LDS).  A refusal can depend on this call's `z`, so the
+    plan is not marked here: a caller that wants to stop asking does that itself."""
+    if plan is not None:
+        try:
+            return plan.forward(z, weight, sigmoid, out), True
+        except Unsupported:
+            pass
+    return distmult_any(z, u_v, edge_type, weight, sigmoid, out), False
+
+
+class DistMultPlan(Handle):
     """Owner of a gn_distmult_plan handle: one static (edge_index, edge_type) list, validated, packed and ordered
     for the LDS-resident decoder kernel (the positive edges a training loop scores every epoch)."""
+    _destroy = "gn_distmult_plan_destroy"
 
     def __init__(self, u_v, edge_type, num_nodes, num_relations, num_features=0):
         """`num_features` (the decoder's in_dim; 0: unknown) lets the plan add the row-class encoding: whole rows of a
         class of nodes in LDS, one table fill per launch (k_distmult_class)."""
-        lib = load()
+        load()
         require_gpu(u_v, edge_type)
         ei, u, v, e = edge_rows(u_v)
         et = i64_vec(edge_type)
         if et.numel() != e:
             raise ValueError("edge_type has {} entries for {} edges".format(et.numel(), e))
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_distmult_plan_create(u, v, ptr(et), e, int(num_nodes), int(num_relations), int(num_features),
-                                              stream_ptr(ei.device), C.byref(h)))
-        self._h, self.device, self.num_edges = h, ei.device, e
+        self._create("gn_distmult_plan_create", ei.device, u, v, ptr(et), e, int(num_nodes), int(num_relations), int(num_features))
+        self.device, self.num_edges = ei.device, e
         self.num_nodes, self.num_relations = int(num_nodes), int(num_relations)
+        self._bwd = None                     # None: not asked for yet; False: the library refused it; else DistMultBwdPlan
+
+    def backward_plan(self, u_v, edge_type):
+        """The DistMultBwdPlan of my list (`u_v`, `edge_type`: the tensors I was built from), or None where the library
+        refuses one (tables too large for the LDS path): built at the first request - the sort happens once per static
+        edge list, not once per step - and kept with me."""
+        if self._bwd is None:
+            try:
+                self._bwd = DistMultBwdPlan(u_v, edge_type, self.num_nodes, self.num_relations)
+            except Unsupported:
+                self._bwd = False
+        return self._bwd or None
 
     def forward(self, z, weight, sigmoid, out):
         _call("gn_distmult_plan_forward_f32", self._h, ptr(z), ld(z), z.shape[1], ptr(weight), ld(weight),
@@ -1060,22 +1065,15 @@ class DistMultPlan:
               ptr(weight), ld(weight), int(bool(sigmoid)), ptr(out), stream_ptr(z.device))
         return out
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_distmult_plan_destroy(h)
 
-
-class RelGradPlan:
+class RelGradPlan(Handle):
     """Owner of a gn_rel_grad_plan handle: the edge-dependent part of the relational layer's weight gradient
     (dW_r = X^T Q_r in one launch), built from the layer's (relation, source)-major sum plan."""
+    _destroy = "gn_rel_grad_plan_destroy"
 
     def __init__(self, sums: "GraphPlan", num_nodes, num_relations):
-        lib = load()
-        h = _p()
-        with torch.cuda.device(sums.device):
-            check(lib.gn_rel_grad_plan_create(sums._h, int(num_nodes), int(num_relations), stream_ptr(sums.device), C.byref(h)))
-        self._h, self.device, self.num_relations = h, sums.device, int(num_relations)
+        self._create("gn_rel_grad_plan_create", sums.device, sums._h, int(num_nodes), int(num_relations))
+        self.device, self.num_relations = sums.device, int(num_relations)
 
     def supported(self, fin, fout) -> bool:
         return bool(load().gn_rel_weight_grad_supported(self._h, int(fin), int(fout)))
@@ -1088,26 +1086,19 @@ class RelGradPlan:
         _call("gn_rel_weight_grad_f32", self._h, ptr(x), ld(x), fin, ptr(gm), ld(gm), fout, ptr(out), stream_ptr(x.device))
         return out
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_rel_grad_plan_destroy(h)
 
-
-class DistMultBwdPlan:
+class DistMultBwdPlan(Handle):
     """Owner of a gn_distmult_bwd_plan handle: the gradient-independent part of the decoder's backward pass for one
     static (edge_index, edge_type) list."""
+    _destroy = "gn_distmult_bwd_plan_destroy"
 
     def __init__(self, u_v, edge_type, num_nodes, num_relations):
-        lib = load()
+        load()
         require_gpu(u_v, edge_type)
         ei, u, v, e = edge_rows(u_v)
         et = i64_vec(edge_type)
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_distmult_bwd_plan_create(u, v, ptr(et), e, int(num_nodes), int(num_relations),
-                                                  stream_ptr(ei.device), C.byref(h)))
-        self._h, self.device, self.num_edges = h, ei.device, e
+        self._create("gn_distmult_bwd_plan_create", ei.device, u, v, ptr(et), e, int(num_nodes), int(num_relations))
+        self.device, self.num_edges = ei.device, e
         self.num_nodes, self.num_relations = int(num_nodes), int(num_relations)
 
     def backward(self, z, weight, grad_logit, dz, dd, probs=None, loss=None):
@@ -1125,11 +1116,6 @@ class DistMultBwdPlan:
         _call("gn_distmult_backward_planned_f32", self._h, ptr(z), ld(z), z.shape[1], ptr(weight), ld(weight),
               ptr(grad_logit), ptr(probs), ptr(dz), ld(dz), ptr(dd), ld(dd), ptr(ws), need, stream_ptr(z.device))
         return dz, dd
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_distmult_bwd_plan_destroy(h)
 
 
 _type_offsets = VersionedCache(4)           # (edge_type tensor, relations) -> offsets + task list, or None: not sorted
@@ -1221,9 +1207,7 @@ def distmult_backward_loss_packed(z, u_v, edge_type, weight, probs, dz, dd, loss
               ptr(weight), ld(weight), weight.shape[0], e, loss.ref(), ptr(probs), ptr(dz), ld(dz), ptr(dd), ld(dd),
               GN_DM_TYPES_SORTED | GN_DM_TYPE_TASKS, ptr(offsets), ptr(dz_add), 0 if dz_add is None else ld(dz_add),
               ptr(dd_add), 0 if dd_add is None else ld(dd_add), ptr(ws), need, stream_ptr(z.device))
-    except GripNetHipError as err:
-        if err.status != GN_ERR_UNSUPPORTED:
-            raise
+    except Unsupported:
         return False
     return True
 
@@ -1244,35 +1228,69 @@ def distmult_backward(z, u_v, edge_type, weight, grad_logit, dz, dd, probs=None)
                   ptr(weight), ld(weight), weight.shape[0], e, ptr(grad_logit), ptr(dz), ld(dz), ptr(dd), ld(dd), flags, ptr(probs),
                   ptr(offsets), ptr(ws), need, stream_ptr(z.device))
             return dz, dd
-        except GripNetHipError as err:                     # tables too large for the counting-sort path: the int64 call
-            if err.status != GN_ERR_UNSUPPORTED:
-                raise
+        except Unsupported:                     # tables too large for the counting-sort path: the int64 call
+            pass
     _call("gn_distmult_backward_ex_f32", ptr(z), ld(z), z.shape[0], z.shape[1], u, v, ptr(et), ptr(weight), ld(weight),
           weight.shape[0], e, ptr(grad_logit), ptr(dz), ld(dz), ptr(dd), ld(dd), flags, ptr(probs), ptr(offsets), ptr(ws),
           need, stream_ptr(z.device))
     return dz, dd
 
 
-class NegativeSampler:
+def distmult_backward_planned(plan, z, u_v, edge_type, weight, grad_logit, dz, dd, probs=None, loss=None):
+    """The decoder's backward ladder for a list that may have a static `plan` (a DistMultPlan or None): the launch on the
+    plan's backward plan; where there is none or it refuses (unaligned rows), the plan-less entry points
+    (`distmult_backward`).  With `loss` (a LinkLossGrad; grad_logit is None) only the loss-fed planned launch is tried.
+    Returns False when nothing was launched (loss-fed and no plan took it: the caller takes the two-step path)."""
+    bwd = None if plan is None else plan.backward_plan(u_v, edge_type)
+    if bwd is not None:
+        try:
+            bwd.backward(z, weight, grad_logit, dz, dd, probs, loss=loss)
+            return True
+        except Unsupported:
+            pass
+    if loss is not None:
+        return False
+    distmult_backward(z, u_v, edge_type, weight, grad_logit, dz, dd, probs=probs)
+    return True
+
+
+def link_loss_forward(pos, neg, eps):
+    """``-mean(log(pos + eps)) - mean(log(1 - neg + eps))`` of two contiguous fp32 score vectors, a 0-d tensor
+    (gn_link_loss_forward_f32; its per-device scratch is zeroed once: the kernel leaves it ready for the next launch)."""
+    loss = torch.empty((), dtype=torch.float32, device=pos.device)
+    ws = zeroed_once(pos.device, "link loss", load().gn_link_loss_workspace_bytes)
+    _call("gn_link_loss_forward_f32", ptr(pos), pos.numel(), ptr(neg), neg.numel(), float(eps), ptr(loss), ptr(ws), ws.numel(),
+          stream_ptr(pos.device))
+    return loss
+
+
+def link_loss_backward(pos, neg, eps, g):
+    """(d loss / d pos, d loss / d neg) of `link_loss_forward` times the upstream gradient `g` (a contiguous fp32 scalar on
+    the device): gn_link_loss_backward_f32."""
+    dp, dn = torch.empty_like(pos), torch.empty_like(neg)
+    _call("gn_link_loss_backward_f32", ptr(pos), pos.numel(), ptr(neg), neg.numel(), float(eps), ptr(g), ptr(dp), ptr(dn),
+          stream_ptr(pos.device))
+    return dp, dn
+
+
+class NegativeSampler(Handle):
     """Device-side typed negative sampling for one static positive edge list (reference:
     gripnet/utils.py:98-119, called once per epoch at GripNet-pose.py:131).
 
         sampler = NegativeSampler(data.train_idx, n_d_node, data.train_range)
         neg_index = sampler.sample(seed=epoch)          # [2, E] int64 on the GPU, no host round trip
     """
+    _destroy = "gn_negative_sampler_destroy"
 
     def __init__(self, pos_edge_index, num_nodes, range_list=None):
-        lib = load()
+        load()
         require_gpu(pos_edge_index)
         ei, u, v, e = edge_rows(pos_edge_index)
         if range_list is None:
             range_list = [[0, e]]
         rl = torch.as_tensor(range_list).to("cpu", torch.int64).contiguous().view(-1, 2)
-        h = _p()
-        with torch.cuda.device(ei.device):
-            check(lib.gn_negative_sampler_create(u, v, rl.data_ptr(), rl.shape[0], e, int(num_nodes),
-                                                 stream_ptr(ei.device), C.byref(h)))
-        self._h, self.device, self.num_edges, self.num_nodes = h, ei.device, e, int(num_nodes)
+        self._create("gn_negative_sampler_create", ei.device, u, v, rl.data_ptr(), rl.shape[0], e, int(num_nodes))
+        self.device, self.num_edges, self.num_nodes = ei.device, e, int(num_nodes)
 
     def sample(self, seed: int = 0, out=None, step=None) -> torch.Tensor:
         """[2, E] int64 negative pairs.  For graphs of up to 65,535 nodes the same launch also leaves every pair as one
@@ -1290,35 +1308,26 @@ class NegativeSampler:
             raise ValueError("`out` must be a contiguous [2, {}] int64 tensor on {}".format(self.num_edges, self.device))
         else:
             out._gn_volatile = True          # refilled behind torch's back (`_version` does not move): never a static list
-        base = out.data_ptr()
+        base, packed = out.data_ptr(), None
         if self.num_nodes <= 65535 and self.num_edges > 0:
             # (a refilled `out` keeps its packed words' buffer: a captured step that scores `out` replays on the new draw)
             held = getattr(out, "_gn_packed", None)
             packed = held[0] if held is not None else torch.empty((self.num_edges,), dtype=torch.int32, device=self.device)
-            if step is not None:
-                _call("gn_negative_sampler_sample_stepped", self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), base,
-                      base + 8 * self.num_edges, ptr(packed), ptr(error_flag(self.device)), stream_ptr(self.device))
-                out._gn_packed = (packed, out._version)
-                return out
-            _call("gn_negative_sampler_sample_packed", self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, base, base + 8 * self.num_edges,
-                  ptr(packed), ptr(error_flag(self.device)), stream_ptr(self.device))
-            out._gn_packed = (packed, out._version)
-            return out
+        head = (self._h, int(seed) & 0xFFFFFFFFFFFFFFFF)
+        pairs = (base, base + 8 * self.num_edges)
+        tail = (ptr(error_flag(self.device)), stream_ptr(self.device))
         if step is not None:
-            _call("gn_negative_sampler_sample_stepped", self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), base,
-                  base + 8 * self.num_edges, None, ptr(error_flag(self.device)), stream_ptr(self.device))
-            return out
-        _call("gn_negative_sampler_sample", self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, base, base + 8 * self.num_edges,
-              ptr(error_flag(self.device)), stream_ptr(self.device))
+            _call("gn_negative_sampler_sample_stepped", *head, ptr(step), *pairs, ptr(packed), *tail)
+        elif packed is not None:
+            _call("gn_negative_sampler_sample_packed", *head, *pairs, ptr(packed), *tail)
+        else:
+            _call("gn_negative_sampler_sample", *head, *pairs, *tail)
+        if packed is not None:
+            out._gn_packed = (packed, out._version)
         return out
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_negative_sampler_destroy(h)
 
-
-class KnownPairs:
+class KnownPairs(Handle):
     """Owner of a gn_known_pairs handle: the union of one or more (edge_index [2,E], edge_type [E]) int64 lists on the GPU
     (train + test, typically) as the filter of filtered ranking (multiRelaInnerProductDecoder.rank / top_k).  Duplicates
     are allowed (set semantics); ids are validated here (IndexError).  One sorted partner row per (relation, u): O(E + R n)
@@ -1326,9 +1335,10 @@ class KnownPairs:
 
         known = KnownPairs([(data.train_idx, data.train_et), (data.test_idx, data.test_et)], n_d, num_et)
     """
+    _destroy = "gn_known_pairs_destroy"
 
     def __init__(self, lists, num_nodes, num_et):
-        lib = load()
+        load()
         if isinstance(lists, tuple) and len(lists) == 2 and torch.is_tensor(lists[0]):
             lists = [lists]
         lists = list(lists)
@@ -1349,16 +1359,8 @@ class KnownPairs:
         ei = torch.cat(rows, dim=1).contiguous() if len(rows) > 1 else rows[0].contiguous()
         et = torch.cat(types).contiguous() if len(types) > 1 else types[0]
         e = int(ei.shape[1])
-        h = _p()
-        with torch.cuda.device(device):
-            check(lib.gn_known_pairs_create(ei.data_ptr(), ei.data_ptr() + 8 * e, et.data_ptr(), e, int(num_nodes),
-                                            int(num_et), stream_ptr(device), C.byref(h)))
-        self._h, self.device, self.num_edges, self.num_nodes, self.num_et = h, device, e, int(num_nodes), int(num_et)
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_known_pairs_destroy(h)
+        self._create("gn_known_pairs_create", device, ei.data_ptr(), ei.data_ptr() + 8 * e, et.data_ptr(), e, int(num_nodes), int(num_et))
+        self.device, self.num_edges, self.num_nodes, self.num_et = device, e, int(num_nodes), int(num_et)
 
 
 def _known_handle(known, z, weight):
@@ -1400,30 +1402,23 @@ def distmult_topk(z, nodes, edge_type, weight, k, known=None):
     return scores, ids
 
 
-class MetricsPlan:
+class MetricsPlan(Handle):
     """Owner of a gn_link_metrics_plan handle: the segments of one range list (what relation_metrics needs besides the scores)."""
+    _destroy = "gn_link_metrics_plan_destroy"
 
     def __init__(self, range_list, device):
         rl = torch.as_tensor(range_list).to("cpu", torch.int64).contiguous().view(-1, 2)
         self.R = int(rl.shape[0])
         self.E = int(rl[-1, 1]) if self.R else 0
         self.device = torch.device(device)
-        h = _p()
-        with torch.cuda.device(self.device):
-            check(load().gn_link_metrics_plan_create(rl.data_ptr(), self.R, self.E, stream_ptr(self.device), C.byref(h)))
-        self._h = h
-        self.workspace_bytes = int(load().gn_link_metrics_plan_workspace_bytes(h))
+        self._create("gn_link_metrics_plan_create", self.device, rl.data_ptr(), self.R, self.E)
+        self.workspace_bytes = int(load().gn_link_metrics_plan_workspace_bytes(self._h))
         self._ws = None
 
     def workspace(self):
         if self._ws is None:
             self._ws = torch.empty((max(self.workspace_bytes, 1),), dtype=torch.uint8, device=self.device)
         return self._ws
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h and _lib is not None:
-            _lib.gn_link_metrics_plan_destroy(h)
 
 
 _range_plans = VersionedCache(4)      # (range_list tensor, device) -> MetricsPlan

@@ -110,9 +110,7 @@ class GcnConvFn(torch.autograd.Function):
             xw = torch.empty((x.shape[0], w.shape[1]), dtype=torch.bfloat16, device=x.device)
             try:
                 _hip.gemm(x, w, xw, out_bf16=True)
-            except _hip.GripNetHipError as err:
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
+            except _hip.Unsupported:
                 xw = torch.empty((x.shape[0], w.shape[1]), dtype=torch.float32, device=x.device)
                 _hip.gemm(x, w, xw)
             plan.aggregate_bf16(xw, b, relu, out, side)
@@ -286,16 +284,7 @@ class DistMultFn(torch.autograd.Function):
         zc = _hip.f32_rows(z.detach())
         w = weight.detach()
         out = torch.empty((edge_index.shape[1],), dtype=torch.float32, device=zc.device)
-        done = False
-        if plan is not None:                                   # a static edge list (the positives): same bits, fewer bytes
-            try:
-                plan.forward(zc, w, sigmoid, out)
-                done = True
-            except _hip.GripNetHipError as err:                # node table too large for the LDS: the general kernels
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
-        if not done:
-            _hip.distmult_any(zc, edge_index, edge_type, w, sigmoid, out)
+        _hip.distmult_forward(zc, edge_index, edge_type, w, sigmoid, out, plan)
         ctx.sigmoid = bool(sigmoid)
         ctx.plan = plan                                        # a static list: its backward plan hangs on the forward one
         ctx.save_for_backward(zc, w, edge_index, edge_type, out if sigmoid else None)
@@ -308,40 +297,8 @@ class DistMultFn(torch.autograd.Function):
         dz = torch.empty_like(z)
         dd = torch.empty_like(w)
         # d sigma(s) / d s = p (1 - p) is applied inside, where the edge records are built
-        probs = out if ctx.sigmoid else None
-        bwd = None
-        if ctx.plan is not None:                               # sort once per static edge list, not once per step
-            bwd = getattr(ctx.plan, "bwd", None)
-            if bwd is None:
-                try:
-                    bwd = _hip.DistMultBwdPlan(ei, et, z.shape[0], w.shape[0])
-                except _hip.GripNetHipError as err:            # tables too large for the LDS path
-                    if err.status != _hip.GN_ERR_UNSUPPORTED:
-                        raise
-                    bwd = False
-                ctx.plan.bwd = bwd
-        done = False
-        if bwd:
-            try:
-                bwd.backward(z, w, g, dz, dd, probs)
-                done = True
-            except _hip.GripNetHipError as err:                # unaligned rows: the general entry point
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
-        if not done:
-            _hip.distmult_backward(z, ei, et, w, g, dz, dd, probs=probs)
+        _hip.distmult_backward_planned(ctx.plan, z, ei, et, w, g, dz, dd, out if ctx.sigmoid else None)
         return (dz if ctx.needs_input_grad[0] else None), (dd if ctx.needs_input_grad[1] else None), None, None, None, None
-
-
-_loss_ws = {}
-
-
-def _loss_workspace(device):
-    """Per-device scratch of gn_link_loss_forward_f32, zeroed once (the kernel leaves it ready for the next launch)."""
-    key = (device.type, device.index)
-    if key not in _loss_ws:
-        _loss_ws[key] = torch.zeros((int(_hip.load().gn_link_loss_workspace_bytes()),), dtype=torch.uint8, device=device)
-    return _loss_ws[key]
 
 
 class LinkLossFn(torch.autograd.Function):
@@ -351,21 +308,14 @@ class LinkLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, neg, eps):
         p, n = pos.detach().contiguous().float(), neg.detach().contiguous().float()
-        loss = torch.empty((), dtype=torch.float32, device=p.device)
-        ws = _loss_workspace(p.device)
-        _hip._call("gn_link_loss_forward_f32", _hip.ptr(p), p.numel(), _hip.ptr(n), n.numel(), float(eps), _hip.ptr(loss),
-                   _hip.ptr(ws), ws.numel(), _hip.stream_ptr(p.device))
         ctx.eps = float(eps)
         ctx.save_for_backward(p, n)
-        return loss
+        return _hip.link_loss_forward(p, n, eps)
 
     @staticmethod
     def backward(ctx, g):
         p, n = ctx.saved_tensors
-        g = g.contiguous().float()
-        dp, dn = torch.empty_like(p), torch.empty_like(n)
-        _hip._call("gn_link_loss_backward_f32", _hip.ptr(p), p.numel(), _hip.ptr(n), n.numel(), ctx.eps, _hip.ptr(g), _hip.ptr(dp),
-                   _hip.ptr(dn), _hip.stream_ptr(p.device))
+        dp, dn = _hip.link_loss_backward(p, n, ctx.eps, g.contiguous().float())
         return (dp if ctx.needs_input_grad[0] else None), (dn if ctx.needs_input_grad[1] else None), None
 
 
@@ -385,21 +335,9 @@ class LinkPredictionLossFn(torch.autograd.Function):
         E = pos_index.shape[1]
         pos = torch.empty((E,), dtype=torch.float32, device=zc.device)
         neg = torch.empty((neg_index.shape[1],), dtype=torch.float32, device=zc.device)
-        done = False
-        if plan is not None:
-            try:
-                plan.forward(zc, w, True, pos)
-                done = True
-            except _hip.GripNetHipError as err:
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
-        if not done:
-            _hip.distmult_any(zc, pos_index, edge_type, w, True, pos)
+        _hip.distmult_forward(zc, pos_index, edge_type, w, True, pos, plan)
         _hip.distmult_any(zc, neg_index, edge_type, w, True, neg)
-        loss = torch.empty((), dtype=torch.float32, device=zc.device)
-        ws = _loss_workspace(zc.device)
-        _hip._call("gn_link_loss_forward_f32", _hip.ptr(pos), pos.numel(), _hip.ptr(neg), neg.numel(), float(eps), _hip.ptr(loss),
-                   _hip.ptr(ws), ws.numel(), _hip.stream_ptr(zc.device))
+        loss = _hip.link_loss_forward(pos, neg, eps)
         ctx.eps, ctx.plan = float(eps), plan
         ctx.save_for_backward(zc, w, pos_index, neg_index, edge_type, pos, neg)
         ctx.mark_non_differentiable(pos, neg)
@@ -414,30 +352,9 @@ class LinkPredictionLossFn(torch.autograd.Function):
         g = g.contiguous().float()
         dz, dd = torch.empty_like(z), torch.empty_like(w)
         # ---- the positives: a static list with a backward plan -> the loss-fed planned launch ----
-        bwd = None
-        if ctx.plan is not None:
-            bwd = getattr(ctx.plan, "bwd", None)
-            if bwd is None:
-                try:
-                    bwd = _hip.DistMultBwdPlan(pos_index, et, z.shape[0], w.shape[0])
-                except _hip.GripNetHipError as err:
-                    if err.status != _hip.GN_ERR_UNSUPPORTED:
-                        raise
-                    bwd = False
-                ctx.plan.bwd = bwd
-        done = False
-        if bwd:
-            try:
-                bwd.backward(z, w, None, dz, dd, pos, loss=_hip.LinkLossGrad(g, ctx.eps, False))
-                done = True
-            except _hip.GripNetHipError as err:
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
         dn = None
-        if not done:                                           # the two-step path: the loss's own backward, then the decoder's
-            dp, dn = torch.empty_like(pos), torch.empty_like(neg)
-            _hip._call("gn_link_loss_backward_f32", _hip.ptr(pos), pos.numel(), _hip.ptr(neg), neg.numel(), ctx.eps, _hip.ptr(g), _hip.ptr(dp),
-                       _hip.ptr(dn), _hip.stream_ptr(z.device))
+        if not _hip.distmult_backward_planned(ctx.plan, z, pos_index, et, w, None, dz, dd, pos, loss=_hip.LinkLossGrad(g, ctx.eps, False)):
+            dp, dn = _hip.link_loss_backward(pos, neg, ctx.eps, g)     # the two-step path: the loss's own backward, then the decoder's
             _hip.distmult_backward(z, pos_index, et, w, dp, dz, dd, probs=pos)
         # ---- the negatives: the sampler's packed pairs -> the loss-fed packed launch ----
         # (the positives' gradients ride on its combine launch as addends: dz / dD of the two lists need no adding launch)
@@ -446,9 +363,7 @@ class LinkPredictionLossFn(torch.autograd.Function):
         dz2, dd2 = torch.empty_like(z), torch.empty_like(w)
         if not _hip.distmult_backward_loss_packed(z, neg_index, et, w, neg, dz2, dd2, _hip.LinkLossGrad(g, ctx.eps, True)):
             if dn is None:
-                dp, dn = torch.empty_like(pos), torch.empty_like(neg)
-                _hip._call("gn_link_loss_backward_f32", _hip.ptr(pos), pos.numel(), _hip.ptr(neg), neg.numel(), ctx.eps, _hip.ptr(g), _hip.ptr(dp),
-                           _hip.ptr(dn), _hip.stream_ptr(z.device))
+                dp, dn = _hip.link_loss_backward(pos, neg, ctx.eps, g)
             _hip.distmult_backward(z, neg_index, et, w, dn, dz2, dd2, probs=neg)
         dz.add_(dz2)
         dd.add_(dd2)

@@ -162,14 +162,12 @@ class multiRelaInnerProductDecoder(Module):
 
     def _infer(self, z, edge_index, edge_type, sigmoid, out):
         plan = self.plan_for(z, edge_index, edge_type)
-        if plan is not None and plan.num_nodes == z.shape[0]:
-            try:
-                return plan.forward(z, self.weight, sigmoid, out)
-            except _hip.GripNetHipError as err:                    # node table too large for the LDS: the general kernels
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
-                self._find(edge_index, edge_type).plan = False
-        return _hip.distmult_any(z, edge_index, edge_type, self.weight, sigmoid, out)
+        if plan is not None and plan.num_nodes != z.shape[0]:
+            plan = None
+        out, served = _hip.distmult_forward(z, edge_index, edge_type, self.weight, sigmoid, out, plan)
+        if plan is not None and not served:                    # (an evaluation loop's z has one shape: do not ask this plan again)
+            self._find(edge_index, edge_type).plan = False
+        return out
 
     def _eval_operands(self, z, *index):
         _hip.require_gpu(z, *index, self.weight)

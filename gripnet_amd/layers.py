@@ -34,16 +34,6 @@ def _unslot(out, side):
     return out, side
 
 
-def _cat_slots(widths, n_rows, device):
-    """Pre-laid-out concat buffer: the layers write their slice in place (layers.py:309,376)."""
-    out = torch.empty((n_rows, int(sum(widths))), dtype=torch.float32, device=device)
-    views, lo = [], 0
-    for w in widths:
-        views.append(out[:, lo:lo + w])
-        lo += w
-    return out, views
-
-
 class myGCN(Module):
     """``out = A_norm (x W) + b`` (reference layers.py:15-105)."""
 
@@ -108,9 +98,7 @@ class myGCN(Module):
             xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.bfloat16, device=x.device)
             try:
                 _hip.gemm(x, self.weight, xw, out_bf16=True, fast=self.arithmetic == "fast")
-            except _hip.GripNetHipError as err:
-                if err.status != _hip.GN_ERR_UNSUPPORTED:
-                    raise
+            except _hip.Unsupported:
                 xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.float32, device=x.device)
                 _hip.gemm(x, self.weight, xw, fast=self.arithmetic == "fast")
             return plan.aggregate_bf16(xw, self.bias, relu, out, side)

@@ -79,9 +79,7 @@ class HipShardKernels:
         out = torch.empty((self.idx.shape[1],), dtype=torch.float32, device=x.device)
         try:
             plan.forward_cols(self._hip.f32_rows(x), dmt.in_dim, 0, x.shape[1], dmt.weight, sigmoid, out)
-        except self._hip.GripNetHipError as err:                         # node table too large for the LDS
-            if err.status != self._hip.GN_ERR_UNSUPPORTED:
-                raise
+        except self._hip.Unsupported:                         # node table too large for the LDS
             return None
         return plan, out, x.shape[1]
 
