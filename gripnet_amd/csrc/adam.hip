@@ -4,11 +4,18 @@
 //   t += 1;  g += wd p;  m += (g - m)(1 - b1);  v = b2 v + (1 - b2) g g;
 //   p -= lr / (1 - b1^t) * m / ( sqrt(v) / sqrt(1 - b2^t) + eps )
 //
+// The betas arrive as doubles, as torch's Python floats do: 1 - b and log b are taken in double on the host and rounded once
+// (1 - 0.999f is 0.00099998713: 1.3e-5 off in every second moment), and the bias corrections are 1 - b^t = -expm1(t log b) on
+// the device.  (1 - __powf(b, t) loses them to cancellation: b2^1 = 0.999 carries half an ulp of 0.999, 6e-8, which is 6e-5 of
+// 1 - b2^1 = 0.001 and 3e-5 of the first steps' size.)
+//
 // The PoSE model has 14 parameter tensors of 16 to 610 K elements: torch's multi-tensor kernel takes 44 us for them inside the
 // replayed training step (plus a launch for the step counters), a per-tensor loop fourteen launches.  Here the tensor table
 // travels as a kernel ARGUMENT (so a captured step replays with it), a workgroup takes a 4096-element slice of one tensor,
 // the step counter lives on the device and is advanced by the last workgroup to arrive (every workgroup has read it by then).
 #include "common.h"
+
+#include <cmath>
 
 namespace {
 
@@ -22,22 +29,24 @@ struct AdamTable {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// omb = 1 - b and logb = log b of the two betas, computed in double and rounded once
 __global__ __launch_bounds__(kAdamThreads) void k_adam(AdamTable tab, float* __restrict__ step, unsigned int* __restrict__ arrived,
-                                                      float lr, float b1, float b2, float eps, float wd, int advance) {
+                                                      float lr, float omb1, float logb1, float b2, float omb2, float logb2, float eps, float wd,
+                                                      int advance) {
     const int b = blockIdx.x;
     int k = 0;
     while (k + 1 < tab.n && b >= tab.first_block[k + 1]) ++k;             // (uniform: scalar registers)
     const gn_adam_tensor T = tab.t[k];
     const float t = *step + 1.0f;
-    const float c1 = 1.0f - __powf(b1, t), c2 = 1.0f - __powf(b2, t);
+    const float c1 = -expm1f(t * logb1), c2 = -expm1f(t * logb2);         // 1 - b^t without the cancellation (b = 0: log b = -inf, c = 1)
     const float step_size = lr / c1, rs2 = 1.0f / sqrtf(c2);
     const int64_t lo = (int64_t)(b - tab.first_block[k]) * kAdamSlice, hi = min(lo + (int64_t)kAdamSlice, T.numel);
     const bool vec = ((reinterpret_cast<uintptr_t>(T.param) | reinterpret_cast<uintptr_t>(T.grad) | reinterpret_cast<uintptr_t>(T.exp_avg) |
                        reinterpret_cast<uintptr_t>(T.exp_avg_sq)) & 15) == 0;
     auto update = [&](float& p, float g, float& m, float& v) {
         g += wd * p;
-        m += (g - m) * (1.0f - b1);
-        v = b2 * v + (1.0f - b2) * g * g;
+        m += (g - m) * omb1;
+        v = b2 * v + omb2 * g * g;
         p -= step_size * (m / (sqrtf(v) * rs2 + eps));
     };
     if (vec) {
@@ -74,11 +83,12 @@ __global__ __launch_bounds__(kAdamThreads) void k_adam(AdamTable tab, float* __r
 }  // namespace
 
 extern "C" gn_status gn_adam_step_f32(const gn_adam_tensor* tensors, int num_tensors, float* step, void* workspace, size_t workspace_bytes,
-                                      float lr, float beta1, float beta2, float eps, float weight_decay, void* stream) {
+                                      float lr, double beta1, double beta2, float eps, float weight_decay, void* stream) {
     GN_REQUIRE(num_tensors >= 0 && (num_tensors == 0 || tensors), "tensor table is null");
     GN_REQUIRE(step && workspace && workspace_bytes >= 4 && (reinterpret_cast<uintptr_t>(workspace) & 3) == 0,
                "step counter / workspace is null (workspace: 4 bytes, zeroed once by the caller)");
-    GN_REQUIRE(lr >= 0.f && beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f, "bad hyper-parameters");
+    GN_REQUIRE(lr >= 0.f && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1. && eps >= 0.f, "bad hyper-parameters");
+    const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2), logb1 = (float)std::log(beta1), logb2 = (float)std::log(beta2);
     std::vector<gn_adam_tensor> live;
     for (int k = 0; k < num_tensors; ++k) {
         const gn_adam_tensor& T = tensors[k];
@@ -97,8 +107,9 @@ extern "C" gn_status gn_adam_step_f32(const gn_adam_tensor* tensors, int num_ten
             blocks += (int)gn::ceil_div(live[done].numel, kAdamSlice);
         }
         tab.first_block[tab.n] = blocks;
-        k_adam<<<blocks, kAdamThreads, 0, gn::as_stream(stream)>>>(tab, step, static_cast<unsigned int*>(workspace), lr, beta1, beta2,
-                                                                    eps, weight_decay, done == live.size() ? 1 : 0);
+        k_adam<<<blocks, kAdamThreads, 0, gn::as_stream(stream)>>>(tab, step, static_cast<unsigned int*>(workspace), lr, omb1, logb1,
+                                                                    (float)beta2, omb2, logb2, eps, weight_decay,
+                                                                    done == live.size() ? 1 : 0);
         GN_LAUNCH_CHECK();
     }
     return GN_OK;

@@ -1218,7 +1218,9 @@ gn_status gn_gemm_addend_f32(const float* a, int64_t lda, int64_t stride_a, cons
     if (m == 0 || n == 0 || batch == 0) return GN_OK;
     GN_REQUIRE(a && b && c, "GEMM operand pointer is null");
     GN_REQUIRE(lda >= (at ? m : k) && ldb >= (bt ? k : n) && ldc >= n, "leading dimension smaller than the row length");
-    GN_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31) && batch <= 65535, "GEMM size out of range");
+    GN_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "GEMM size out of range");
+    if (batch > 65535)           // a legal request beyond the grid's third dimension: the caller cuts it (as rgcn.hip does), not an argument error
+        return gn::fail(GN_ERR_UNSUPPORTED, "a batch of %lld products: one call takes 65535 at most", (long long)batch);
     GemmArgs g;
     g.a = a; g.lda = lda; g.stride_a = stride_a; g.a_rows = a_rows; g.a_table_rows = a_table_rows;
     g.b = b; g.ldb = ldb; g.stride_b = stride_b;

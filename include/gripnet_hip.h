@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 158 /* 0.1.52 */
+#define GN_VERSION 159 /* 0.1.53 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -184,7 +184,7 @@ GN_API gn_status gn_graph_aggregate_t_f32(const gn_graph_plan* plan, const float
  *   C[b] = act( gather_rows(A[b]) @ B[b] + bias ),  b in [0, batch).
  * Replaces torch.matmul at gripnet/layers.py:73,172-173,193,383 and decoder.py:42.
  * a_rows (int64, may be NULL) selects rows of A (z[node_list], decoder.py:42).
- * stride_* are batch strides in elements (0 = shared operand).
+ * stride_* are batch strides in elements (0 = shared operand).  batch <= 65535 (more: GN_ERR_UNSUPPORTED, the caller cuts it).
  * Arithmetic (part of the contract, never read from the environment): by default fp32-faithful - the fp32 matrix
  * instruction (v_mfma_f32_16x16x4_f32, exact) or, for tall-skinny products, bf16 matrix instructions on operands split
  * into THREE bf16 terms (six products; what is dropped is below 2^-23 of a product).  GN_GEMM_ARITH_FAST keeps two terms
@@ -607,7 +607,8 @@ GN_API gn_status gn_grad_prologue_f32(const float* g, int64_t ld_g, const float*
  * `tensors` is a HOST array (copied into the launch's arguments, so a captured launch replays with it): device pointers
  * of parameter, gradient, first and second moment, and the element count.  `step`: one float on the device, the number of
  * steps taken so far (0 before the first), advanced by the launch.  `workspace`: 4 bytes on the device, 4-byte aligned,
- * ZEROED ONCE by the caller.  Calls on one (step, workspace) must be stream-ordered. */
+ * ZEROED ONCE by the caller.  Calls on one (step, workspace) must be stream-ordered.  The betas are doubles (torch's are Python
+ * floats): 1 - beta and the bias corrections 1 - beta^t are taken from them without the cancellation of an fp32 beta. */
 #define GN_ADAM_MAX_TENSORS 64   /* per launch; longer tables take several launches */
 typedef struct gn_adam_tensor {
     float* param;
@@ -617,7 +618,7 @@ typedef struct gn_adam_tensor {
     int64_t numel;
 } gn_adam_tensor;
 GN_API gn_status gn_adam_step_f32(const gn_adam_tensor* tensors, int num_tensors, float* step, void* workspace, size_t workspace_bytes,
-                           float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+                           float lr, double beta1, double beta2, float eps, float weight_decay, void* stream);
 
 /* The link-prediction loss of the training loop and its gradient (GripNet-pose.py:140-142 with EPS of gripnet/utils.py:10):
  *   loss = - mean(log(pos + eps)) - mean(log(1 - neg + eps)),
