@@ -51,6 +51,8 @@ inline gn_status fail(gn_status code, const char* fmt, ...) {
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 
 // Compute units of the current device (persistent kernels launch one workgroup each); 256 if the query fails.
 inline int compute_units() {

@@ -281,14 +281,8 @@ __global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp
     }
 #endif
     } while (0);
-    if (a.side.dst) {                                                      // concat slot: streamed by the whole grid, last
-        const int64_t total = a.side.rows * a.side.cols;
-        for (int64_t tt = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; tt < total; tt += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t i = tt / a.side.cols, c = tt - i * a.side.cols;
-            const float v = a.side.src[i * a.side.ld_src + c];
-            a.side.dst[i * a.side.ld_dst + c] = a.side.mode ? fabsf(v) : v;
-        }
-    }
+    // concat slot: streamed by the whole grid, here last
+    gn::side_copy_stream(a.side, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
 template <int FIN, int NT>

@@ -82,9 +82,7 @@ extern "C" gn_status gn_split_planes_f32(const float* src, int64_t ld_src, int64
                    col0 + cols <= 16 * planes->nt, "split planes do not hold these columns");
     if (rows == 0 || cols == 0) return GN_OK;
     GN_REQUIRE(src && ld_src >= cols, "source matrix is null or its leading dimension too small");
-    gn::k_split_planes<0><<<gn::stream_grid(rows * cols, 256), 256, 0, gn::as_stream(stream)>>>(src, ld_src, rows, (int)cols, (int)col0, *planes);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
+    return gn::launch_split_planes(src, ld_src, rows, (int)cols, (int)col0, *planes, gn::as_stream(stream));
 }
 
 // Backward of the aggregation with respect to its table: gxw[s, :] = sum_{e: src(e)=s} coef_e * g[dst(e), :]

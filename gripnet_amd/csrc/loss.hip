@@ -11,7 +11,6 @@
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 constexpr int kLossGroups = 512, kLossThreads = 256;
 
@@ -208,7 +207,7 @@ gn_status gn_link_loss_forward_f32(const float* pos_score, int64_t num_pos, cons
                "workspace too small or unaligned: need %zu bytes, 8-byte aligned, zero-initialised once", gn_link_loss_workspace_bytes());
     double* partial = static_cast<double*>(workspace);
     unsigned int* counter = reinterpret_cast<unsigned int*>(partial + 2 * kLossGroups);
-    if (aligned16(pos_score) && aligned16(neg_score))
+    if (gn::aligned16(pos_score) && gn::aligned16(neg_score))
         k_link_loss<true><<<kLossGroups, kLossThreads, 0, gn::as_stream(stream)>>>(pos_score, num_pos, neg_score, num_neg, eps, partial, counter, loss);
     else
         k_link_loss<false><<<kLossGroups, kLossThreads, 0, gn::as_stream(stream)>>>(pos_score, num_pos, neg_score, num_neg, eps, partial, counter, loss);

@@ -77,14 +77,8 @@ GeneralWs general_layout(const gn_rgcn_plan* plan, int64_t fin, int64_t fout) {
 __global__ void k_rgcn_finalize(const float* __restrict__ summed, int64_t ld_s, const float* __restrict__ indeg,
                                 int relu, float* __restrict__ out, int64_t ld_o, int64_t rows, int cols,
                                 gn_side_copy side) {
-    if (side.dst) {                                            // concat slot 0
-        const int64_t stotal = side.rows * side.cols;
-        for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < stotal; t += (int64_t)gridDim.x * blockDim.x) {
-            const int64_t i = t / side.cols, c = t - i * side.cols;
-            const float v = side.src[i * side.ld_src + c];
-            side.dst[i * side.ld_dst + c] = side.mode ? fabsf(v) : v;
-        }
-    }
+    // concat slot 0
+    gn::side_copy_stream(side, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
     const int64_t total = rows * cols;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t i = t / cols;

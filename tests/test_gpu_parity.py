@@ -1294,6 +1294,60 @@ def test_bf16_group_gather_on_many_short_rows(gpu, fout):
     assert float((y16.cpu() - ref32).abs().max()) <= 2.0 ** -7 * max(float(ref32.abs().max()), 1.0)
 
 
+# kernel of the gather-reduce family: (rows, edges per row, table width, width after weight= or None, bf16 storage); the
+# smallest shapes that still select it (aggregate.hip: launch_aggregate and its siblings, graph_bf16.hip)
+_SIDE_COPY_CASES = {
+    "wave-per-row-scalar": (64, 50, 6, None, False),          # features % 4 != 0: the unaligned fallback
+    "wave-per-row-float4": (64, 50, 8, None, False),          # >= GN_AGG_GROUP_MAX_DEG edges a row
+    "short": (200, 3, 16, None, False),                       # < GN_AGG_SHORT_MAX_DEG edges a row
+    "group": (200, 20, 32, None, False),
+    "fused-transform": (200, 20, 32, 16, False),
+    "quad-transform": (200, 20, 16, 16, False),
+    "matrix-core": (4100, 10, 64, 64, False),                 # >= 4096 rows
+    "bf16-wave-per-row": (200, 20, 24, None, True),           # < 4096 rows
+    "bf16-group": (4100, 10, 32, None, True),
+}
+
+
+# (with GN_DISABLE_FAST=1 these select another kernel, or - weight= - are refused: transform_fusable says no)
+_SIDE_COPY_FAST = ("short", "group", "fused-transform", "quad-transform", "matrix-core", "bf16-group")
+
+
+@pytest.mark.parametrize("kernel", [pytest.param(k, marks=needs_fast_paths) if k in _SIDE_COPY_FAST else k for k in _SIDE_COPY_CASES])
+def test_gather_family_side_copy_on_every_kernel(gpu, kernel):
+    """Every kernel of the gather-reduce family streams the launch's side copy (a concat slot) with the same loop: a
+    source of fewer rows than the launch, a destination slice of a wider matrix, both modes (copy, abs).  The slot holds
+    the source bit for bit, the columns around it keep their fill, and the launch's own output is the oracle's.  (The
+    LDS-table kernel is never selected with a side copy.)"""
+    rows, deg, fin, fout, bf16 = _SIDE_COPY_CASES[kernel]
+    gen = torch.Generator().manual_seed(rows + 7 * fin)
+    ei = torch.stack([torch.randint(0, rows, (rows * deg,), generator=gen), torch.arange(rows).repeat_interleave(deg)])
+    w = torch.rand(rows * deg, generator=gen) + 0.5
+    x = torch.randn(rows, fin, generator=gen)
+    width = fout or fin
+    weight = None if fout is None else torch.randn(fin, fout, generator=gen) / fin ** 0.5
+    bias = torch.randn(width, generator=gen)
+    src = torch.randn(37, 5, generator=gen)
+    ei2, norm = orc.gcn_norm(ei, rows, w)
+    table = _bf16_round(x) if bf16 else x
+    ref = torch.zeros(rows, fin).index_add_(0, ei2[1], norm.view(-1, 1) * table.index_select(0, ei2[0]))
+    ref = torch.relu((ref if weight is None else ref @ weight) + bias)
+    plan = _hip.GraphPlan.gcn(ei.to(gpu), rows, w.to(gpu))
+    if weight is not None:
+        assert plan.transform_ok(fin, fout, x.to(gpu))
+    for mode in (0, 1):
+        wide = torch.full((37, 9), float("nan"), device=gpu)
+        out = torch.full((rows, width), float("nan"), device=gpu)
+        side = (src.to(gpu), wide[:, 2:7], mode)
+        if bf16:
+            plan.aggregate_bf16(x.to(gpu), bias.to(gpu), True, out, side=side)
+        else:
+            plan.aggregate(x.to(gpu), bias.to(gpu), True, out, side=side, weight=None if weight is None else weight.to(gpu))
+        assert torch.equal(wide[:, 2:7].cpu(), src.abs() if mode else src), (kernel, mode)
+        assert torch.isnan(wide[:, :2]).all() and torch.isnan(wide[:, 7:]).all(), (kernel, mode)
+        close(out, ref)
+
+
 def test_nc_pipeline_with_bf16_tables(gpu, golden):
     """The aminer pipeline of the golden fixtures with bf16 tables in every GCN-style layer: class probabilities within
     5e-3 of the reference's fp32 result (three stacked layers of rounded tables), argmax unchanged on >= 99 % of nodes."""
