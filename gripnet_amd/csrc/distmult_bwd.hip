@@ -18,7 +18,7 @@
 // ~10^3 relations - the LDS path below is used instead:
 //   * dz: ONE sort of 2 E half-edge records (key = the node that receives, payload = the other endpoint, the
 //     relation and g) - dz[i] = sum over the records of i of g z[other] * D[r]; a counting sort on wave-private LDS
-//     histograms for up to 4,096 nodes (count pass, scan, scatter pass staged through LDS), rocPRIM's radix sort beyond;
+//     histograms (count pass, offsets, scatter pass staged through LDS): every node table that fits the LDS fits them;
 //   * dD: when the caller says edge_type is sorted (GN_DM_TYPES_SORTED; it is in the reference's layout,
 //     utils.py:168-198) the records stay in edge order and the row offsets come from a binary search;
 //   * k_seg_lds: a workgroup keeps a 16-column block of both tables in LDS, a wave owns a task (<= 512 records of
@@ -29,7 +29,6 @@
 #include "common.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
 
 #include <unordered_map>
 #include <vector>
@@ -251,20 +250,6 @@ constexpr size_t kLdsTableBudget = 150 * 1024;
 
 __device__ __forceinline__ uint64_t pack_rec(uint32_t a, uint32_t b, float g) {
     return (uint64_t)(a | (b << 16)) | ((uint64_t)__float_as_uint(g) << 32);
-}
-
-// two half-edge records per edge, in edge order (the sort is stable, so the records of a node stay in edge order)
-__global__ void k_half_recs(const int64_t* __restrict__ u, const int64_t* __restrict__ v, const int64_t* __restrict__ et,
-                            GradSrc gs, int64_t E, int64_t n, int64_t R, uint32_t* __restrict__ keys,
-                            uint64_t* __restrict__ recs) {
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t uu = u[e], vv = v[e], rr = et[e];
-        const bool ok = (uint64_t)uu < (uint64_t)n && (uint64_t)vv < (uint64_t)n && (uint64_t)rr < (uint64_t)R;
-        const float g = ok ? gs.at(e) : 0.f;
-        reinterpret_cast<uint2*>(keys)[e] = ok ? make_uint2((uint32_t)uu, (uint32_t)vv) : make_uint2((uint32_t)n, (uint32_t)n);
-        recs[2 * e] = ok ? pack_rec((uint32_t)vv, (uint32_t)rr, g) : 0ull;
-        recs[2 * e + 1] = ok ? pack_rec((uint32_t)uu, (uint32_t)rr, g) : 0ull;
-    }
 }
 
 // one record per edge for dD: (u, v, g); keys only when a sort follows
@@ -750,6 +735,9 @@ __global__ __launch_bounds__(256) void k_seg_lds_combine(CombineSet first, int f
     }
 }
 
+// ---- host side ----------------------------------------------------------------------------------------------------
+// The general path's scratch, and the LDS path's over the same bytes (a call that takes the LDS path for dD only runs its
+// general passes after it).
 struct WsLayout { size_t keys, keys_sorted, recs, recs_sorted, rowptr, partial, sort_tmp, total; };
 
 WsLayout ws_layout(int64_t e, int64_t max_rows) {
@@ -768,42 +756,119 @@ WsLayout ws_layout(int64_t e, int64_t max_rows) {
     return l;
 }
 
-struct LdsLayout { size_t keys, keys_sorted, recs, recs_sorted, rowptr, taskptr, tasks, partial, counts, sort_tmp, sort_tmp_bytes, total; };
+// A table block of 16 columns is 64 bytes per row; the LDS path keeps z and D (node-major reduction) or z alone
+// (relation-major) in LDS.  The counting sort takes every node count that fits, and the 16-bit ids of the packed record hold
+// every id of such tables: no run-time test of either.
+bool tables_fit_lds(int64_t rows) { return (size_t)rows * 64 <= kLdsTableBudget; }
+static_assert(kLdsTableBudget / 64 <= kSortMaxKeys, "every node table that fits the LDS fits the counting sort's histograms");
+static_assert(kLdsTableBudget / 64 <= 65535, "every row of a table that fits the LDS has a 16-bit id");
+
+struct LdsLayout { size_t keys, keys_sorted, recs, recs_sorted, rowptr, taskptr, tasks, partial, partial_dd, counts, sort_tmp, sort_tmp_bytes, total; };
 
 int64_t lds_max_tasks(int64_t records, int64_t keys) { return records / kTaskRecs + keys + 1; }
 
+// a static edge_type's offsets with the task list of the relation-major reduction behind them (GN_DM_TYPE_TASKS)
+struct TypeTasks { size_t taskptr, tasks, total; };           // in int32 words
+TypeTasks type_tasks_layout(int64_t r, int64_t e) {
+    TypeTasks t;
+    t.taskptr = (size_t)((r + 2 + 63) & ~(int64_t)63);
+    t.tasks = t.taskptr + (size_t)((r + 2 + 63) & ~(int64_t)63);
+    t.total = t.tasks + (size_t)lds_max_tasks(e, r) * 4;
+    return t;
+}
+
 LdsLayout lds_layout(int64_t e, int64_t n, int64_t r, int64_t f) {
     LdsLayout l;
-    size_t sort_bytes = 0;
+    size_t sort_bytes = 0;                                                     // the one sort of this path: dD's E pairs under unsorted types
     (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint64_t*)nullptr,
-                                    (uint64_t*)nullptr, (size_t)(2 * e), 0, 32, (hipStream_t)0);
+                                    (uint64_t*)nullptr, (size_t)e, 0, 32, (hipStream_t)0);
     const int64_t rows = std::max(n, r);
-    const int64_t tasks = lds_max_tasks(2 * e, n) + lds_max_tasks(e, r);        // both reductions' partial sums side by side
+    const int64_t tasks_dz = lds_max_tasks(2 * e, n), tasks = tasks_dz + lds_max_tasks(e, r);   // both reductions' partial sums side by side
     l.keys = 0;
-    l.keys_sorted = l.keys + align_up(2 * e * sizeof(uint32_t));
-    l.recs = l.keys_sorted + align_up(2 * e * sizeof(uint32_t));
-    l.recs_sorted = l.recs + align_up((2 * e + 64) * sizeof(uint64_t));
+    l.keys_sorted = l.keys + align_up(e * sizeof(uint32_t));
+    l.recs = l.keys_sorted + align_up(e * sizeof(uint32_t));
+    l.recs_sorted = l.recs + align_up((2 * e + 64) * sizeof(uint64_t));       // (the scatter's spare slots sit at 2 E)
     l.rowptr = l.recs_sorted + align_up((2 * e + 64) * sizeof(uint64_t));
     l.taskptr = l.rowptr + align_up((rows + 2) * sizeof(int32_t));
     l.tasks = l.taskptr + align_up((rows + 2) * sizeof(int32_t));
     l.partial = l.tasks + align_up((size_t)tasks * sizeof(int4));
+    l.partial_dd = l.partial + (size_t)tasks_dz * f * sizeof(float);
     l.counts = l.partial + align_up((size_t)tasks * f * sizeof(float));
-    const size_t cells = n <= kSortMaxKeys ? (size_t)n * kSortWaves + 1 : 1;
-    size_t scan_bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, 0, cells, rocprim::plus<int32_t>(),
-                                  (hipStream_t)0);
+    const size_t cells = tables_fit_lds(n + r) ? (size_t)n * kSortWaves + 1 : 0;   // (node, wave): where the counting sort can run
     l.sort_tmp = l.counts + align_up(cells * sizeof(int32_t));
-    l.sort_tmp_bytes = align_up(std::max(sort_bytes, scan_bytes));
+    l.sort_tmp_bytes = align_up(sort_bytes);
     l.total = l.sort_tmp + l.sort_tmp_bytes;
     return l;
 }
 
-// what the LDS path takes: 16-bit ids in the packed record, float4 columns, the table blocks inside the LDS
-bool lds_path_shapes(int64_t n, int64_t f, int64_t r) {
-    return !gn::fast_paths_disabled() && n <= 65535 && r <= 65535 && f % 4 == 0 && f >= 4;
+struct LdsWs {
+    uint32_t *keys, *keys_sorted;
+    uint64_t *recs, *recs_sorted;
+    int32_t *rowptr, *taskptr;
+    int4* tasks;
+    float *partial_dz, *partial_dd;
+    int32_t* counts;
+    void* sort_tmp; size_t sort_tmp_bytes;
+};
+
+LdsWs carve(char* ws, const LdsLayout& l) {
+    LdsWs w;
+    w.keys = reinterpret_cast<uint32_t*>(ws + l.keys);
+    w.keys_sorted = reinterpret_cast<uint32_t*>(ws + l.keys_sorted);
+    w.recs = reinterpret_cast<uint64_t*>(ws + l.recs);
+    w.recs_sorted = reinterpret_cast<uint64_t*>(ws + l.recs_sorted);
+    w.rowptr = reinterpret_cast<int32_t*>(ws + l.rowptr);
+    w.taskptr = reinterpret_cast<int32_t*>(ws + l.taskptr);
+    w.tasks = reinterpret_cast<int4*>(ws + l.tasks);
+    w.partial_dz = reinterpret_cast<float*>(ws + l.partial);
+    w.partial_dd = reinterpret_cast<float*>(ws + l.partial_dd);
+    w.counts = reinterpret_cast<int32_t*>(ws + l.counts);
+    w.sort_tmp = ws + l.sort_tmp;
+    w.sort_tmp_bytes = l.sort_tmp_bytes;
+    return w;
 }
-bool lds_dz_fits(int64_t n, int64_t r) { return (size_t)(n + r) * 64 <= kLdsTableBudget; }
-bool lds_dd_fits(int64_t n) { return (size_t)n * 64 <= kLdsTableBudget; }
+
+// what both float4 reductions (k_seg_reduce, k_seg_lds) read and write: rows of 16-byte columns
+bool float4_rows(int64_t f, const float* z, int64_t ld_z, const float* d, int64_t ld_d, const float* dz, int64_t ld_dz,
+                 const float* dd, int64_t ld_dd) {
+    return f % 4 == 0 && ld_z % 4 == 0 && ld_d % 4 == 0 && ld_dz % 4 == 0 && ld_dd % 4 == 0 && gn::aligned16(z) && gn::aligned16(d) &&
+           gn::aligned16(dz) && gn::aligned16(dd);
+}
+
+// Which reduction takes which path.  The one place that decides it: the entry points' refusals, the plan builder's guard and
+// the passes below read the answer.
+struct Route {
+    bool vec;              // float4 rows (the general path's k_seg_reduce; its scalar kernel otherwise)
+    bool counting_dz;      // dz: counting sort + node-major LDS reduction; z and D in LDS.  Implies lds_dd
+    bool lds_dd;           // dD: relation-major LDS reduction; z in LDS
+    bool types_sorted;     // GN_DM_TYPES_SORTED: the dD records stay in list order
+    bool listed;           // the caller's type offsets bring the relation-major task list (GN_DM_TYPE_TASKS)
+    bool both;             // both reductions in LDS and combined in one launch (the scratch holds one task list: the node-major
+                           // one's outlives its combine only when the relation-major one brings its own)
+};
+
+// the shape part: what a plan builder knows (no features or pointers yet)
+Route route_of_shapes(int64_t n, int64_t r, int64_t e) {
+    Route rt = {};
+    const bool on = !gn::fast_paths_disabled() && 2 * e + 64 < (1ll << 31);     // (record positions are 32-bit)
+    rt.counting_dz = on && tables_fit_lds(n + r);
+    // r <= 65535 is implied for dz.  For dD it decides (200 nodes x 65,536 relations) and nothing in the relation-major reduction
+    // needs it - its records hold node ids, the relation is a 32-bit task key: it is kept only so that no shape changes its route
+    rt.lds_dd = on && tables_fit_lds(n) && r <= 65535;
+    return rt;
+}
+
+Route route_of(int64_t n, int64_t f, int64_t r, int64_t e, int flags, const int32_t* type_offsets, const float* z, int64_t ld_z,
+               const float* d, int64_t ld_d, const float* dz, int64_t ld_dz, const float* dd, int64_t ld_dd) {
+    Route rt = route_of_shapes(n, r, e);
+    rt.vec = float4_rows(f, z, ld_z, d, ld_d, dz, ld_dz, dd, ld_dd);
+    rt.counting_dz = rt.counting_dz && rt.vec;
+    rt.lds_dd = rt.lds_dd && rt.vec;
+    rt.types_sorted = (flags & GN_DM_TYPES_SORTED) != 0;
+    rt.listed = rt.lds_dd && rt.types_sorted && type_offsets && (flags & GN_DM_TYPE_TASKS);
+    rt.both = rt.counting_dz && rt.listed;
+    return rt;
+}
 
 gn_status launch_seg_lds(const uint64_t* recs, const int32_t* rowptr, int64_t rowptr_stride, int32_t* taskptr, int4* tasks, int64_t keys,
                          const float* A, int64_t ld_a,
@@ -840,6 +905,205 @@ gn_status combine_both(const CombineSet& a, int64_t keys_a, const CombineSet& b,
     return GN_OK;
 }
 
+// The counting sort up to its scatter: the (node, wave) counts, then every cell's write offset in place (`counts`, with the
+// record count in the cell behind the last node) and the task list of the node-major reduction.  `totals`: n words of scratch.
+gn_status count_half_edges(const EdgeSrc& edges, const GradSrc& grad, int64_t E, int64_t n, int64_t R, int32_t* counts, int32_t* totals,
+                           int32_t* taskptr, int4* tasks, hipStream_t st) {
+    { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_he_sort<false>), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
+    const size_t hist_bytes = (size_t)kSortWavesPerWg * n * sizeof(int32_t);
+    k_he_sort<false><<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, hist_bytes, st>>>(edges, grad, E, (int)n, R, counts, nullptr, nullptr);
+    GN_LAUNCH_CHECK();
+    k_node_totals<<<(unsigned)n, kOffsetThreads, 0, st>>>(counts, totals);
+    GN_LAUNCH_CHECK();
+    k_he_offsets<<<(unsigned)n, kOffsetThreads, 0, st>>>(counts, totals, (int)n, taskptr, tasks);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+// The counting sort's scatter pass: staged through LDS where a workgroup's records fit next to its offsets, placed directly
+// otherwise.  The direct pass advances `offsets` in place; a caller that keeps them hands over the scratch its copy comes from.
+gn_status launch_he_scatter(const EdgeSrc& edges, const GradSrc& grad, int64_t E, int64_t n, int64_t R, int32_t* offsets, uint64_t* recs,
+                            uint64_t* pair_recs, gn::Scratch* keep_offsets, hipStream_t st) {
+    const unsigned grid = kSortWaves / kSortWavesPerWg, block = kSortWavesPerWg * 64;
+    const size_t hist_bytes = (size_t)kSortWavesPerWg * n * sizeof(int32_t);
+    const size_t stage_cap = (size_t)2 * gn::ceil_div(E, kSortWaves) * kSortWavesPerWg;
+    const size_t staged_bytes = hist_bytes + (2 * (size_t)n + 2 + 1) * sizeof(int32_t) + stage_cap * sizeof(uint64_t);
+    if (staged_bytes <= 127 * 1024) {                      // (78 KB on pose0-syn: two workgroups per CU)
+        { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_he_scatter_staged), 128 * 1024); if (lds_status != GN_OK) return lds_status; }
+        k_he_scatter_staged<<<grid, block, staged_bytes, st>>>(edges, grad, E, (int)n, R, offsets, recs, pair_recs, (int)stage_cap);
+    } else {
+        if (keep_offsets) {
+            const size_t cells = (size_t)n * kSortWaves + 1;
+            int32_t* copy;
+            GN_HIP(keep_offsets->get(&copy, cells));
+            GN_HIP(hipMemcpyAsync(copy, offsets, cells * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+            offsets = copy;
+        }
+        { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_he_sort<true>), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
+        k_he_sort<true><<<grid, block, hist_bytes, st>>>(edges, grad, E, (int)n, R, offsets, recs, pair_recs);
+    }
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+// one call's operands, as the entry points receive them
+struct Call {
+    const float* z; int64_t ld_z, n, f;
+    EdgeSrc edges;
+    const float* d; int64_t ld_d, r, e;
+    GradSrc grad;
+    float* dz; int64_t ld_dz;
+    float* dd; int64_t ld_dd;
+    hipStream_t st;
+};
+
+// dz on the LDS path: half-edge records straight into node order, then the node-major reduction.  `pair_recs`: where the same
+// pass leaves the list-order records of dD (null: nobody wants them).
+gn_status dz_counting_sort(const Call& c, const LdsWs& w, uint64_t* pair_recs, CombineSet* defer) {
+    // (the totals sit in the row-offset scratch, unused on this path)
+    gn_status rc = count_half_edges(c.edges, c.grad, c.e, c.n, c.r, w.counts, w.rowptr, w.taskptr, w.tasks, c.st);
+    if (rc != GN_OK) return rc;
+    rc = launch_he_scatter(c.edges, c.grad, c.e, c.n, c.r, w.counts, w.recs_sorted, pair_recs, nullptr, c.st);
+    if (rc != GN_OK) return rc;
+    return launch_seg_lds(w.recs_sorted, w.counts, kSortWaves, w.taskptr, w.tasks, c.n, c.z, c.ld_z, c.n, c.d, c.ld_d, c.r, c.f, w.partial_dz,
+                          c.dz, c.ld_dz, c.st, true, defer);
+}
+
+// dD on the LDS path.  `have_recs`: the counting sort left the list-order records in w.recs.
+gn_status dd_lds(const Call& c, const LdsWs& w, const Route& rt, const int32_t* type_offsets, bool have_recs, CombineSet* defer) {
+    const int64_t e = c.e, r = c.r;
+    hipStream_t st = c.st;
+    if (!have_recs) {
+        k_pair_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(c.edges.u, c.edges.v, c.edges.et, c.grad, e, c.n, r, rt.types_sorted ? nullptr : w.keys, w.recs);
+        GN_LAUNCH_CHECK();
+    }
+    const uint64_t* recs = w.recs;
+    const int32_t* rowptr = w.rowptr;
+    if (rt.types_sorted && type_offsets) {
+        rowptr = type_offsets;                             // the caller keeps them with its static edge_type
+    } else if (rt.types_sorted) {
+        k_key_offsets64<<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(c.edges.et, e, (int)r, w.rowptr);
+        GN_LAUNCH_CHECK();
+    } else {
+        size_t sort_bytes = w.sort_tmp_bytes;
+        GN_HIP(rocprim::radix_sort_pairs(w.sort_tmp, sort_bytes, w.keys, w.keys_sorted, w.recs, w.recs_sorted, (size_t)e, 0, bits_for(r + 1), st));
+        k_key_offsets<<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(w.keys_sorted, e, (int)r, w.rowptr);
+        GN_LAUNCH_CHECK();
+        recs = w.recs_sorted;
+    }
+    int32_t* taskptr = w.taskptr;
+    int4* tasks = w.tasks;
+    if (rt.listed) {
+        const TypeTasks t = type_tasks_layout(r, e);
+        taskptr = const_cast<int32_t*>(type_offsets) + t.taskptr;
+        tasks = reinterpret_cast<int4*>(const_cast<int32_t*>(type_offsets) + t.tasks);
+    }
+    return launch_seg_lds(recs, rowptr, 1, taskptr, tasks, r, c.z, c.ld_z, c.n, c.z, c.ld_z, c.n, c.f, w.partial_dd, c.dd, c.ld_dd, st, rt.listed, defer);
+}
+
+// One pass of the general path: records of the mode (k_make_recs), radix sort, row offsets, segmented reduction from L2.
+gn_status general_pass(int mode, const Call& c, bool vec, char* ws, const WsLayout& l) {
+    uint32_t* keys = reinterpret_cast<uint32_t*>(ws + l.keys);
+    uint32_t* keys_sorted = reinterpret_cast<uint32_t*>(ws + l.keys_sorted);
+    Rec* recs = reinterpret_cast<Rec*>(ws + l.recs);
+    Rec* recs_sorted = reinterpret_cast<Rec*>(ws + l.recs_sorted);
+    int32_t* rowptr = reinterpret_cast<int32_t*>(ws + l.rowptr);
+    float* partial = reinterpret_cast<float*>(ws + l.partial);
+    size_t sort_bytes = l.total - l.sort_tmp;
+    const int64_t e = c.e, f = c.f;
+    hipStream_t st = c.st;
+    const unsigned chunks = (unsigned)gn::ceil_div(e, kChunkRecs);
+    const int64_t rows = mode == 2 ? c.r : c.n;
+    const float* A = c.z;                                // a is always a node id
+    const int64_t ld_a = c.ld_z;
+    const float* B = mode == 2 ? c.z : c.d;              // b: relation row of D, or the other endpoint's z row
+    const int64_t ld_b = mode == 2 ? c.ld_z : c.ld_d;
+    float* out = mode == 2 ? c.dd : c.dz;
+    const int64_t ld_out = mode == 2 ? c.ld_dd : c.ld_dz;
+    const int accumulate = mode == 1;                    // dz = u-side pass, then + v-side pass
+    k_make_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(mode, c.edges.u, c.edges.v, c.edges.et, c.grad, e, c.n, c.r, (uint32_t)rows, keys, recs);
+    GN_LAUNCH_CHECK();
+    GN_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, sort_bytes, keys, keys_sorted, recs, recs_sorted, (size_t)e, 0, bits_for(rows + 1), st));
+    k_key_offsets<<<(int)gn::ceil_div(rows + 1, 256), 256, 0, st>>>(keys_sorted, e, (int)rows, rowptr);
+    GN_LAUNCH_CHECK();
+    if (!vec) {
+        k_seg_reduce_scalar<<<(unsigned)rows, 256, 0, st>>>(rowptr, recs_sorted, A, ld_a, B, ld_b, out, ld_out, (int)f, accumulate);
+        GN_LAUNCH_CHECK();
+        return GN_OK;
+    }
+    for (int c0 = 0; c0 < f; c0 += 64) {
+        const int width = (int)std::min<int64_t>(64, f - c0);
+        if (width > 32)
+            k_seg_reduce<16><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b, out, ld_out, partial, c0, width,
+                                                     accumulate);
+        else if (width > 16)
+            k_seg_reduce<8><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b, out, ld_out, partial, c0, width,
+                                                    accumulate);
+        else
+            k_seg_reduce<4><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b, out, ld_out, partial, c0, width,
+                                                    accumulate);
+        GN_LAUNCH_CHECK();
+        k_seg_combine<<<(unsigned)rows, 64, 0, st>>>(rowptr, keys_sorted, e, (int)rows, partial, out, ld_out, c0, width, accumulate);
+        GN_LAUNCH_CHECK();
+    }
+    return GN_OK;
+}
+
+// gradients of an empty sum
+gn_status zero_gradients(float* dz, int64_t ld_dz, int64_t n, float* dd, int64_t ld_dd, int64_t r, int64_t f, hipStream_t st) {
+    if (n > 0 && f > 0) GN_HIP(hipMemset2DAsync(dz, ld_dz * sizeof(float), 0, f * sizeof(float), n, st));
+    if (r > 0 && f > 0) GN_HIP(hipMemset2DAsync(dd, ld_dd * sizeof(float), 0, f * sizeof(float), r, st));
+    return GN_OK;
+}
+
+gn_status backward_impl(const float* z, int64_t ld_z, int64_t n, int64_t f, const EdgeSrc& edges, const float* d, int64_t ld_d,
+                        int64_t r, int64_t e, const float* grad_logit, float* dz, int64_t ld_dz,
+                        float* dd, int64_t ld_dd, int flags, const float* sigmoid_scores,
+                        const int32_t* type_offsets, void* workspace, size_t workspace_bytes,
+                        void* stream, const gn_link_loss_grad* loss = nullptr, const float* dz_add = nullptr, int64_t ld_dz_add = 0,
+                        const float* dd_add = nullptr, int64_t ld_dd_add = 0) {
+    const bool from_words = edges.packed != nullptr;           // no int64 arrays: the counting-sort / LDS path or nothing
+    GN_REQUIRE(n >= 0 && f >= 0 && r >= 0 && e >= 0, "negative size");
+    GN_REQUIRE(f < (1ll << 31) && n < (1ll << 31) && r < (1ll << 31) && e < (1ll << 31), "table or edge list too large");
+    GN_REQUIRE((n == 0 || f == 0 || dz) && (r == 0 || f == 0 || dd), "gradient output pointer is null");
+    GN_REQUIRE(ld_dz >= f && ld_dd >= f, "leading dimension smaller than the row length");
+    hipStream_t st = gn::as_stream(stream);
+    if (e == 0 || f == 0 || n == 0 || r == 0) {
+        const gn_status rc = zero_gradients(dz, ld_dz, n, dd, ld_dd, r, f, st);
+        if (rc != GN_OK) return rc;
+        GN_REQUIRE(e == 0 || f == 0 || (n > 0 && r > 0), "edges given but the node or relation table is empty");
+        return GN_OK;
+    }
+    GN_REQUIRE(z && d && (loss ? sigmoid_scores != nullptr : grad_logit != nullptr) &&
+               (from_words ? edges.rel16 != nullptr : (edges.u && edges.v && edges.et)), "operand pointer is null");
+    GN_REQUIRE(ld_z >= f && ld_d >= f, "leading dimension smaller than the row length");
+    const WsLayout l = ws_layout(e, std::max(n, r));
+    const LdsLayout ll = lds_layout(e, n, r, f);
+    GN_REQUIRE(workspace && workspace_bytes >= std::max(l.total, ll.total), "workspace too small: need %zu bytes",
+               std::max(l.total, ll.total));
+    char* ws = static_cast<char*>(workspace);
+    const Route rt = route_of(n, f, r, e, flags, type_offsets, z, ld_z, d, ld_d, dz, ld_dz, dd, ld_dd);
+    if (from_words && !(rt.counting_dz && rt.types_sorted && type_offsets))
+        return gn::fail(GN_ERR_UNSUPPORTED, "packed pairs: only the counting-sort path (tables in LDS, sorted edge_type with its offsets); use gn_distmult_backward_ex_f32");
+    if ((dz_add || dd_add) && !rt.both)
+        return gn::fail(GN_ERR_UNSUPPORTED, "addends ride on the common combine launch of the two LDS reductions: not taken for these shapes / flags");
+    const Call c = {z, ld_z, n, f, edges, d, ld_d, r, e, make_grad_src(grad_logit, sigmoid_scores, loss, e), dz, ld_dz, dd, ld_dd, st};
+    const LdsWs w = carve(ws, ll);
+    CombineSet cz, cd;
+    gn_status rc = GN_OK;
+    const bool pairs_by_sort = rt.counting_dz && rt.types_sorted;      // the dD records come out of the sort's scatter pass
+    if (rt.counting_dz) rc = dz_counting_sort(c, w, pairs_by_sort ? w.recs : nullptr, rt.both ? &cz : nullptr);
+    if (rc == GN_OK && rt.lds_dd) rc = dd_lds(c, w, rt, type_offsets, pairs_by_sort, rt.both ? &cd : nullptr);
+    if (rc == GN_OK && rt.both) {
+        cz.add = dz_add; cz.ld_add = ld_dz_add; cd.add = dd_add; cd.ld_add = ld_dd_add;
+        rc = combine_both(cz, n, cd, r, f, st);
+    }
+    if (rc == GN_OK && !rt.counting_dz) rc = general_pass(0, c, rt.vec, ws, l);        // key = u
+    if (rc == GN_OK && !rt.counting_dz) rc = general_pass(1, c, rt.vec, ws, l);        // + key = v
+    if (rc == GN_OK && !rt.lds_dd) rc = general_pass(2, c, rt.vec, ws, l);
+    return rc;
+}
+
 
 // ---- a static edge list (the positive edges of a training loop: the same tensors every epoch) -----------------------
 // What the sort and the reductions derive from the triples alone is kept: the pairing of an edge's two directions, the
@@ -848,321 +1112,6 @@ gn_status combine_both(const CombineSet& a, int64_t keys_a, const CombineSet& b,
 // places them into the node-order records (k_place_g: 2 M random 4-byte reads, 19.5 us - the scatter pass it replaces took
 // 26 us plus the list-order records; without the pairing the gather is 4 M reads and loses to the scatter) and runs the two
 // segment reductions and their common combine: 5 launches.
-}  // namespace
-
-struct gn_distmult_bwd_plan {
-    int64_t e = 0, n = 0, r = 0, he_tasks_max = 0, pr_tasks_max = 0;   // e: triples after pairing (below)
-    int64_t e_list = 0;                             // triples of the caller's list
-    // Two triples with the same unordered node pair and relation (the two directions of an edge) produce the same
-    // records but for g: they are reduced as ONE triple with g1 + g2.  eu / ev / er: the triples that are left, in list
-    // order; own / mir: where their gradients sit in the caller's list (mir = kNoPair: unpaired).
-    gn::DevBuf<int64_t> eu, ev, er;
-    gn::DevBuf<uint32_t> own, mir;
-    gn::DevBuf<int32_t> offsets;                    // [n * kSortWaves + 1] where every wave's records of every node start
-    gn::DevBuf<int32_t> he_taskptr, pr_taskptr;     // [n + 1], [R + 1]
-    gn::DevBuf<int32_t> he_tasks, pr_tasks;         // int4 descriptors
-    // The half-edge records in node order and the pair records in list order with the POSITION of their triple (in eu / ev /
-    // er) where the gradient goes: what a step's gradients are placed into (k_place_g), instead of sorting every step.
-    gn::DevBuf<uint64_t> he_static, pr_static;      // [2 e + 64], [e + 64]
-};
-
-namespace {
-
-void bwd_plan_free(gn_distmult_bwd_plan* p) {
-    if (!p) return;
-    p->eu.release(); p->ev.release(); p->er.release(); p->own.release(); p->mir.release();
-    p->offsets.release(); p->he_taskptr.release(); p->pr_taskptr.release(); p->he_tasks.release(); p->pr_tasks.release();
-    p->he_static.release(); p->pr_static.release();
-    delete p;
-}
-
-struct PlanWs { size_t g, he, pr, partial, total; };
-PlanWs plan_ws(const gn_distmult_bwd_plan* p, int64_t f) {
-    PlanWs w;
-    w.g = 0;
-    w.he = w.g + align_up((size_t)(p->e + 64) * sizeof(float));
-    w.pr = w.he + align_up((size_t)(2 * p->e + 64) * sizeof(uint64_t));
-    w.partial = w.pr + align_up((size_t)(2 * p->e + 64) * sizeof(uint64_t));
-    w.total = w.partial + align_up((size_t)(p->he_tasks_max + p->pr_tasks_max) * f * sizeof(float));   // both reductions' partial sums (one combine launch)
-    return w;
-}
-
-}  // namespace
-
-namespace {
-// a static edge_type's offsets with the task list of the relation-major reduction behind them (GN_DM_TYPE_TASKS)
-struct TypeTasks { size_t taskptr, tasks, total; };           // in int32 words
-TypeTasks type_tasks_layout(int64_t r, int64_t e) {
-    TypeTasks t;
-    t.taskptr = (size_t)((r + 2 + 63) & ~(int64_t)63);
-    t.tasks = t.taskptr + (size_t)((r + 2 + 63) & ~(int64_t)63);
-    t.total = t.tasks + (size_t)lds_max_tasks(e, r) * 4;
-    return t;
-}
-}  // namespace
-
-extern "C" size_t gn_distmult_type_tasks_bytes(int64_t r, int64_t e) {
-    if (r <= 0 || e < 0) return 0;
-    return type_tasks_layout(r, e).total * sizeof(int32_t);
-}
-
-extern "C" gn_status gn_distmult_type_tasks(const int32_t* type_offsets, int64_t r, int64_t e, void* out, size_t out_bytes, void* stream) {
-    GN_REQUIRE(type_offsets && out && r > 0 && e >= 0, "null pointer or bad size");
-    GN_REQUIRE(r < (1ll << 31) && e < (1ll << 31), "too large");
-    GN_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "the buffer is not 16-byte aligned");
-    const TypeTasks t = type_tasks_layout(r, e);
-    GN_REQUIRE(out_bytes >= t.total * sizeof(int32_t), "buffer too small: need %zu bytes", t.total * sizeof(int32_t));
-    hipStream_t st = gn::as_stream(stream);
-    int32_t* o = static_cast<int32_t*>(out);
-    if (o != type_offsets) GN_HIP(hipMemcpyAsync(o, type_offsets, (size_t)(r + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    k_task_ptr<<<1, 1024, 0, st>>>(o, 1, (int)r, o + t.taskptr, reinterpret_cast<int4*>(o + t.tasks));
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-extern "C" size_t gn_distmult_backward_workspace_bytes(int64_t n, int64_t f, int64_t r, int64_t e) {
-    if (n <= 0 || f <= 0 || r <= 0 || e <= 0) return 0;
-    return std::max(ws_layout(e, std::max(n, r)).total, lds_layout(e, n, r, f).total);
-}
-
-namespace {
-gn_status backward_impl(const float* z, int64_t ld_z, int64_t n, int64_t f, const EdgeSrc& edges, const float* d, int64_t ld_d,
-                        int64_t r, int64_t e, const float* grad_logit, float* dz, int64_t ld_dz,
-                        float* dd, int64_t ld_dd, int flags, const float* sigmoid_scores,
-                        const int32_t* type_offsets, void* workspace, size_t workspace_bytes,
-                        void* stream, const gn_link_loss_grad* loss = nullptr, const float* dz_add = nullptr, int64_t ld_dz_add = 0,
-                        const float* dd_add = nullptr, int64_t ld_dd_add = 0) {
-    const int64_t* u = edges.u;
-    const int64_t* v = edges.v;
-    const int64_t* et = edges.et;
-    const bool from_words = edges.packed != nullptr;           // no int64 arrays: the counting-sort / LDS path or nothing
-    GN_REQUIRE(n >= 0 && f >= 0 && r >= 0 && e >= 0, "negative size");
-    GN_REQUIRE(f < (1ll << 31) && n < (1ll << 31) && r < (1ll << 31) && e < (1ll << 31), "table or edge list too large");
-    GN_REQUIRE((n == 0 || f == 0 || dz) && (r == 0 || f == 0 || dd), "gradient output pointer is null");
-    GN_REQUIRE(ld_dz >= f && ld_dd >= f, "leading dimension smaller than the row length");
-    hipStream_t st = gn::as_stream(stream);
-    if (e == 0 || f == 0 || n == 0 || r == 0) {
-        if (n > 0 && f > 0) GN_HIP(hipMemset2DAsync(dz, ld_dz * sizeof(float), 0, f * sizeof(float), n, st));
-        if (r > 0 && f > 0) GN_HIP(hipMemset2DAsync(dd, ld_dd * sizeof(float), 0, f * sizeof(float), r, st));
-        GN_REQUIRE(e == 0 || f == 0 || (n > 0 && r > 0), "edges given but the node or relation table is empty");
-        return GN_OK;
-    }
-    GN_REQUIRE(z && d && (loss ? sigmoid_scores != nullptr : grad_logit != nullptr) && (from_words ? edges.rel16 != nullptr : (u && v && et)), "operand pointer is null");
-    const GradSrc grad = make_grad_src(grad_logit, sigmoid_scores, loss, e);
-    GN_REQUIRE(ld_z >= f && ld_d >= f, "leading dimension smaller than the row length");
-    const WsLayout l = ws_layout(e, std::max(n, r));
-    const LdsLayout ll = lds_layout(e, n, r, f);
-    GN_REQUIRE(workspace && workspace_bytes >= std::max(l.total, ll.total), "workspace too small: need %zu bytes",
-               std::max(l.total, ll.total));
-    char* ws = static_cast<char*>(workspace);
-    uint32_t* keys = reinterpret_cast<uint32_t*>(ws + l.keys);
-    uint32_t* keys_sorted = reinterpret_cast<uint32_t*>(ws + l.keys_sorted);
-    Rec* recs = reinterpret_cast<Rec*>(ws + l.recs);
-    Rec* recs_sorted = reinterpret_cast<Rec*>(ws + l.recs_sorted);
-    int32_t* rowptr = reinterpret_cast<int32_t*>(ws + l.rowptr);
-    float* partial = reinterpret_cast<float*>(ws + l.partial);
-    const unsigned chunks = (unsigned)gn::ceil_div(e, kChunkRecs);
-    size_t sort_bytes = l.total - l.sort_tmp;
-    const bool vec = (f % 4 == 0) && (ld_z % 4 == 0) && (ld_d % 4 == 0) && (ld_dz % 4 == 0) && (ld_dd % 4 == 0) &&
-                     ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(dz) |
-                       reinterpret_cast<uintptr_t>(dd)) & 15) == 0;
-
-    const bool lds_shapes = lds_path_shapes(n, f, r) && 2 * e + 64 < (1ll << 31) && (ld_z % 4 == 0) && (ld_d % 4 == 0) && (ld_dz % 4 == 0) && (ld_dd % 4 == 0) &&
-                            ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(dz) |
-                              reinterpret_cast<uintptr_t>(dd)) & 15) == 0;
-    const bool lds_dz = lds_shapes && lds_dz_fits(n, r), lds_dd = lds_shapes && lds_dd_fits(n);
-    if (from_words && !(lds_dz && lds_dd && n <= kSortMaxKeys && (flags & GN_DM_TYPES_SORTED) && type_offsets))
-        return gn::fail(GN_ERR_UNSUPPORTED, "packed pairs: only the counting-sort path (tables in LDS, sorted edge_type with its offsets); use gn_distmult_backward_ex_f32");
-    if (lds_dz || lds_dd) {
-        uint32_t* k2 = reinterpret_cast<uint32_t*>(ws + ll.keys);
-        uint32_t* k2s = reinterpret_cast<uint32_t*>(ws + ll.keys_sorted);
-        uint64_t* r2 = reinterpret_cast<uint64_t*>(ws + ll.recs);
-        uint64_t* r2s = reinterpret_cast<uint64_t*>(ws + ll.recs_sorted);
-        int32_t* rp = reinterpret_cast<int32_t*>(ws + ll.rowptr);
-        int32_t* tp = reinterpret_cast<int32_t*>(ws + ll.taskptr);
-        int4* tk = reinterpret_cast<int4*>(ws + ll.tasks);
-        const bool sorted_types = (flags & GN_DM_TYPES_SORTED) != 0;
-        bool pairs_done = false;
-        float* part = reinterpret_cast<float*>(ws + ll.partial);
-        float* part_dd = part + (size_t)lds_max_tasks(2 * e, n) * f;      // the relation-major reduction's partial sums
-        CombineSet cz, cd;                                                 // both reductions are combined in one launch ...
-        // ... when the relation-major one brings its task list (the scratch holds one list: the node-major one's must outlive its combine)
-        const bool listed = lds_dd && (flags & GN_DM_TYPES_SORTED) && type_offsets && (flags & GN_DM_TYPE_TASKS);
-        const bool both = lds_dz && listed;
-        if ((dz_add || dd_add) && !both)
-            return gn::fail(GN_ERR_UNSUPPORTED, "addends ride on the common combine launch of the two LDS reductions: not taken for these shapes / flags");
-        size_t sort2 = ll.sort_tmp_bytes;
-        if (lds_dz && n <= kSortMaxKeys) {
-            static thread_local bool sort_configured = false;
-            if (!sort_configured) {
-                GN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_he_sort<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                GN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_he_sort<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                GN_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_he_scatter_staged), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                sort_configured = true;
-            }
-            int32_t* counts = reinterpret_cast<int32_t*>(ws + ll.counts);
-            const size_t hist_bytes = (size_t)kSortWavesPerWg * n * sizeof(int32_t);
-            k_he_sort<false><<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, hist_bytes, st>>>(edges, grad, e, (int)n, r,
-                                                                                                   counts, nullptr, nullptr);
-            GN_LAUNCH_CHECK();
-            // offsets of every (node, wave) cell + the reduction's task list (the totals sit in the row-offset scratch, unused on this path)
-            k_node_totals<<<(unsigned)n, kOffsetThreads, 0, st>>>(counts, rp);
-            GN_LAUNCH_CHECK();
-            k_he_offsets<<<(unsigned)n, kOffsetThreads, 0, st>>>(counts, rp, (int)n, tp, tk);
-            GN_LAUNCH_CHECK();
-            pairs_done = lds_dd && sorted_types;               // the dD records come out of the same pass
-            const int64_t per_wave = gn::ceil_div(e, kSortWaves);
-            const size_t stage_cap = (size_t)2 * per_wave * kSortWavesPerWg;
-            const size_t staged_bytes = hist_bytes + (2 * (size_t)n + 2 + 1) * sizeof(int32_t) + stage_cap * sizeof(uint64_t);
-            if (staged_bytes <= 127 * 1024) {                  // (78 KB on pose0-syn: two workgroups per CU)
-                k_he_scatter_staged<<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, staged_bytes, st>>>(
-                    edges, grad, e, (int)n, r, counts, r2s, pairs_done ? r2 : nullptr, (int)stage_cap);
-            } else {
-                k_he_sort<true><<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, hist_bytes, st>>>(edges, grad, e, (int)n, r,
-                                                                                                      counts, r2s, pairs_done ? r2 : nullptr);
-            }
-            GN_LAUNCH_CHECK();
-            const gn_status rc = launch_seg_lds(r2s, counts, kSortWaves, tp, tk, n, z, ld_z, n, d, ld_d, r, f, part, dz, ld_dz, st, true,
-                                                both ? &cz : nullptr);
-            if (rc != GN_OK) return rc;
-        } else if (lds_dz) {
-            k_half_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(u, v, et, grad, e, n, r, k2, r2);
-            GN_LAUNCH_CHECK();
-            GN_HIP(rocprim::radix_sort_pairs(ws + ll.sort_tmp, sort2, k2, k2s, r2, r2s, (size_t)(2 * e), 0, bits_for(n + 1), st));
-            k_key_offsets<<<(int)gn::ceil_div(n + 1, 256), 256, 0, st>>>(k2s, 2 * e, (int)n, rp);
-            GN_LAUNCH_CHECK();
-            const gn_status rc = launch_seg_lds(r2s, rp, 1, tp, tk, n, z, ld_z, n, d, ld_d, r, f, part, dz, ld_dz, st, false, both ? &cz : nullptr);
-            if (rc != GN_OK) return rc;
-        }
-        if (lds_dd) {
-            const bool sorted = sorted_types;
-            if (!pairs_done) {
-                k_pair_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(u, v, et, grad, e, n, r, sorted ? nullptr : k2, r2);
-                GN_LAUNCH_CHECK();
-            }
-            const uint64_t* recs_dd = r2;
-            const int32_t* rp_dd = rp;
-            if (sorted && type_offsets) {
-                rp_dd = type_offsets;                          // the caller keeps them with its static edge_type
-            } else if (sorted) {
-                k_key_offsets64<<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(et, e, (int)r, rp);
-            } else {
-                GN_HIP(rocprim::radix_sort_pairs(ws + ll.sort_tmp, sort2, k2, k2s, r2, r2s, (size_t)e, 0, bits_for(r + 1), st));
-                k_key_offsets<<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(k2s, e, (int)r, rp);
-                recs_dd = r2s;
-            }
-            GN_LAUNCH_CHECK();
-            int32_t* tp_dd = tp;
-            int4* tk_dd = tk;
-            if (listed) {
-                const TypeTasks t = type_tasks_layout(r, e);
-                tp_dd = const_cast<int32_t*>(type_offsets) + t.taskptr;
-                tk_dd = reinterpret_cast<int4*>(const_cast<int32_t*>(type_offsets) + t.tasks);
-            }
-            gn_status rc = launch_seg_lds(recs_dd, rp_dd, 1, tp_dd, tk_dd, r, z, ld_z, n, z, ld_z, n, f, part_dd, dd, ld_dd, st, listed,
-                                          both ? &cd : nullptr);
-            if (rc == GN_OK && both) {
-                cz.add = dz_add; cz.ld_add = ld_dz_add; cd.add = dd_add; cd.ld_add = ld_dd_add;
-                rc = combine_both(cz, n, cd, r, f, st);
-            }
-            if (rc != GN_OK) return rc;
-        }
-    } else if (dz_add || dd_add) {
-        return gn::fail(GN_ERR_UNSUPPORTED, "addends ride on the common combine launch of the two LDS reductions: not taken for these shapes");
-    }
-    for (int mode = 0; mode < 3; ++mode) {
-        if (mode == 2 ? lds_dd : lds_dz) continue;       // done above
-        const int64_t rows = mode == 2 ? r : n;
-        const float* A = z;                              // a is always a node id
-        const int64_t ld_a = ld_z;
-        const float* B = mode == 2 ? z : d;              // b: relation row of D, or the other endpoint's z row
-        const int64_t ld_b = mode == 2 ? ld_z : ld_d;
-        float* out = mode == 2 ? dd : dz;
-        const int64_t ld_out = mode == 2 ? ld_dd : ld_dz;
-        const int accumulate = mode == 1;                // dz = u-side pass, then + v-side pass
-        k_make_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(mode, u, v, et, grad, e, n, r, (uint32_t)rows, keys, recs);
-        GN_LAUNCH_CHECK();
-        GN_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, sort_bytes, keys, keys_sorted, recs, recs_sorted, (size_t)e, 0,
-                                         bits_for(rows + 1), st));
-        k_key_offsets<<<(int)gn::ceil_div(rows + 1, 256), 256, 0, st>>>(keys_sorted, e, (int)rows, rowptr);
-        GN_LAUNCH_CHECK();
-        if (vec) {
-            for (int c0 = 0; c0 < f; c0 += 64) {
-                const int width = (int)std::min<int64_t>(64, f - c0);
-                if (width > 32)
-                    k_seg_reduce<16><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b,
-                                                             out, ld_out, partial, c0, width, accumulate);
-                else if (width > 16)
-                    k_seg_reduce<8><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b,
-                                                            out, ld_out, partial, c0, width, accumulate);
-                else
-                    k_seg_reduce<4><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b,
-                                                            out, ld_out, partial, c0, width, accumulate);
-                GN_LAUNCH_CHECK();
-                k_seg_combine<<<(unsigned)rows, 64, 0, st>>>(rowptr, keys_sorted, e, (int)rows, partial, out, ld_out, c0, width,
-                                                            accumulate);
-                GN_LAUNCH_CHECK();
-            }
-        } else {
-            k_seg_reduce_scalar<<<(unsigned)rows, 256, 0, st>>>(rowptr, recs_sorted, A, ld_a, B, ld_b, out, ld_out, (int)f, accumulate);
-            GN_LAUNCH_CHECK();
-        }
-    }
-    return GN_OK;
-}
-}  // namespace
-
-extern "C" gn_status gn_distmult_backward_ex_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
-                                                 const int64_t* v, const int64_t* et, const float* d, int64_t ld_d,
-                                                 int64_t r, int64_t e, const float* grad_logit, float* dz, int64_t ld_dz,
-                                                 float* dd, int64_t ld_dd, int flags, const float* sigmoid_scores,
-                                                 const int32_t* type_offsets, void* workspace, size_t workspace_bytes,
-                                                 void* stream) {
-    return backward_impl(z, ld_z, n, f, EdgeSrc{u, v, et, nullptr, nullptr}, d, ld_d, r, e, grad_logit, dz, ld_dz, dd, ld_dd, flags,
-                         sigmoid_scores, type_offsets, workspace, workspace_bytes, stream);
-}
-
-extern "C" gn_status gn_distmult_backward_packed_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const uint32_t* packed_uv,
-                                                     const uint16_t* rel16, const float* d, int64_t ld_d, int64_t r, int64_t e,
-                                                     const float* grad_logit, float* dz, int64_t ld_dz, float* dd, int64_t ld_dd,
-                                                     int flags, const float* sigmoid_scores, const int32_t* type_offsets,
-                                                     void* workspace, size_t workspace_bytes, void* stream) {
-    GN_REQUIRE(e == 0 || (packed_uv && rel16), "packed pairs or relation ids are null");
-    GN_REQUIRE(n <= 65536 && r <= 65536, "packed pairs hold ids of 16 bits");
-    return backward_impl(z, ld_z, n, f, EdgeSrc{nullptr, nullptr, nullptr, packed_uv, rel16}, d, ld_d, r, e, grad_logit, dz, ld_dz, dd,
-                         ld_dd, flags, sigmoid_scores, type_offsets, workspace, workspace_bytes, stream);
-}
-
-extern "C" gn_status gn_distmult_backward_loss_packed_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const uint32_t* packed_uv,
-                                                          const uint16_t* rel16, const float* d, int64_t ld_d, int64_t r, int64_t e,
-                                                          const gn_link_loss_grad* loss, const float* sigmoid_scores, float* dz, int64_t ld_dz,
-                                                          float* dd, int64_t ld_dd, int flags, const int32_t* type_offsets,
-                                                          const float* dz_add, int64_t ld_dz_add, const float* dd_add, int64_t ld_dd_add,
-                                                          void* workspace, size_t workspace_bytes, void* stream) {
-    GN_REQUIRE(loss != nullptr && (e == 0 || sigmoid_scores), "the loss source and the forward's probabilities are required");
-    GN_REQUIRE((!dz_add || ld_dz_add >= f) && (!dd_add || ld_dd_add >= f) && (e > 0 || (!dz_add && !dd_add)),
-               "addends: rows of at least num_features floats, and a non-empty list");
-    // a legal layout the combine launch cannot read (its 16-byte accesses): the caller adds the sums itself
-    if ((dz_add && (ld_dz_add % 4 != 0 || (reinterpret_cast<uintptr_t>(dz_add) & 15) != 0)) ||
-        (dd_add && (ld_dd_add % 4 != 0 || (reinterpret_cast<uintptr_t>(dd_add) & 15) != 0)))
-        return gn::fail(GN_ERR_UNSUPPORTED, "addends: the combine launch reads 16-byte aligned rows with ld %% 4 == 0 (call without addends and add)");
-    GN_REQUIRE(e == 0 || (packed_uv && rel16), "packed pairs or relation ids are null");
-    GN_REQUIRE(n <= 65536 && r <= 65536, "packed pairs hold ids of 16 bits");
-    return backward_impl(z, ld_z, n, f, EdgeSrc{nullptr, nullptr, nullptr, packed_uv, rel16}, d, ld_d, r, e, nullptr, dz, ld_dz, dd,
-                         ld_dd, flags, sigmoid_scores, type_offsets, workspace, workspace_bytes, stream, loss, dz_add, ld_dz_add, dd_add, ld_dd_add);
-}
-
-extern "C" gn_status gn_distmult_backward_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
-                                              const int64_t* v, const int64_t* et, const float* d, int64_t ld_d,
-                                              int64_t r, int64_t e, const float* grad_logit, float* dz, int64_t ld_dz,
-                                              float* dd, int64_t ld_dd, void* workspace, size_t workspace_bytes,
-                                              void* stream) {
-    return gn_distmult_backward_ex_f32(z, ld_z, n, f, u, v, et, d, ld_d, r, e, grad_logit, dz, ld_dz, dd, ld_dd, 0, nullptr, nullptr, workspace,
-                                       workspace_bytes, stream);
-}
-
-namespace {
-
 constexpr uint32_t kNoPair = 0xffffffffu;
 
 // g of a pair = the sum of its two triples' gradients (each with its own sigmoid factor); own == null: no pairing, triple i
@@ -1202,55 +1151,113 @@ __global__ __launch_bounds__(256) void k_place_g(const uint64_t* __restrict__ he
     }
 }
 
-__global__ void k_is_sorted64(const int64_t* __restrict__ x, int64_t n, int* __restrict__ unsorted) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i + 1 < n; i += (int64_t)gridDim.x * blockDim.x)
-        if (x[i] > x[i + 1]) *unsorted = 1;
+}  // namespace
+
+struct gn_distmult_bwd_plan {
+    int64_t e = 0, n = 0, r = 0, he_tasks_max = 0, pr_tasks_max = 0;   // e: triples after pairing (below)
+    int64_t e_list = 0;                             // triples of the caller's list
+    // Two triples with the same unordered node pair and relation (the two directions of an edge) produce the same
+    // records but for g: they are reduced as ONE triple with g1 + g2.  eu / ev / er: the triples that are left, in list
+    // order; own / mir: where their gradients sit in the caller's list (mir = kNoPair: unpaired).
+    gn::DevBuf<int64_t> eu, ev, er;
+    gn::DevBuf<uint32_t> own, mir;
+    gn::DevBuf<int32_t> offsets;                    // [n * kSortWaves + 1] where every wave's records of every node start
+    gn::DevBuf<int32_t> he_taskptr, pr_taskptr;     // [n + 1], [R + 1]
+    gn::DevBuf<int32_t> he_tasks, pr_tasks;         // int4 descriptors
+    // The half-edge records in node order and the pair records in list order with the POSITION of their triple (in eu / ev /
+    // er) where the gradient goes: what a step's gradients are placed into (k_place_g), instead of sorting every step.
+    gn::DevBuf<uint64_t> he_static, pr_static;      // [2 e + 64], [e + 64]
+};
+
+namespace {
+
+void bwd_plan_free(gn_distmult_bwd_plan* p) {
+    if (!p) return;
+    p->eu.release(); p->ev.release(); p->er.release(); p->own.release(); p->mir.release();
+    p->offsets.release(); p->he_taskptr.release(); p->pr_taskptr.release(); p->he_tasks.release(); p->pr_tasks.release();
+    p->he_static.release(); p->pr_static.release();
+    delete p;
 }
 
-struct TmpBufs {
-    std::vector<void*> ptrs;
-    ~TmpBufs() { for (void* q : ptrs) (void)hipFree(q); }
-    template <typename T>
-    hipError_t get(T** out, size_t count) {
-        void* q = nullptr;
-        hipError_t err = hipMalloc(&q, (count ? count : 1) * sizeof(T));
-        if (err == hipSuccess) ptrs.push_back(q);
-        *out = static_cast<T*>(q);
-        return err;
+struct PlanWs { size_t g, he, pr, partial, total; };
+PlanWs plan_ws(const gn_distmult_bwd_plan* p, int64_t f) {
+    PlanWs w;
+    w.g = 0;
+    w.he = w.g + align_up((size_t)(p->e + 64) * sizeof(float));
+    w.pr = w.he + align_up((size_t)(2 * p->e + 64) * sizeof(uint64_t));
+    w.partial = w.pr + align_up((size_t)(2 * p->e + 64) * sizeof(uint64_t));
+    w.total = w.partial + align_up((size_t)(p->he_tasks_max + p->pr_tasks_max) * f * sizeof(float));   // both reductions' partial sums (one combine launch)
+    return w;
+}
+
+gn_status backward_planned_impl(const gn_distmult_bwd_plan* plan, const float* z, int64_t ld_z, int64_t f,
+                                const float* d, int64_t ld_d, const float* grad_logit,
+                                const float* sigmoid_scores, float* dz, int64_t ld_dz, float* dd,
+                                int64_t ld_dd, void* workspace, size_t workspace_bytes, void* stream, const gn_link_loss_grad* loss) {
+    GN_REQUIRE(plan != nullptr, "plan is null");
+    GN_REQUIRE(f >= 0 && f < (1ll << 31), "bad feature count");
+    GN_REQUIRE(f == 0 || (dz && dd && ld_dz >= f && ld_dd >= f), "gradient output pointer is null or its leading dimension too small");
+    hipStream_t st = gn::as_stream(stream);
+    const int64_t n = plan->n, r = plan->r, e = plan->e;
+    if (f == 0) return GN_OK;
+    if (e == 0) return zero_gradients(dz, ld_dz, n, dd, ld_dd, r, f, st);
+    GN_REQUIRE(z && d && (loss || grad_logit) && ld_z >= f && ld_d >= f, "operand pointer is null or a leading dimension too small");
+    if (!float4_rows(f, z, ld_z, d, ld_d, dz, ld_dz, dd, ld_dd))
+        return gn::fail(GN_ERR_UNSUPPORTED, "rows are not 16-byte aligned float4 columns: use gn_distmult_backward_f32");
+    const PlanWs w = plan_ws(plan, f);
+    GN_REQUIRE(workspace && workspace_bytes >= w.total, "workspace too small: need %zu bytes", w.total);
+    char* ws = static_cast<char*>(workspace);
+    uint64_t* he = reinterpret_cast<uint64_t*>(ws + w.he);
+    uint64_t* pr = reinterpret_cast<uint64_t*>(ws + w.pr);
+    float* part = reinterpret_cast<float*>(ws + w.partial);
+    float* gpair = reinterpret_cast<float*>(ws + w.g);
+    k_pair_grad<<<gn::stream_grid(e, 256), 256, 0, st>>>(plan->own.p, plan->mir.p, e, make_grad_src(grad_logit, sigmoid_scores, loss, plan->e_list), gpair, plan->pr_static.p, pr);
+    GN_LAUNCH_CHECK();
+    k_place_g<<<(unsigned)std::min<int64_t>(gn::ceil_div(2 * e, 4 * 256), 4096), 256, 0, st>>>(plan->he_static.p, 2 * e, gpair, he);
+    GN_LAUNCH_CHECK();
+    CombineSet cz, cd;
+    gn_status rc = launch_seg_lds(he, nullptr, 0, plan->he_taskptr.p, reinterpret_cast<int4*>(plan->he_tasks.p), n, z, ld_z, n, d, ld_d, r, f,
+                                  part, dz, ld_dz, st, true, &cz);
+    if (rc != GN_OK) return rc;
+    rc = launch_seg_lds(pr, nullptr, 0, plan->pr_taskptr.p, reinterpret_cast<int4*>(plan->pr_tasks.p), r, z, ld_z, n, z, ld_z, n, f,
+                        part + (size_t)plan->he_tasks_max * f, dd, ld_dd, st, true, &cd);
+    if (rc != GN_OK) return rc;
+    return combine_both(cz, n, cd, r, f, st);
+}
+
+// The full 64-record batches of [begin, end) - records of one key that one wave task reads - in the bank-balanced order
+// (host_layout.hpp): the four rows of an LDS lane group get four different indices mod 4, for both factor tables, where the batch
+// allows it.  class_of(i): element i's two indices mod 4 as a | b << 2; move(b0, order): element b0 + i comes from b0 + order[i].
+template <typename ClassOf, typename Move>
+void balance_batches(int64_t begin, int64_t end, ClassOf class_of, Move move) {
+    for (int64_t b0 = begin; b0 + 64 <= end; b0 += 64) {
+        uint8_t cls[64];
+        int order[64];
+        for (int i = 0; i < 64; ++i) cls[i] = class_of(b0 + i);
+        gn_layout::balance_batch64(cls, order);
+        move(b0, order);
     }
-};
+}
+
+template <typename T>
+void take_in_order(T* batch, const int* order) {
+    T tmp[64];
+    for (int i = 0; i < 64; ++i) tmp[i] = batch[order[i]];
+    std::copy(tmp, tmp + 64, batch);
+}
 
 // The records of the plan's triples, sorted once: the counting sort's scatter pass with the triple's position in place of
 // its gradient (GradSrc index mode).  A step then only places its gradients (k_pair_grad, k_place_g).
-gn_status place_static_records(gn_distmult_bwd_plan* p, const int64_t* u, const int64_t* v, const int64_t* et, TmpBufs& tmp, hipStream_t st) {
-    const int64_t E = p->e, n = p->n, R = p->r;
-    GN_HIP(p->he_static.alloc((size_t)(2 * E + 64)));
-    GN_HIP(p->pr_static.alloc((size_t)(2 * E + 64)));          // (the scatter's spare slots sit at 2 E)
+gn_status place_static_records(gn_distmult_bwd_plan* p, gn::Scratch& tmp, hipStream_t st) {
+    GN_HIP(p->he_static.alloc((size_t)(2 * p->e + 64)));
+    GN_HIP(p->pr_static.alloc((size_t)(2 * p->e + 64)));          // (the scatter's spare slots sit at 2 E)
     const GradSrc index = {nullptr, nullptr};
-    const size_t hist_bytes = (size_t)kSortWavesPerWg * n * sizeof(int32_t);
-    const int64_t per_wave = gn::ceil_div(E, kSortWaves);
-    const size_t stage_cap = (size_t)2 * per_wave * kSortWavesPerWg;
-    const size_t staged_bytes = hist_bytes + (2 * (size_t)n + 2 + 1) * sizeof(int32_t) + stage_cap * sizeof(uint64_t);
-    if (staged_bytes <= 127 * 1024) {
-        { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_he_scatter_staged), 128 * 1024); if (lds_status != GN_OK) return lds_status; }
-        k_he_scatter_staged<<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, staged_bytes, st>>>(EdgeSrc{u, v, et, nullptr, nullptr}, index, E, (int)n, R, p->offsets.p,
-                                                                                                  p->he_static.p, p->pr_static.p, (int)stage_cap);
-    } else {
-        // the unstaged pass advances its offsets in place: it works on a copy
-        const size_t cells = (size_t)n * kSortWaves + 1;
-        int32_t* copy;
-        GN_HIP(tmp.get(&copy, cells));
-        GN_HIP(hipMemcpyAsync(copy, p->offsets.p, cells * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_he_sort<true>), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
-        k_he_sort<true><<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, hist_bytes, st>>>(EdgeSrc{u, v, et, nullptr, nullptr}, index, E, (int)n, R, copy, p->he_static.p,
-                                                                                              p->pr_static.p);
-    }
-    GN_LAUNCH_CHECK();
-    return GN_OK;
+    return launch_he_scatter(EdgeSrc{p->eu.p, p->ev.p, p->er.p, nullptr, nullptr}, index, p->e, p->n, p->r, p->offsets.p, p->he_static.p,
+                             p->pr_static.p, &tmp, st);
 }
 
-// The node-major records of a static list, batch by batch of their tasks, in the bank-balanced order (host_layout.hpp): the
-// partner's row of z and the relation's row of D have four different indices mod 4 in every lane group where the batch allows it.
+// The node-major records of a static list, batch by batch of their tasks, in the bank-balanced order: the partner's row of z
+// and the relation's row of D.
 gn_status balance_static_records(gn_distmult_bwd_plan* p, hipStream_t st) {
     const int64_t n_rec = 2 * p->e;
     int32_t n_tasks = 0;
@@ -1262,73 +1269,43 @@ gn_status balance_static_records(gn_distmult_bwd_plan* p, hipStream_t st) {
     GN_HIP(hipMemcpyAsync(recs.data(), p->he_static.p, recs.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     GN_HIP(hipMemcpyAsync(tasks.data(), p->he_tasks.p, tasks.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
-    uint64_t tmp[64];
     for (int32_t t = 0; t < n_tasks; ++t) {
         const int64_t begin = tasks[(size_t)t * 4 + 1], end = tasks[(size_t)t * 4 + 2];
         if (begin < 0 || end > n_rec) return gn::fail(GN_ERR_INVALID_ARG, "task %d of the decoder gradient plan lies outside its records", (int)t);
-        for (int64_t b0 = begin; b0 + 64 <= end; b0 += 64) {
-            uint8_t cls[64];
-            int order[64];
-            for (int i = 0; i < 64; ++i) {
-                const uint32_t w = (uint32_t)recs[(size_t)(b0 + i)];
-                cls[i] = (uint8_t)((w & 3u) | (((w >> 16) & 3u) << 2));
-            }
-            gn_layout::balance_batch64(cls, order);
-            for (int i = 0; i < 64; ++i) tmp[i] = recs[(size_t)(b0 + order[i])];
-            for (int i = 0; i < 64; ++i) recs[(size_t)(b0 + i)] = tmp[i];
-        }
+        balance_batches(begin, end,
+                        [&](int64_t i) { const uint32_t w = (uint32_t)recs[(size_t)i]; return (uint8_t)((w & 3u) | (((w >> 16) & 3u) << 2)); },
+                        [&](int64_t b0, const int* order) { take_in_order(&recs[(size_t)b0], order); });
     }
     GN_HIP(hipMemcpyAsync(p->he_static.p, recs.data(), recs.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     GN_HIP(hipStreamSynchronize(st));
     return GN_OK;
 }
 
-gn_status build_bwd_plan(gn_distmult_bwd_plan* p, const int64_t* u, const int64_t* v, const int64_t* et, hipStream_t st) {
+// The device half of a plan, from the uploaded triples (in range and sorted by relation: gn_distmult_bwd_plan_create has looked):
+// the counting sort's offsets and the node-major task list exactly as a plan-less call derives them, the relation-major task
+// list, the static records.
+gn_status build_bwd_plan(gn_distmult_bwd_plan* p, hipStream_t st) {
     const int64_t E = p->e, n = p->n, R = p->r;
-    TmpBufs tmp;
-    int32_t* rp;
-    int* unsorted;
-    const size_t cells = (size_t)n * kSortWaves + 1;
-    size_t scan_bytes = 0;
-    (void)rocprim::exclusive_scan(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, 0, cells, rocprim::plus<int32_t>(), (hipStream_t)0);
-    char* scratch;
+    gn::Scratch tmp;
+    int32_t *totals, *rp;
+    GN_HIP(tmp.get(&totals, (size_t)n));
     GN_HIP(tmp.get(&rp, (size_t)R + 2));
-    GN_HIP(tmp.get(&unsorted, 1));
-    GN_HIP(tmp.get(&scratch, scan_bytes));
-    GN_HIP(hipMemsetAsync(unsorted, 0, sizeof(int), st));
-    k_is_sorted64<<<gn::stream_grid(E, 256), 256, 0, st>>>(et, E, unsorted);
-    GN_LAUNCH_CHECK();
-    { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_he_sort<false>), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
-    GN_HIP(p->offsets.alloc(cells));
-    const GradSrc none = {nullptr, nullptr};
-    const size_t hist_bytes = (size_t)kSortWavesPerWg * n * sizeof(int32_t);
-    k_he_sort<false><<<kSortWaves / kSortWavesPerWg, kSortWavesPerWg * 64, hist_bytes, st>>>(EdgeSrc{u, v, et, nullptr, nullptr}, none, E, (int)n, R, p->offsets.p, nullptr,
-                                                                                           nullptr);
-    GN_LAUNCH_CHECK();
-    GN_HIP(rocprim::exclusive_scan(scratch, scan_bytes, p->offsets.p, p->offsets.p, 0, cells, rocprim::plus<int32_t>(), st));
-    int32_t placed = 0;
-    int is_unsorted = 0;
-    GN_HIP(hipMemcpyAsync(&placed, p->offsets.p + cells - 1, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GN_HIP(hipMemcpyAsync(&is_unsorted, unsorted, sizeof(int), hipMemcpyDeviceToHost, st));
-    GN_HIP(hipStreamSynchronize(st));
-    if ((int64_t)placed != 2 * E)
-        return gn::fail(GN_ERR_INDEX_RANGE, "%lld of the %lld edges have a node or relation id outside its table",
-                        (long long)(E - placed / 2), (long long)E);
-    if (is_unsorted)
-        return gn::fail(GN_ERR_UNSUPPORTED, "edge_type is not sorted: the dD records need a sort per call (gn_distmult_backward_f32)");
     p->he_tasks_max = lds_max_tasks(2 * E, n);
     p->pr_tasks_max = lds_max_tasks(E, R);
+    GN_HIP(p->offsets.alloc((size_t)n * kSortWaves + 1));
     GN_HIP(p->he_taskptr.alloc((size_t)n + 2));
     GN_HIP(p->pr_taskptr.alloc((size_t)R + 2));
     GN_HIP(p->he_tasks.alloc((size_t)p->he_tasks_max * 4));
     GN_HIP(p->pr_tasks.alloc((size_t)p->pr_tasks_max * 4));
-    k_task_ptr<<<1, 1024, 0, st>>>(p->offsets.p, (int64_t)kSortWaves, (int)n, p->he_taskptr.p, reinterpret_cast<int4*>(p->he_tasks.p));
-    GN_LAUNCH_CHECK();
-    k_key_offsets64<<<(int)gn::ceil_div(R + 1, 256), 256, 0, st>>>(et, E, (int)R, rp);
+    const GradSrc none = {nullptr, nullptr};
+    gn_status rc = count_half_edges(EdgeSrc{p->eu.p, p->ev.p, p->er.p, nullptr, nullptr}, none, E, n, R, p->offsets.p, totals, p->he_taskptr.p,
+                                    reinterpret_cast<int4*>(p->he_tasks.p), st);
+    if (rc != GN_OK) return rc;
+    k_key_offsets64<<<(int)gn::ceil_div(R + 1, 256), 256, 0, st>>>(p->er.p, E, (int)R, rp);
     GN_LAUNCH_CHECK();
     k_task_ptr<<<1, 1024, 0, st>>>(rp, 1, (int)R, p->pr_taskptr.p, reinterpret_cast<int4*>(p->pr_tasks.p));
     GN_LAUNCH_CHECK();
-    const gn_status rc = place_static_records(p, u, v, et, tmp, st);
+    rc = place_static_records(p, tmp, st);
     if (rc != GN_OK) return rc;
     GN_HIP(hipStreamSynchronize(st));       // scratch goes out of scope
     return GN_OK;
@@ -1336,14 +1313,85 @@ gn_status build_bwd_plan(gn_distmult_bwd_plan* p, const int64_t* u, const int64_
 
 }  // namespace
 
+extern "C" size_t gn_distmult_type_tasks_bytes(int64_t r, int64_t e) {
+    if (r <= 0 || e < 0) return 0;
+    return type_tasks_layout(r, e).total * sizeof(int32_t);
+}
+
+extern "C" gn_status gn_distmult_type_tasks(const int32_t* type_offsets, int64_t r, int64_t e, void* out, size_t out_bytes, void* stream) {
+    GN_REQUIRE(type_offsets && out && r > 0 && e >= 0, "null pointer or bad size");
+    GN_REQUIRE(r < (1ll << 31) && e < (1ll << 31), "too large");
+    GN_REQUIRE(gn::aligned16(out), "the buffer is not 16-byte aligned");
+    const TypeTasks t = type_tasks_layout(r, e);
+    GN_REQUIRE(out_bytes >= t.total * sizeof(int32_t), "buffer too small: need %zu bytes", t.total * sizeof(int32_t));
+    hipStream_t st = gn::as_stream(stream);
+    int32_t* o = static_cast<int32_t*>(out);
+    if (o != type_offsets) GN_HIP(hipMemcpyAsync(o, type_offsets, (size_t)(r + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    k_task_ptr<<<1, 1024, 0, st>>>(o, 1, (int)r, o + t.taskptr, reinterpret_cast<int4*>(o + t.tasks));
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+extern "C" size_t gn_distmult_backward_workspace_bytes(int64_t n, int64_t f, int64_t r, int64_t e) {
+    if (n <= 0 || f <= 0 || r <= 0 || e <= 0) return 0;
+    return std::max(ws_layout(e, std::max(n, r)).total, lds_layout(e, n, r, f).total);
+}
+
+extern "C" gn_status gn_distmult_backward_ex_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
+                                                 const int64_t* v, const int64_t* et, const float* d, int64_t ld_d,
+                                                 int64_t r, int64_t e, const float* grad_logit, float* dz, int64_t ld_dz,
+                                                 float* dd, int64_t ld_dd, int flags, const float* sigmoid_scores,
+                                                 const int32_t* type_offsets, void* workspace, size_t workspace_bytes,
+                                                 void* stream) {
+    return backward_impl(z, ld_z, n, f, EdgeSrc{u, v, et, nullptr, nullptr}, d, ld_d, r, e, grad_logit, dz, ld_dz, dd, ld_dd, flags,
+                         sigmoid_scores, type_offsets, workspace, workspace_bytes, stream);
+}
+
+extern "C" gn_status gn_distmult_backward_packed_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const uint32_t* packed_uv,
+                                                     const uint16_t* rel16, const float* d, int64_t ld_d, int64_t r, int64_t e,
+                                                     const float* grad_logit, float* dz, int64_t ld_dz, float* dd, int64_t ld_dd,
+                                                     int flags, const float* sigmoid_scores, const int32_t* type_offsets,
+                                                     void* workspace, size_t workspace_bytes, void* stream) {
+    GN_REQUIRE(e == 0 || (packed_uv && rel16), "packed pairs or relation ids are null");
+    GN_REQUIRE(n <= 65536 && r <= 65536, "packed pairs hold ids of 16 bits");
+    return backward_impl(z, ld_z, n, f, EdgeSrc{nullptr, nullptr, nullptr, packed_uv, rel16}, d, ld_d, r, e, grad_logit, dz, ld_dz, dd,
+                         ld_dd, flags, sigmoid_scores, type_offsets, workspace, workspace_bytes, stream);
+}
+
+extern "C" gn_status gn_distmult_backward_loss_packed_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const uint32_t* packed_uv,
+                                                          const uint16_t* rel16, const float* d, int64_t ld_d, int64_t r, int64_t e,
+                                                          const gn_link_loss_grad* loss, const float* sigmoid_scores, float* dz, int64_t ld_dz,
+                                                          float* dd, int64_t ld_dd, int flags, const int32_t* type_offsets,
+                                                          const float* dz_add, int64_t ld_dz_add, const float* dd_add, int64_t ld_dd_add,
+                                                          void* workspace, size_t workspace_bytes, void* stream) {
+    GN_REQUIRE(loss != nullptr && (e == 0 || sigmoid_scores), "the loss source and the forward's probabilities are required");
+    GN_REQUIRE((!dz_add || ld_dz_add >= f) && (!dd_add || ld_dd_add >= f) && (e > 0 || (!dz_add && !dd_add)),
+               "addends: rows of at least num_features floats, and a non-empty list");
+    // a legal layout the combine launch cannot read (its 16-byte accesses): the caller adds the sums itself
+    if ((dz_add && (ld_dz_add % 4 != 0 || !gn::aligned16(dz_add))) || (dd_add && (ld_dd_add % 4 != 0 || !gn::aligned16(dd_add))))
+        return gn::fail(GN_ERR_UNSUPPORTED, "addends: the combine launch reads 16-byte aligned rows with ld %% 4 == 0 (call without addends and add)");
+    GN_REQUIRE(e == 0 || (packed_uv && rel16), "packed pairs or relation ids are null");
+    GN_REQUIRE(n <= 65536 && r <= 65536, "packed pairs hold ids of 16 bits");
+    return backward_impl(z, ld_z, n, f, EdgeSrc{nullptr, nullptr, nullptr, packed_uv, rel16}, d, ld_d, r, e, nullptr, dz, ld_dz, dd,
+                         ld_dd, flags, sigmoid_scores, type_offsets, workspace, workspace_bytes, stream, loss, dz_add, ld_dz_add, dd_add, ld_dd_add);
+}
+
+extern "C" gn_status gn_distmult_backward_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
+                                              const int64_t* v, const int64_t* et, const float* d, int64_t ld_d,
+                                              int64_t r, int64_t e, const float* grad_logit, float* dz, int64_t ld_dz,
+                                              float* dd, int64_t ld_dd, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+    return gn_distmult_backward_ex_f32(z, ld_z, n, f, u, v, et, d, ld_d, r, e, grad_logit, dz, ld_dz, dd, ld_dd, 0, nullptr, nullptr, workspace,
+                                       workspace_bytes, stream);
+}
+
 extern "C" gn_status gn_distmult_bwd_plan_create(const int64_t* u, const int64_t* v, const int64_t* edge_type, int64_t num_edges,
                                                  int64_t num_nodes, int64_t num_relations, void* stream, gn_distmult_bwd_plan** out) {
     GN_REQUIRE(out != nullptr, "plan output pointer is null");
     *out = nullptr;
     GN_REQUIRE(num_edges >= 0 && num_nodes >= 0 && num_relations >= 0, "negative size");
     GN_REQUIRE(num_edges == 0 || (u && v && edge_type), "edge pointers are null");
-    if (gn::fast_paths_disabled() || num_nodes < 1 || num_relations < 1 || num_nodes > kSortMaxKeys || num_relations > 65535 ||
-        !lds_dz_fits(num_nodes, num_relations) || 2 * num_edges + 64 >= (1ll << 31))
+    if (num_nodes < 1 || num_relations < 1 || !route_of_shapes(num_nodes, num_relations, num_edges).counting_dz)
         return gn::fail(GN_ERR_UNSUPPORTED, "node and relation tables do not fit the LDS path (or it is disabled): use gn_distmult_backward_f32");
     hipStream_t st = gn::as_stream(stream);
     const int64_t E = num_edges;
@@ -1355,6 +1403,8 @@ extern "C" gn_status gn_distmult_bwd_plan_create(const int64_t* u, const int64_t
         GN_HIP(hipMemcpyAsync(hr.data(), edge_type, E * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         GN_HIP(hipStreamSynchronize(st));
     }
+    // every id in range, relation ids in order: the device passes behind this loop rely on both and do not look again (the
+    // pairing keeps list order, the balancing permutes inside one relation)
     for (int64_t e = 0; e < E; ++e) {
         if ((uint64_t)hu[e] >= (uint64_t)num_nodes || (uint64_t)hv[e] >= (uint64_t)num_nodes || (uint64_t)hr[e] >= (uint64_t)num_relations)
             return gn::fail(GN_ERR_INDEX_RANGE, "edge %lld = (%lld, %lld, type %lld) is outside [0,%lld) x [0,%lld) x [0,%lld)",
@@ -1382,36 +1432,21 @@ extern "C" gn_status gn_distmult_bwd_plan_create(const int64_t* u, const int64_t
             }
         }
     }
-    // The pairs of a relation may stand in any order: inside every full 64-record batch of the relation-major reduction's tasks
-    // they are placed so that the four rows of an LDS lane group have four different indices mod 4, for u and for v (host_layout.hpp)
-    {
-        const int64_t P = (int64_t)eu.size();
-        std::vector<int64_t> tu(64), tv(64);
-        std::vector<uint32_t> to(64), tm(64);
-        for (int64_t s0 = 0; s0 < P;) {
-            int64_t s1 = s0;
-            while (s1 < P && er[(size_t)s1] == er[(size_t)s0]) ++s1;
-            for (int64_t t0 = s0; t0 < s1; t0 += kTaskRecs)
-                for (int64_t b0 = t0; b0 + 64 <= std::min(s1, t0 + kTaskRecs); b0 += 64) {
-                    uint8_t cls[64];
-                    int order[64];
-                    for (int i = 0; i < 64; ++i) cls[i] = (uint8_t)((eu[(size_t)(b0 + i)] & 3) | ((ev[(size_t)(b0 + i)] & 3) << 2));
-                    gn_layout::balance_batch64(cls, order);
-                    for (int i = 0; i < 64; ++i) {
-                        const size_t from = (size_t)(b0 + order[i]);
-                        tu[i] = eu[from]; tv[i] = ev[from]; to[i] = own[from]; tm[i] = mir[from];
-                    }
-                    for (int i = 0; i < 64; ++i) {
-                        const size_t at = (size_t)(b0 + i);
-                        eu[at] = tu[i]; ev[at] = tv[i]; own[at] = to[i]; mir[at] = tm[i];
-                    }
-                }
-            s0 = s1;
-        }
+    // The pairs of a relation may stand in any order: the batches of the relation-major reduction's tasks are balanced for u and for v
+    const int64_t P = (int64_t)eu.size();
+    for (int64_t s0 = 0, s1; s0 < P; s0 = s1) {
+        for (s1 = s0; s1 < P && er[(size_t)s1] == er[(size_t)s0];) ++s1;
+        for (int64_t t0 = s0; t0 < s1; t0 += kTaskRecs)
+            balance_batches(t0, std::min(s1, t0 + kTaskRecs),
+                            [&](int64_t i) { return (uint8_t)((eu[(size_t)i] & 3) | ((ev[(size_t)i] & 3) << 2)); },
+                            [&](int64_t b0, const int* order) {
+                                take_in_order(&eu[(size_t)b0], order); take_in_order(&ev[(size_t)b0], order);
+                                take_in_order(&own[(size_t)b0], order); take_in_order(&mir[(size_t)b0], order);
+                            });
     }
     gn_distmult_bwd_plan* p = new (std::nothrow) gn_distmult_bwd_plan();
     GN_REQUIRE(p != nullptr, "out of host memory");
-    p->e_list = E; p->e = (int64_t)eu.size(); p->n = num_nodes; p->r = num_relations;
+    p->e_list = E; p->e = P; p->n = num_nodes; p->r = num_relations;
     if (p->e > 0) {
         auto up = [&](auto& buf, const auto& host) -> hipError_t {
             hipError_t err = buf.alloc(host.size());
@@ -1425,7 +1460,7 @@ extern "C" gn_status gn_distmult_bwd_plan_create(const int64_t* u, const int64_t
             bwd_plan_free(p);
             return gn::fail(GN_ERR_HIP, "decoder gradient plan upload failed: %s", hipGetErrorString(err));
         }
-        gn_status rc = build_bwd_plan(p, p->eu.p, p->ev.p, p->er.p, st);
+        gn_status rc = build_bwd_plan(p, st);
         if (rc == GN_OK) rc = balance_static_records(p, st);
         if (rc != GN_OK) { bwd_plan_free(p); return rc; }
     }
@@ -1440,11 +1475,6 @@ extern "C" size_t gn_distmult_bwd_plan_workspace_bytes(const gn_distmult_bwd_pla
     return plan_ws(plan, num_features).total;
 }
 
-static gn_status backward_planned_impl(const gn_distmult_bwd_plan* plan, const float* z, int64_t ld_z, int64_t f,
-                                       const float* d, int64_t ld_d, const float* grad_logit,
-                                       const float* sigmoid_scores, float* dz, int64_t ld_dz, float* dd,
-                                       int64_t ld_dd, void* workspace, size_t workspace_bytes, void* stream, const gn_link_loss_grad* loss);
-
 extern "C" gn_status gn_distmult_backward_planned_f32(const gn_distmult_bwd_plan* plan, const float* z, int64_t ld_z, int64_t f,
                                                       const float* d, int64_t ld_d, const float* grad_logit,
                                                       const float* sigmoid_scores, float* dz, int64_t ld_dz, float* dd,
@@ -1458,44 +1488,4 @@ extern "C" gn_status gn_distmult_backward_loss_planned_f32(const gn_distmult_bwd
                                                            int64_t ld_dd, void* workspace, size_t workspace_bytes, void* stream) {
     GN_REQUIRE(loss != nullptr && sigmoid_scores != nullptr, "the loss source and the forward's probabilities are required");
     return backward_planned_impl(plan, z, ld_z, f, d, ld_d, nullptr, sigmoid_scores, dz, ld_dz, dd, ld_dd, workspace, workspace_bytes, stream, loss);
-}
-
-static gn_status backward_planned_impl(const gn_distmult_bwd_plan* plan, const float* z, int64_t ld_z, int64_t f,
-                                       const float* d, int64_t ld_d, const float* grad_logit,
-                                       const float* sigmoid_scores, float* dz, int64_t ld_dz, float* dd,
-                                       int64_t ld_dd, void* workspace, size_t workspace_bytes, void* stream, const gn_link_loss_grad* loss) {
-    GN_REQUIRE(plan != nullptr, "plan is null");
-    GN_REQUIRE(f >= 0 && f < (1ll << 31), "bad feature count");
-    GN_REQUIRE(f == 0 || (dz && dd && ld_dz >= f && ld_dd >= f), "gradient output pointer is null or its leading dimension too small");
-    hipStream_t st = gn::as_stream(stream);
-    const int64_t n = plan->n, r = plan->r, e = plan->e;
-    if (f == 0) return GN_OK;
-    if (e == 0) {
-        GN_HIP(hipMemset2DAsync(dz, ld_dz * sizeof(float), 0, f * sizeof(float), n, st));
-        GN_HIP(hipMemset2DAsync(dd, ld_dd * sizeof(float), 0, f * sizeof(float), r, st));
-        return GN_OK;
-    }
-    GN_REQUIRE(z && d && (loss || grad_logit) && ld_z >= f && ld_d >= f, "operand pointer is null or a leading dimension too small");
-    if (f % 4 != 0 || ld_z % 4 != 0 || ld_d % 4 != 0 || ld_dz % 4 != 0 || ld_dd % 4 != 0 ||
-        ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(dd)) & 15) != 0)
-        return gn::fail(GN_ERR_UNSUPPORTED, "rows are not 16-byte aligned float4 columns: use gn_distmult_backward_f32");
-    const PlanWs w = plan_ws(plan, f);
-    GN_REQUIRE(workspace && workspace_bytes >= w.total, "workspace too small: need %zu bytes", w.total);
-    char* ws = static_cast<char*>(workspace);
-    uint64_t* he = reinterpret_cast<uint64_t*>(ws + w.he);
-    uint64_t* pr = reinterpret_cast<uint64_t*>(ws + w.pr);
-    float* part = reinterpret_cast<float*>(ws + w.partial);
-    float* gpair = reinterpret_cast<float*>(ws + w.g);
-    k_pair_grad<<<gn::stream_grid(e, 256), 256, 0, st>>>(plan->own.p, plan->mir.p, e, make_grad_src(grad_logit, sigmoid_scores, loss, plan->e_list), gpair, plan->pr_static.p, pr);
-    GN_LAUNCH_CHECK();
-    k_place_g<<<(unsigned)std::min<int64_t>(gn::ceil_div(2 * e, 4 * 256), 4096), 256, 0, st>>>(plan->he_static.p, 2 * e, gpair, he);
-    GN_LAUNCH_CHECK();
-    CombineSet cz, cd;
-    gn_status rc = launch_seg_lds(he, nullptr, 0, plan->he_taskptr.p, reinterpret_cast<int4*>(plan->he_tasks.p), n, z, ld_z, n, d, ld_d, r, f,
-                                  part, dz, ld_dz, st, true, &cz);
-    if (rc != GN_OK) return rc;
-    rc = launch_seg_lds(pr, nullptr, 0, plan->pr_taskptr.p, reinterpret_cast<int4*>(plan->pr_tasks.p), r, z, ld_z, n, z, ld_z, n, f,
-                        part + (size_t)plan->he_tasks_max * f, dd, ld_dd, st, true, &cd);
-    if (rc != GN_OK) return rc;
-    return combine_both(cz, n, cd, r, f, st);
 }
