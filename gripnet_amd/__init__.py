@@ -7,7 +7,7 @@ The arithmetic runs in hand-written HIP kernels for gfx950 behind a C ABI
 (include/gripnet_hip.h, gripnet_amd/lib/libgripnet_hip.so); importing the package does not
 need a GPU, running a layer does.
 """
-from .layers import myGCN, myRGCN, homoGraph, interGraph
+from .layers import myGCN, myRGCN, homoGraph, interGraph, gene_stack_to_external, gene_stack_path
 from .decoder import multiRelaInnerProductDecoder, multiClassInnerProductDecoder
 from . import utils, synth, optim
 

@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 159                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 160                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -54,6 +54,10 @@ SIGNATURES = {
     "gn_graph_plan_build_blocked": (_int, [_p, _i64, _p]),
     "gn_graph_plan_blocked_cols": (_i64, [_p]),
     "gn_graph_blocked_applicable": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _i64]),
+    "gn_graph_chain_applicable": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "gn_graph_aggregate_chain_f32": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _p, _p]),
+    "gn_graph_gather_chained_f32": (_int, [_p, _p, _i64, _p]),
+    "gn_graph_aggregate_tail_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _p, _p, _p, _p, _int, _p]),
     "gn_graph_plan_build_transpose": (_int, [_p, _p]),
     "gn_graph_aggregate_t_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p]),
     "gn_xtg_wide_supported": (_int, [_i64, _i64, _i64]),
@@ -370,7 +374,8 @@ def replay(calls):
 
 # Test hooks the library reads from the environment at call time (common.h, aggregate.cuh, gcn_blocked.hip): part of every
 # memo key, so that a shortcut recorded under one setting is not replayed under another.
-_ENV_HOOKS = ("GN_DISABLE_FAST", "GN_DISABLE_QUAD", "GN_DISABLE_BLOCKED", "GN_BLOCKED_ANY", "GN_DISABLE_LDS_TABLE")
+_ENV_HOOKS = ("GN_DISABLE_FAST", "GN_DISABLE_QUAD", "GN_DISABLE_BLOCKED", "GN_BLOCKED_ANY", "GN_DISABLE_LDS_TABLE",
+              "GN_ENABLE_CHAIN")
 # hooks the C side reads that can NOT change what a memoised inference forward launches: the host threads of the plan builders
 # (plans do not depend on them), the sampler's kernel choice (same draws; no module forward calls the sampler) and the slab size of the
 # general relational path (read inside the entry point at every call: a slab is a range of rows, the bits do not depend on it).
@@ -782,18 +787,43 @@ class GraphPlan(Handle):
     def __iter__(self):          # lets `edge_index, norm = conv.cached_result` keep working
         return iter(self.export())
 
-    def aggregate(self, xw: torch.Tensor, bias, relu: bool, out: torch.Tensor, side=None, weight=None, planes=None):
+    def aggregate(self, xw: torch.Tensor, bias, relu: bool, out: torch.Tensor, side=None, weight=None, planes=None, tail=None):
         """out = act(A_norm xw + b), or with `weight` act((A_norm xw) weight + b) (xw is then the layer input).
         `planes` = (SplitPlanes, col_main, col_side): the launch also leaves the bf16 split planes of its output and of
-        its side copy."""
+        its side copy.  `tail` = (W2 [16, 16], b2): every gathered row's last 16 columns enter the sum as
+        relu(row[-16:] W2 + b2) (gn_graph_aggregate_tail_f32: 64 -> 16 features only, raises Unsupported otherwise)."""
         sc = side_copy(side)
         pd = None
         if planes is not None:
             pd = planes[0].desc(planes[1], planes[2])
             planes[0].generation += 1
+        if tail is not None:
+            _call("gn_graph_aggregate_tail_f32", self._h, ptr(xw), ld(xw), xw.shape[1], ptr(weight), weight.shape[1], ptr(bias),
+                  int(bool(relu)), ptr(out), ld(out), _ref(sc), _ref(pd), ptr(tail[0]), ptr(tail[1]), 1, stream_ptr(xw.device),
+                  tag="gn_graph_aggregate_tail_f32[{}]".format(self.kind))
+            return out
         _call("gn_graph_aggregate_f32", self._h, ptr(xw), ld(xw), xw.shape[1], ptr(weight),
               0 if weight is None else weight.shape[1], ptr(bias), int(bool(relu)),
               ptr(out), ld(out), _ref(sc), _ref(pd), stream_ptr(xw.device), tag="gn_graph_aggregate_f32[{}]".format(self.kind))
+        return out
+
+    def chain_ok(self, nxt: "GraphPlan", x: torch.Tensor, weight: torch.Tensor, bias, out: torch.Tensor, out_next: torch.Tensor) -> bool:
+        """True when `aggregate_chain` / `nxt.gather_chained` can run this layer and the 16 -> 16 layer behind it (the
+        library's own answer: plans, widths, alignment, environment switches)."""
+        return bool(load().gn_graph_chain_applicable(self._h, nxt._h, x.data_ptr(), ld(x), x.shape[1], weight.data_ptr(),
+                                                     weight.shape[1], None if bias is None else bias.data_ptr(),
+                                                     out.data_ptr(), ld(out), out_next.data_ptr()))
+
+    def aggregate_chain(self, nxt: "GraphPlan", x: torch.Tensor, weight: torch.Tensor, bias, relu: bool, out: torch.Tensor, side=None):
+        """`aggregate(x, weight=weight)` on the LDS-staged kernels whose gather also fills `nxt`'s table with dis * out."""
+        sc = side_copy(side)
+        _call("gn_graph_aggregate_chain_f32", self._h, nxt._h, ptr(x), ld(x), x.shape[1], ptr(weight), weight.shape[1], ptr(bias),
+              int(bool(relu)), ptr(out), ld(out), _ref(sc), stream_ptr(x.device))
+        return out
+
+    def gather_chained(self, out: torch.Tensor):
+        """out[:, 0:16] = A_norm h, h the layer output the previous `aggregate_chain(nxt=self)` left in this plan's table."""
+        _call("gn_graph_gather_chained_f32", self._h, ptr(out), ld(out), stream_ptr(out.device))
         return out
 
     def aggregate_bf16(self, xw: torch.Tensor, bias, relu: bool, out: torch.Tensor, side=None):

@@ -62,6 +62,14 @@ struct AggArgs {
     const uint16_t* table_bf16 = nullptr;   // the gathered table in bf16 storage (ld_table counts bf16 elements)
 };
 
+// A 16 -> 16 transform left to the reader of its input (k_aggregate_transform_tail): relu(G w + b) of the last 16 columns
+// of every gathered row
+struct AggTail {
+    const float* w;        // [16, 16] row-major, 16-byte aligned
+    const float* b;        // [16], 16-byte aligned, nullable
+    int relu;
+};
+
 // The fused row copy of a launch (a concat slot), streamed by the whole grid; where in the kernel is the caller's choice
 // (the gather family streams it before its own rows, k_col_gather behind them: nothing depends on the order).  The kernel
 // hands in its global thread index and the grid's thread count: blockDim read inside a __device__ function compiles to
@@ -133,6 +141,8 @@ gn_status launch_aggregate(const AggArgs& a, hipStream_t st);
 gn_status launch_aggregate_bf16(const AggArgs& a, int lpe, bool by_group, hipStream_t st);
 // out = act( (A table) w + bias ): shuffle or quad epilogue (transform_fusable), or the matrix cores (mfma_fusable)
 gn_status launch_aggregate_transform(const AggArgs& a, const float* w, int fout, hipStream_t st);
+// the 64 -> 16 shuffle form with the deferred tail transform of the table's columns 48..63
+gn_status launch_aggregate_transform_tail(const AggArgs& a, const float* w, int fout, const AggTail& tail, hipStream_t st);
 gn_status launch_aggregate_mfma(const AggArgs& a, const float* w, int fout, hipStream_t st);
 // the three bf16 terms of src[rows, cols] into columns col0 .. of the planes
 gn_status launch_split_planes(const float* src, int64_t ld_src, int64_t rows, int cols, int col0, const gn_split_planes& sp, hipStream_t st);

@@ -272,10 +272,22 @@ __global__ __launch_bounds__(256) void k_aggregate_group(AggArgs a) {
 // aggregated features 4j..4j+3 of its j; lane (c = lane % FOUT, kq = lane / FOUT) multiplies KPL = FIN * FOUT / 64
 // of them (fetched with shuffles) by its register-resident slice W[kq*KPL .. , c] and the 64 / FOUT partial
 // sums are folded with two more shuffles.
-template <int LPE, int FOUT>
-__global__ __launch_bounds__(256) void k_aggregate_transform(AggArgs a, const float* __restrict__ w) {
+//
+// TAIL (64 input features): the table's last 16 columns hold G = A_norm h of a 16 -> 16 layer whose transform was left to
+// its reader (gn_graph_aggregate_tail_f32): every GATHERED row gets relu(G W2 + b2) in their place before it is multiplied
+// by its coefficient - the ReLU sits between the two sums, so the product cannot move behind this one.  The four lanes
+// j = 12..15 of a neighbour's group hold the 16 floats: a quad, which hands them round with DPP; lane jj of it computes
+// the columns 4 jj .. 4 jj + 3 against its register-resident slice of W2 (one wave per SIMD here: registers are free).
+template <int CTRL>
+__device__ __forceinline__ float tail_bcast(float v) {
+    return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true));
+}
+
+template <int LPE, int FOUT, bool TAIL>
+__device__ __forceinline__ void aggregate_transform(const AggArgs& a, const float* __restrict__ w, const AggTail& tail) {
     constexpr int FIN = 4 * LPE, S = kWave / LPE, G = kWave / FOUT, KPL = FIN / G;
     static_assert(KPL % 4 == 0, "K slice per lane must cover whole float4 groups");
+    static_assert(!TAIL || LPE == 16, "the deferred tail transform is the last quad of a 16-lane group");
     const int lane = threadIdx.x & 63;
     const int slot = lane / LPE, j = lane % LPE;
     const int c = lane % FOUT, kq = lane / FOUT;
@@ -286,6 +298,12 @@ __global__ __launch_bounds__(256) void k_aggregate_transform(AggArgs a, const fl
 #pragma unroll
     for (int i = 0; i < KPL; ++i) wreg[i] = w[(kq * KPL + i) * FOUT + c];
     const float bias = a.bias ? a.bias[c] : 0.f;
+    f32x4 tw[TAIL ? 16 : 1], tb = (f32x4){0.f, 0.f, 0.f, 0.f};               // W2[k][4 jj .. 4 jj + 3], b2[4 jj ..]
+    if constexpr (TAIL) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) tw[k] = *reinterpret_cast<const f32x4*>(tail.w + 16 * k + 4 * (j & 3));
+        if (tail.b) tb = *reinterpret_cast<const f32x4*>(tail.b + 4 * (j & 3));
+    }
 
     // concat slot, by the whole grid: the first element of every thread is REQUESTED here and stored behind the rows (a
     // load -> store in front of them put its round trip in front of the rows' own three), the rest (slots longer than
@@ -333,6 +351,27 @@ __global__ __launch_bounds__(256) void k_aggregate_transform(AggArgs a, const fl
                     t[it] = make_float4(0.f, 0.f, 0.f, 0.f);
                     if (idx < cnt) t[it] = *reinterpret_cast<const float4*>(a.table + (int64_t)cc * a.ld_table + 4 * j);
                 }
+                if constexpr (TAIL) {
+#pragma unroll
+                    for (int it = 0; it < U; ++it) {
+                        if ((it0 + it) * S >= cnt) continue;                       // (wave-uniform: no row in this group)
+                        const float g[4] = {t[it].x, t[it].y, t[it].z, t[it].w};
+                        f32x4 h = tb;
+#pragma unroll
+                        for (int cc = 0; cc < 4; ++cc) {                           // lane jj of the quad holds G[4 jj + cc]
+                            h += tail_bcast<0x00>(g[cc]) * tw[cc];
+                            h += tail_bcast<0x55>(g[cc]) * tw[4 + cc];
+                            h += tail_bcast<0xAA>(g[cc]) * tw[8 + cc];
+                            h += tail_bcast<0xFF>(g[cc]) * tw[12 + cc];
+                        }
+                        if (tail.relu) {
+#pragma unroll
+                            for (int cc = 0; cc < 4; ++cc) h[cc] = fmaxf(h[cc], 0.f);
+                        }
+                        // (a slot beyond the row's end stays zero: relu(b2) is not)
+                        if (j >= 12 && (it0 + it) * S + slot < cnt) t[it] = make_float4(h[0], h[1], h[2], h[3]);
+                    }
+                }
 #pragma unroll
                 for (int it = 0; it < U; ++it) {
                     acc[0] += vv[it] * t[it].x; acc[1] += vv[it] * t[it].y; acc[2] += vv[it] * t[it].z; acc[3] += vv[it] * t[it].w;
@@ -364,6 +403,14 @@ __global__ __launch_bounds__(256) void k_aggregate_transform(AggArgs a, const fl
         a.side.dst[i * a.side.ld_dst + cc] = o;
         if (a.split.planes) write_split(a.split, i, a.split.col_side + (int)cc, o);
     }
+}
+
+template <int LPE, int FOUT>
+__global__ __launch_bounds__(256) void k_aggregate_transform(AggArgs a, const float* __restrict__ w) {
+    aggregate_transform<LPE, FOUT, false>(a, w, AggTail{nullptr, nullptr, 0});
+}
+__global__ __launch_bounds__(256) void k_aggregate_transform_tail(AggArgs a, const float* __restrict__ w, AggTail tail) {
+    aggregate_transform<16, 16, true>(a, w, tail);
 }
 
 
@@ -710,6 +757,16 @@ gn_status launch_aggregate_transform(const AggArgs& a, const float* w, int fout,
         case 6432: k_aggregate_transform<16, 32><<<grid, 256, 0, st>>>(a, w); break;
         default: return fail(GN_ERR_UNSUPPORTED, "no fused transform for %d -> %d features", a.features, fout);
     }
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+gn_status launch_aggregate_transform_tail(const AggArgs& a, const float* w, int fout, const AggTail& tail, hipStream_t st) {
+    if (a.features != 64 || fout != 16)
+        return fail(GN_ERR_UNSUPPORTED, "the deferred tail transform exists for 64 -> 16 features, got %d -> %d", a.features, fout);
+    if (a.rows == 0) return GN_OK;
+    const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
+    k_aggregate_transform_tail<<<grid, 256, 0, st>>>(a, w, tail);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

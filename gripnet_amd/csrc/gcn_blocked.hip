@@ -149,6 +149,7 @@ struct ColArgs {
     float* out; int64_t ld_out;
     int n, rows_pad, groups, ranges, relu;
     gn_side_copy side;
+    float* next_table;                   // k_col_gather_next: the next layer's table, [groups][rows_pad][CW] (see col_gather)
 };
 
 #ifdef GN_STAMPS
@@ -156,8 +157,12 @@ struct ColArgs {
 __device__ unsigned long long g_blk_stamps[2][512][4];
 #endif
 
-template <int CW>
-__global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp_set) {
+// NEXT: the workgroup that owns (column group, destination rows) also writes dis[row] * r, r = what it stores to `out`,
+// into ITS cells of next_table: the table T' = dis * h of a following layer over the same graph whose transform is applied
+// behind that layer's sum instead of in front of it, (A h) W = A (h W) (gn_graph_aggregate_chain_f32).  Column-local: no
+// workgroup waits for another, the kernel boundary that follows hands the table over.
+template <int CW, bool NEXT>
+__device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
     typedef float vec_t __attribute__((ext_vector_type(CW)));
     extern __shared__ f32x4 lds4[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -238,6 +243,8 @@ __global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp
                 _Pragma("unroll") for (int c = 0; c < CW; ++c) r[c] = fmaxf(r[c], 0.f);                        \
             }                                                                                                  \
             *reinterpret_cast<vec_t*>(a.out + (int64_t)row * a.ld_out + CW * cg) = r;                          \
+            if constexpr (NEXT)                                                                                \
+                *reinterpret_cast<vec_t*>(a.next_table + ((size_t)cg * a.rows_pad + row) * CW) = r * d;        \
         }                                                                                                      \
         acc = (vec_t)(0.f);                                                                                    \
         ++t;                                                                                                   \
@@ -285,6 +292,11 @@ __global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp
     gn::side_copy_stream(a.side, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
+template <int CW>
+__global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp_set) { col_gather<CW, false>(a, stamp_set); }
+template <int CW>
+__global__ __launch_bounds__(kColThreads) void k_col_gather_next(ColArgs a, int stamp_set) { col_gather<CW, true>(a, stamp_set); }
+
 template <int FIN, int NT>
 void launch_transform(const TransArgs& t, int cw, hipStream_t st) {
     const int grid = (int)std::min<int64_t>(gn::ceil_div(t.rows_pad / 16, 4), GN_AGG_GRID);
@@ -312,17 +324,15 @@ bool gn_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld
     return (ld_x % 4) == 0 && gn::aligned16(x);
 }
 
-gn_status gn_blocked_aggregate(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w,
-                               int64_t fout, const float* bias, int relu, float* out, int64_t ld_out,
-                               const gn_side_copy& side, hipStream_t st) {
-    const int cw = plan->blk_cw;
-    GN_REQUIRE((ld_out % cw) == 0 && (reinterpret_cast<uintptr_t>(out) % (4 * cw)) == 0 &&
-               (!bias || (reinterpret_cast<uintptr_t>(bias) % (4 * cw)) == 0),
-               "the LDS-staged path writes %d-float column groups: out and bias must be aligned to them", cw);
-    // 1. the scaled table T = dis * (x W), column-group-major
+namespace {
+
+// T = dis * (x W) of the plan, column-group-major (w == null: T = dis * x)
+gn_status blocked_transform(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout,
+                            hipStream_t st) {
     TransArgs t;
     t.x = x; t.ld_x = ld_x; t.w = w; t.dis = plan->blk_dis.p; t.table = plan->blk_table.p; t.n = (int)plan->rows;
     t.rows_pad = plan->blk_rows;
+    const int cw = plan->blk_cw;
     switch ((int)((w ? fin : fout) * 100 + fout)) {
         case 1616: launch_transform<16, 1>(t, cw, st); break;
         case 3216: launch_transform<32, 1>(t, cw, st); break;
@@ -333,27 +343,96 @@ gn_status gn_blocked_aggregate(const gn_graph_plan* plan, const float* x, int64_
         default: return gn::fail(GN_ERR_UNSUPPORTED, "no LDS-staged kernel for %lld -> %lld features", (long long)fin, (long long)fout);
     }
     GN_LAUNCH_CHECK();
-    // 2. gather from LDS, one workgroup per (column group, range of destination rows)
+    return GN_OK;
+}
+
+// The gather from LDS over the plan's table as it stands, one workgroup per (column group, range of destination rows);
+// next_table != null: the launch also fills that table of a following layer (k_col_gather_next)
+gn_status blocked_gather(const gn_graph_plan* plan, int64_t fout, const float* bias, int relu, float* out, int64_t ld_out,
+                         const gn_side_copy& side, float* next_table, int stamp_set, hipStream_t st) {
+    const int cw = plan->blk_cw;
+    GN_REQUIRE((ld_out % cw) == 0 && (reinterpret_cast<uintptr_t>(out) % (4 * cw)) == 0 &&
+               (!bias || (reinterpret_cast<uintptr_t>(bias) % (4 * cw)) == 0),
+               "the LDS-staged path writes %d-float column groups: out and bias must be aligned to them", cw);
     ColArgs a;
     a.table = plan->blk_table.p; a.cell = plan->blk_cell.p; a.tile_off = plan->blk_tile_off.p; a.tile_rows = plan->blk_tile_rows.p;
     a.tile_dis = plan->blk_tile_dis.p;
     a.ids = reinterpret_cast<const u32x2*>(plan->blk_ids.p); a.dis = plan->blk_dis.p; a.bias = bias;
     a.out = out; a.ld_out = ld_out; a.n = (int)plan->rows; a.rows_pad = plan->blk_rows;
-    a.groups = (int)(fout / cw); a.ranges = plan->blk_cells; a.relu = relu; a.side = side;
+    a.groups = (int)(fout / cw); a.ranges = plan->blk_cells; a.relu = relu; a.side = side; a.next_table = next_table;
     const int per_x = (a.ranges + 7) / 8;
     const int grid = 8 * per_x * a.groups;
     const size_t lds = (size_t)plan->blk_rows * cw * sizeof(float);
-    if (cw == 2) {
-        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(k_col_gather<2>), (int)kColLdsBytes);
-        if (s != GN_OK) return s;
-        k_col_gather<2><<<grid, kColThreads, lds, st>>>(a, (int)(fin == 32 ? 0 : 1));
-    } else {
-        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(k_col_gather<1>), (int)kColLdsBytes);
-        if (s != GN_OK) return s;
-        k_col_gather<1><<<grid, kColThreads, lds, st>>>(a, (int)(fin == 32 ? 0 : 1));
-    }
+    auto launch = [&](auto kernel) {
+        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(kernel), (int)kColLdsBytes);
+        if (s == GN_OK) kernel<<<grid, kColThreads, lds, st>>>(a, stamp_set);
+        return s;
+    };
+    gn_status s;
+    if (next_table) s = cw == 2 ? launch(k_col_gather_next<2>) : launch(k_col_gather_next<1>);
+    else s = cw == 2 ? launch(k_col_gather<2>) : launch(k_col_gather<1>);
+    if (s != GN_OK) return s;
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+// The chained gene stack is opt-in (GN_ENABLE_CHAIN=1) until it has been measured against the four-launch stack on the GPU
+bool chain_disabled() {
+    const char* e = getenv("GN_ENABLE_CHAIN");
+    return !(e && e[0] == '1') || blocked_disabled();
+}
+
+// `next` can take its table from a gather over `plan`: both have the LDS-staged encoding of the same unit-weight graph
+bool chain_plans_match(const gn_graph_plan* plan, const gn_graph_plan* next) {
+    return plan && next && plan != next && plan->blk_ok && next->blk_ok && plan->is_gcn && next->is_gcn && plan->unit_weights &&
+           next->unit_weights && plan->rows == next->rows && plan->nnz == next->nnz && plan->blk_rows == next->blk_rows &&
+           plan->blk_cw == next->blk_cw && plan->blk_cells == next->blk_cells && plan->blk_iters == next->blk_iters &&
+           next->blk_cols >= 16;
+}
+
+}  // namespace
+
+gn_status gn_blocked_aggregate(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w,
+                               int64_t fout, const float* bias, int relu, float* out, int64_t ld_out,
+                               const gn_side_copy& side, hipStream_t st) {
+    // 1. the scaled table T = dis * (x W), column-group-major; 2. the gather from LDS
+    const gn_status s = blocked_transform(plan, x, ld_x, fin, w, fout, st);
+    return s != GN_OK ? s : blocked_gather(plan, fout, bias, relu, out, ld_out, side, nullptr, fin == 32 ? 0 : 1, st);
+}
+
+// ---- two layers over one graph, the second one's transform deferred to its reader (gripnet_hip.h) ----------------------
+extern "C" int gn_graph_chain_applicable(const gn_graph_plan* plan, const gn_graph_plan* next, const float* x, int64_t ld_x,
+                                         int64_t num_features, const float* weight, int64_t out_features, const float* bias,
+                                         const float* out, int64_t ld_out, const float* out_next) {
+    if (chain_disabled() || !chain_plans_match(plan, next) || !weight || out_features != 16) return 0;
+    if (!gn_blocked_applicable(plan, x, ld_x, num_features, weight, out_features, bias, out, ld_out)) return 0;
+    return (reinterpret_cast<uintptr_t>(out_next) % (4 * next->blk_cw)) == 0 ? 1 : 0;
+}
+
+extern "C" gn_status gn_graph_aggregate_chain_f32(const gn_graph_plan* plan, const gn_graph_plan* next, const float* x,
+                                                  int64_t ld_x, int64_t num_features, const float* weight, int64_t out_features,
+                                                  const float* bias, int relu, float* out, int64_t ld_out,
+                                                  const gn_side_copy* side, void* stream) {
+    GN_REQUIRE(plan && next && x && weight && out, "a plan or a feature pointer is null");
+    GN_REQUIRE(ld_x >= num_features && ld_out >= out_features, "leading dimension smaller than the row length");
+    if (!gn_graph_chain_applicable(plan, next, x, ld_x, num_features, weight, out_features, bias, out, ld_out, nullptr))
+        return gn::fail(GN_ERR_UNSUPPORTED, "the two plans do not chain (LDS-staged plans of one unit-weight graph, 16 output "
+                                            "features, GN_ENABLE_CHAIN=1) or the operands keep the wave-per-row kernels");
+    gn_side_copy sc;
+    gn_status s = gn::check_side(side, plan->rows, &sc);
+    if (s != GN_OK) return s;
+    hipStream_t st = gn::as_stream(stream);
+    s = blocked_transform(plan, x, ld_x, num_features, weight, out_features, st);
+    return s != GN_OK ? s : blocked_gather(plan, out_features, bias, relu, out, ld_out, sc, next->blk_table.p, 0, st);
+}
+
+extern "C" gn_status gn_graph_gather_chained_f32(const gn_graph_plan* plan, float* out, int64_t ld_out, void* stream) {
+    GN_REQUIRE(plan && out && ld_out >= 16, "plan or out is null, or the leading dimension smaller than 16");
+    if (chain_disabled() || !plan->blk_ok || !plan->is_gcn || !plan->unit_weights || plan->blk_cols < 16)
+        return gn::fail(GN_ERR_UNSUPPORTED, "the plan has no LDS-staged encoding of a unit-weight graph, or the chain is not enabled (GN_ENABLE_CHAIN=1)");
+    const gn_side_copy none = {nullptr, 0, nullptr, 0, 0, 0, 0};
+    // no bias, no activation: dis[i] * the sum of the table rows, i.e. A_norm h of the table's layer
+    return blocked_gather(plan, 16, nullptr, 0, out, ld_out, none, nullptr, 1, gn::as_stream(stream));
 }
 
 // Adds the LDS-staged encoding to a GCN plan whose stored weights are all 1 (self loops included), for layers of up to
@@ -414,6 +493,9 @@ extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t co
     GN_HIP(plan->blk_ids.alloc(ids.size() / 2));
     GN_HIP(plan->blk_cell.alloc(cell.size()));
     GN_HIP(plan->blk_table.alloc((size_t)rows_pad * cols));
+    // rows beyond the last node stay zero for the life of the plan (padded id slots name row N): k_col_transform writes
+    // zeros there, a table filled by another plan's gather (k_col_gather_next) is written at the nodes' rows only
+    GN_HIP(hipMemsetAsync(plan->blk_table.p, 0, (size_t)rows_pad * cols * sizeof(float), st));
     GN_HIP(hipMemcpyAsync(plan->blk_dis.p, dis_host.data(), dis_host.size() * sizeof(float), hipMemcpyHostToDevice, st));
     GN_HIP(hipMemcpyAsync(plan->blk_tile_off.p, tile_off.data(), tile_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     GN_HIP(hipMemcpyAsync(plan->blk_tile_rows.p, tile_rows.data(), tile_rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));

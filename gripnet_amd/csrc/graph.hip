@@ -9,16 +9,9 @@ gn_status gn_blocked_aggregate(const gn_graph_plan* plan, const float* x, int64_
                                int64_t fout, const float* bias, int relu, float* out, int64_t ld_out,
                                const gn_side_copy& side, hipStream_t st);
 
-extern "C" gn_status gn_graph_aggregate_f32(const gn_graph_plan* plan, const float* xw, int64_t ld_xw,
-                                            int64_t num_features, const float* weight, int64_t out_features,
-                                            const float* bias, int relu, float* out, int64_t ld_out,
-                                            const gn_side_copy* side, const gn_split_planes* planes, void* stream) {
-    GN_REQUIRE(plan != nullptr, "plan is null");
-    GN_REQUIRE(num_features >= 0 && num_features < (1ll << 31), "bad feature count");
-    if (plan->rows == 0 || num_features == 0) return GN_OK;
-    GN_REQUIRE(xw && out, "feature pointers are null");
-    const int64_t width = weight ? out_features : num_features;
-    GN_REQUIRE(ld_xw >= num_features && ld_out >= width, "leading dimension smaller than the row length");
+// the gather's arguments of a forward call on `plan`
+static gn::AggArgs forward_args(const gn_graph_plan* plan, const float* xw, int64_t ld_xw, int64_t num_features, const float* bias,
+                                int relu, float* out, int64_t ld_out) {
     gn::AggArgs a;
     a.rowptr = plan->rowptr.p;
     a.col = reinterpret_cast<const uint32_t*>(plan->col.p);
@@ -37,14 +30,34 @@ extern "C" gn_status gn_graph_aggregate_f32(const gn_graph_plan* plan, const flo
     a.nnz = plan->nnz;
     a.table_rows = plan->table_rows;
     if (plan->ell_ok) { a.ell_col = plan->ell_col.p; a.ell_coef = plan->ell_coef.p; }
-    gn_status ss = gn::check_side(side, plan->rows, &a.side);
-    if (ss != GN_OK) return ss;
+    return a;
+}
+
+static gn_status check_planes(const gn_split_planes* planes, const gn_graph_plan* plan, int64_t width, const gn_side_copy& side) {
     if (planes && planes->planes) {
         GN_REQUIRE(planes->nt >= 1 && planes->nt <= 4 && planes->rows >= plan->rows && planes->col_main >= 0 &&
                        planes->col_main + width <= 16 * planes->nt &&
-                       (!a.side.dst || (planes->col_side >= 0 && planes->col_side + a.side.cols <= 16 * planes->nt)),
+                       (!side.dst || (planes->col_side >= 0 && planes->col_side + side.cols <= 16 * planes->nt)),
                    "split planes do not hold the launch's columns");
     }
+    return GN_OK;
+}
+
+extern "C" gn_status gn_graph_aggregate_f32(const gn_graph_plan* plan, const float* xw, int64_t ld_xw,
+                                            int64_t num_features, const float* weight, int64_t out_features,
+                                            const float* bias, int relu, float* out, int64_t ld_out,
+                                            const gn_side_copy* side, const gn_split_planes* planes, void* stream) {
+    GN_REQUIRE(plan != nullptr, "plan is null");
+    GN_REQUIRE(num_features >= 0 && num_features < (1ll << 31), "bad feature count");
+    if (plan->rows == 0 || num_features == 0) return GN_OK;
+    GN_REQUIRE(xw && out, "feature pointers are null");
+    const int64_t width = weight ? out_features : num_features;
+    GN_REQUIRE(ld_xw >= num_features && ld_out >= width, "leading dimension smaller than the row length");
+    gn::AggArgs a = forward_args(plan, xw, ld_xw, num_features, bias, relu, out, ld_out);
+    gn_status ss = gn::check_side(side, plan->rows, &a.side);
+    if (ss != GN_OK) return ss;
+    ss = check_planes(planes, plan, width, a.side);
+    if (ss != GN_OK) return ss;
     // the kernels that do not write the planes themselves are followed by the stand-alone split of what they wrote
     auto then_split = [&](gn_status s) {
         if (s != GN_OK || !planes || !planes->planes) return s;
@@ -68,6 +81,32 @@ extern "C" gn_status gn_graph_aggregate_f32(const gn_graph_plan* plan, const flo
         return quad ? then_split(s) : s;
     }
     return then_split(gn::launch_aggregate(a, gn::as_stream(stream)));
+}
+
+// act( (A_norm x') weight + bias ), x' = x with its columns 48..63 replaced row by row by act2(x[:, 48:64] tail_w + tail_b):
+// the external layer reading a gene concat whose last layer left A_norm h there and its 16 -> 16 transform to this launch
+extern "C" gn_status gn_graph_aggregate_tail_f32(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,
+                                                 const float* weight, int64_t out_features, const float* bias, int relu,
+                                                 float* out, int64_t ld_out, const gn_side_copy* side,
+                                                 const gn_split_planes* planes, const float* tail_w, const float* tail_b,
+                                                 int tail_relu, void* stream) {
+    GN_REQUIRE(plan != nullptr, "plan is null");
+    GN_REQUIRE(x && weight && out && tail_w, "a feature or weight pointer is null");
+    GN_REQUIRE(ld_x >= num_features && ld_out >= out_features, "leading dimension smaller than the row length");
+    if (num_features != 64 || out_features != 16 || gn::fast_paths_disabled() || (ld_x % 4) != 0 || !gn::aligned16(x) ||
+        !gn::aligned16(tail_w) || !gn::aligned16(tail_b))
+        return gn::fail(GN_ERR_UNSUPPORTED, "the deferred tail transform exists for 64 -> 16 features over 16-byte aligned rows "
+                                            "on the wave-per-row kernel, got %lld -> %lld", (long long)num_features,
+                        (long long)out_features);
+    if (plan->rows == 0) return GN_OK;
+    gn::AggArgs a = forward_args(plan, x, ld_x, num_features, bias, relu, out, ld_out);
+    gn_status ss = gn::check_side(side, plan->rows, &a.side);
+    if (ss != GN_OK) return ss;
+    ss = check_planes(planes, plan, out_features, a.side);
+    if (ss != GN_OK) return ss;
+    if (planes && planes->planes) a.split = *planes;                                 // written by the kernel's own epilogue
+    return gn::launch_aggregate_transform_tail(a, weight, (int)out_features, gn::AggTail{tail_w, tail_b, tail_relu},
+                                               gn::as_stream(stream));
 }
 
 extern "C" size_t gn_split_planes_bytes(int64_t rows, int nt) {

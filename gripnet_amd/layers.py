@@ -117,13 +117,16 @@ class myGCN(Module):
         # (_pass: also return x, for the concat that holds it - homoGraph's training path; GcnConvFn)
         _hip.require_gpu(x, edge_index, edge_weight, self.weight)
         n = x.size(0)
+        return self._run(self._gcn_plan(edge_index, n, edge_weight), x, n, _out, _relu, _side, passthrough=_pass)
+
+    def _gcn_plan(self, edge_index, n, edge_weight):
+        """The layer's plan over a square graph of `n` nodes, under the cache protocol of `_plan`."""
         def build():
             plan = _hip.GraphPlan.gcn(edge_index, n, edge_weight, self.improved)
             if self.cached:                              # LDS-staged gathers where the graph qualifies: a host-side
                 plan.build_blocked(self.out_channels)    # schedule of the CSR, worth it only for a graph that is kept
             return plan
-        plan = self._plan(edge_index, build)
-        return self._run(plan, x, n, _out, _relu, _side, passthrough=_pass)
+        return self._plan(edge_index, build)
 
     def forward_bipartite(self, x, inter_edge_index, n_target, edge_weight=None, *, _out=None, _relu=False, _side=None,
                           _planes=None):
@@ -352,11 +355,7 @@ class interGraph(Module):
                 _, (ys, ts) = cat_slots([self.target_dim, self.target_feat_dim], self.n_target, dev)
                 # the same launch leaves the row as bf16 split planes (as on the inference path): a relational layer that takes
                 # this output contracts with them instead of splitting x in every unit
-                width, planes = self.target_dim + self.target_feat_dim, None
-                if width % 16 == 0 and width <= 64 and self.conv.table_storage == "fp32":
-                    planes = getattr(self, "_planes", None)
-                    if planes is None or planes.device != dev:
-                        planes = self._planes = _hip.SplitPlanes(self.n_target, width // 16, dev)
+                planes = self._cat_planes(dev)
                 y = self.conv.forward_bipartite(x, inter_edge_index, self.n_target, edge_weight, _relu=if_relu, _out=ys,
                                                 _side=(self.target_feat, ts, 1),
                                                 _planes=None if planes is None else (planes, 0, self.target_dim))
@@ -397,20 +396,117 @@ class interGraph(Module):
         _hip.gemm(self.target_feat, self.target_feat_down, down)
         return _hip.merge(y, down, 3)
 
+    def _cat_planes(self, dev):
+        """The split planes the `cat` launch leaves of its output row (None: widths or storage they do not cover)."""
+        width, planes = self.target_dim + self.target_feat_dim, None
+        if width % 16 == 0 and width <= 64 and self.conv.table_storage == "fp32":
+            planes = getattr(self, "_planes", None)
+            if planes is None or planes.device != dev:
+                planes = self._planes = _hip.SplitPlanes(self.n_target, width // 16, dev)
+        return planes
+
     def _infer_cat(self, x, inter_edge_index, edge_weight, if_relu, out):
         """[y | |target_feat|] (layers.py:375-376) written into the columns of `out` by ONE launch, which also leaves the
         row as bf16 split planes: a relational layer that takes this output as its input (GripNet-pose.py:120-127)
         contracts with them instead of splitting x in every unit."""
         dev = x.device
         y, tf = out[:, :self.target_dim], out[:, self.target_dim:]
-        width, planes = self.target_dim + self.target_feat_dim, None
-        if width % 16 == 0 and width <= 64 and self.conv.table_storage == "fp32":
-            planes = getattr(self, "_planes", None)
-            if planes is None or planes.device != dev:
-                planes = self._planes = _hip.SplitPlanes(self.n_target, width // 16, dev)
+        planes = self._cat_planes(dev)
         self.conv.forward_bipartite(x, inter_edge_index, self.n_target, edge_weight, _out=y, _relu=if_relu,
                                     _side=(self.target_feat, tf, 1),     # |target_feat| slot, same launch
                                     _planes=None if planes is None else (planes, 0, self.target_dim))
         if planes is not None and getattr(self.conv, "_planes_written", False):
             planes.tag(out)
         return out
+
+
+def gene_stack_to_external(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu=True):
+    """``gd(gg(None, gg_edge_index, edge_weight=edge_weight, if_catout=True), gd_edge_index, mod="cat", if_relu=if_relu)``
+    (GripNet-pose.py:117-120), and where it can in three gene launches instead of four: the last gene layer is 16 -> 16, so
+    relu(A (h1 W2) + b2) = relu((A h1) W2 + b2) - its gather reads a table dis * h1 that the gather of the layer before it
+    writes, and its transform is applied by the external layer's launch to every gene row it gathers, the only reader of
+    those rows.  The gene concat then holds A h1 in its last slot, not h2: it stays inside this function.
+
+    Chained when no gradient is recorded (grad mode off), `gg` starts the graph with a two-layer non-relational stack whose
+    last layer is 16 -> 16, both layers hold LDS-staged plans, storage and arithmetic are the defaults, `gd` is the
+    one-external `cat` form over 64 gene columns and the library takes the operands (gn_graph_chain_applicable: opt-in with
+    GN_ENABLE_CHAIN=1 until the step has been measured with it); otherwise the two module calls, as before.  `gene_stack_path(gg)` tells which.  One re-associated fp32 sum apart, the chained
+    result is the separate one."""
+    chained = _gene_chain(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu)
+    gg.__dict__["_gene_stack_path"] = "separate" if chained is None else "chained"
+    if chained is not None:
+        return chained
+    z = gg(None, gg_edge_index, edge_weight=edge_weight, if_catout=True)
+    return gd(z, gd_edge_index, mod="cat", if_relu=if_relu)
+
+
+def gene_stack_path(gg):
+    """"chained" or "separate": the path the last `gene_stack_to_external` call on `gg` took (None before the first)."""
+    return gg.__dict__.get("_gene_stack_path")
+
+
+def _gene_chain(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu):
+    """The chained launches of `gene_stack_to_external`, or None where they do not apply."""
+    if torch.is_grad_enabled() or not isinstance(gg, homoGraph) or not isinstance(gd, interGraph):
+        return None
+    if gg.multi_relational or not gg.start_graph or len(gg.conv_list) != 2 or not gd.if_one_external:
+        return None
+    c1, c2, cd = gg.conv_list[0], gg.conv_list[1], gd.conv
+    widths = [gg.embedding.shape[1], c1.out_channels, c2.out_channels]
+    if (c2.in_channels, c2.out_channels) != (16, 16) or sum(widths) != 64 or (cd.in_channels, cd.out_channels) != (64, 16):
+        return None
+    if any(c.table_storage != "fp32" or c.arithmetic != "fp32" or not c.weight.is_contiguous() for c in (c1, c2, cd)):
+        return None
+    if not c1.cached or not c2.cached or c2.bias is None or not gd.target_feat.is_contiguous():
+        return None
+    _hip.require_gpu(gg.embedding, gg_edge_index, edge_weight, gd_edge_index)
+    x = _hip.f32_rows(gg.embedding.detach())
+    n, dev = x.shape[0], x.device
+    p1, p2 = c1._gcn_plan(gg_edge_index, n, edge_weight), c2._gcn_plan(gg_edge_index, n, edge_weight)
+    pd = cd._plan(gd_edge_index, lambda: _hip.GraphPlan.bipartite(gd_edge_index, n, gd.n_target, None))
+    out = torch.empty((gd.n_target, gd.target_dim + gd.target_feat_dim), dtype=torch.float32, device=dev)
+
+    def run():
+        genes = torch.empty((n, 64), dtype=torch.float32, device=dev)     # [embedding | h1 | A h1], internal
+        s0, s1, s2 = genes[:, :widths[0]], genes[:, widths[0]:widths[0] + 16], genes[:, 48:]
+        if not (p1.chain_ok(p2, x, c1.weight, c1.bias, s1, s2) and pd.transform_ok(64, 16, genes)):
+            raise _NotChained()                  # (before the first launch: nothing is recorded, nothing memoised)
+        p1.aggregate_chain(p2, x, c1.weight, c1.bias, True, s1, side=(x, s0, 0))
+        p2.gather_chained(s2)
+        planes = gd._cat_planes(dev)
+        pd.aggregate(genes, cd.bias, if_relu, out[:, :gd.target_dim], (gd.target_feat, out[:, gd.target_dim:], 1),
+                     weight=cd.weight, planes=None if planes is None else (planes, 0, gd.target_dim), tail=(c2.weight, c2.bias))
+        if planes is not None:
+            planes.tag(out)
+        return out
+
+    try:
+        return _gene_chain_memo(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu, x, out, (c1, c2, cd), (p1, p2, pd), run)
+    except _NotChained:
+        return None
+
+
+class _NotChained(Exception):
+    """The library does not take the chained launches for these operands."""
+
+
+def _gene_chain_memo(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu, x, out, convs, plans, run):
+    """`run()`, or in the steady state its recorded calls (_hip.CallMemo; see homoGraph.forward): one entry under both
+    modules' guards."""
+    if _hip._recorder is not None:
+        return run()
+    n, dev = x.shape[0], x.device
+    guard = (x.data_ptr(), n, x.stride(0), id(gg_edge_index), gg_edge_index._version, id(edge_weight),
+             0 if edge_weight is None else edge_weight._version, id(gd_edge_index), gd_edge_index._version, bool(if_relu), id(gd),
+             gd.target_feat.data_ptr(),
+             tuple([(id(c.cached_result),) + tuple([0 if p is None else p.data_ptr() for p in c._parameters.values()])
+                    for c in convs]),
+             _hip.launch_context(dev), _hip.env_stamp())
+    memo = gg.__dict__.get("_chain_memo")
+    if memo is None:
+        memo = gg.__dict__["_chain_memo"] = _hip.CallMemo()
+
+    def retag():                        # the launch leaves the output's split planes: on a hit they describe THAT output
+        planes = _hip.SplitPlanes.of(out, out.shape[1] // 16) if out.shape[1] % 16 == 0 else None
+        return None if planes is None else planes.rewritten_for
+    return memo.run(guard, out, run, drop=(out,), hold=lambda: (gg_edge_index, edge_weight, gd_edge_index, gd) + tuple(plans), post=retag)

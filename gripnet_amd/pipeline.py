@@ -14,7 +14,7 @@ from torch.nn import Module
 
 from . import _hip
 from .decoder import multiClassInnerProductDecoder, multiRelaInnerProductDecoder
-from .layers import homoGraph, interGraph
+from .layers import gene_stack_to_external, homoGraph, interGraph
 
 POSE_HPARAMS = dict(gg_nhids=[32, 16, 16], gd_out=[16, 32])     # GripNet-pose.py:86-89
 
@@ -33,8 +33,7 @@ class PoseModel(Module):
         self.dmt = multiRelaInnerProductDecoder(sum(dd_nhids), n_dd_edge_type)                 # pose.py:98
 
     def encode(self, data):
-        z = self.gg(None, data.gg_edge_index, edge_weight=data.edge_weight, if_catout=True)    # pose.py:117-119
-        z = self.gd(z, data.gd_edge_index, mod="cat", if_relu=True)                            # pose.py:120
+        z = gene_stack_to_external(self.gg, self.gd, data.gg_edge_index, data.edge_weight, data.gd_edge_index)   # pose.py:117-120
         return self.dd(z, data.train_idx, edge_type=data.train_et, range_list=data.train_range,
                        if_catout=True)                                                         # pose.py:121-127
 
@@ -249,8 +248,8 @@ class PoseStages:
 
     def _genes_eager(self):
         d = self.data
-        z = self.model.gg(None, d.gg_edge_index, edge_weight=d.edge_weight, if_catout=True)
-        return self.model.gd(z, d.gd_edge_index, mod="cat", if_relu=True)    # x, tagged with its bf16 split planes
+        return gene_stack_to_external(self.model.gg, self.model.gd, d.gg_edge_index, d.edge_weight,
+                                      d.gd_edge_index)                      # x, tagged with its bf16 split planes
 
     def _decode_eager(self):
         return self.model.dmt(self.z, self.idx, self.et)

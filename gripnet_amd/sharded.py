@@ -39,8 +39,9 @@ class HipShardKernels:
         self.et = data.train_et[lo:hi].contiguous()
 
     def encode_genes(self):
-        z = self.model.gg(None, self.data.gg_edge_index, edge_weight=self.data.edge_weight, if_catout=True)
-        return self.model.gd(z, self.data.gd_edge_index, mod="cat", if_relu=True)
+        from .layers import gene_stack_to_external
+        return gene_stack_to_external(self.model.gg, self.model.gd, self.data.gg_edge_index, self.data.edge_weight,
+                                      self.data.gd_edge_index)
 
     def partial(self, x, out, fresh_weights=False):
         """(`fresh_weights` stays in the signature the CPU stand-in kernels of the gloo tests share: every call computes what it needs.)"""

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 159 /* 0.1.53 */
+#define GN_VERSION 160 /* 0.1.54 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -159,6 +159,39 @@ GN_API int64_t gn_graph_plan_blocked_cols(const gn_graph_plan* plan);
 GN_API int gn_graph_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,
                                        const float* weight, int64_t out_features, const float* bias, const float* out,
                                        int64_t ld_out);
+
+/* Two GCN-style layers over ONE graph followed by a reader of their rows, with the second layer's 16 -> 16 transform left
+ * to that reader (the gene stack of PoSE feeding the external layer: three gene launches instead of four):
+ *   h1 = act( A (x W1) + b1 ),   h2 = act( A (h1 W2) + b2 ) = act( (A h1) W2 + b2 ).
+ * `plan` and `next` are the two layers' plans: both with the LDS-staged encoding of the same unit-weight graph (equal
+ * rows, stored edges, table rows, column groups and schedule sizes; the caller vouches that the edge lists are the same).
+ *   gn_graph_aggregate_chain_f32   layer 1 as gn_graph_aggregate_f32 computes it (same launches, same bits in `out`); the
+ *                                  gather also stores dis[i] * h1[i, :] into `next`'s scratch table, each workgroup its
+ *                                  own (column group, rows) cells.  out_features = 16.
+ *   gn_graph_gather_chained_f32    out[i, 0:16] = dis[i] * sum of the rows of the plan's table AS IT STANDS (no transform
+ *                                  launch, no bias, no activation): G = A h1 after the call above, with plan = `next`.
+ *   gn_graph_aggregate_tail_f32    gn_graph_aggregate_f32 with `weight` for 64 -> 16 features on the wave-per-row kernel,
+ *                                  except that columns 48..63 of every gathered row are replaced, in registers, by
+ *                                  act(row[48:64] tail_w + tail_b) (tail_relu: the ReLU) BEFORE the row enters the sum.
+ * GN_ERR_UNSUPPORTED where the chain cannot hold: a plan without the encoding, a weighted graph, plans that differ, other
+ * widths, operands gn_graph_blocked_applicable refuses, GN_DISABLE_BLOCKED / GN_DISABLE_FAST, or without GN_ENABLE_CHAIN=1
+ * (the chain is opt-in until it has been measured against the four-launch stack).  gn_graph_chain_applicable tells without launching; out_next is where gn_graph_gather_chained_f32 will write.
+ * Nothing is kept between calls: weights and biases are read by the launches that use them.  The calls on the two plans
+ * must be stream-ordered.  The sum of layer 2 is re-associated, (sum dis h1) W2 instead of sum dis (h1 W2): the same number
+ * of fp32 operations per element, not the same bits. */
+GN_API int gn_graph_chain_applicable(const gn_graph_plan* plan, const gn_graph_plan* next, const float* x, int64_t ld_x,
+                                     int64_t num_features, const float* weight, int64_t out_features, const float* bias,
+                                     const float* out, int64_t ld_out, const float* out_next);
+GN_API gn_status gn_graph_aggregate_chain_f32(const gn_graph_plan* plan, const gn_graph_plan* next, const float* x, int64_t ld_x,
+                                       int64_t num_features, const float* weight, int64_t out_features, const float* bias,
+                                       int relu, float* out, int64_t ld_out, const gn_side_copy* side /* nullable */,
+                                       void* stream);
+GN_API gn_status gn_graph_gather_chained_f32(const gn_graph_plan* plan, float* out, int64_t ld_out, void* stream);
+GN_API gn_status gn_graph_aggregate_tail_f32(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,
+                                      const float* weight, int64_t out_features, const float* bias, int relu, float* out,
+                                      int64_t ld_out, const gn_side_copy* side /* nullable */,
+                                      const gn_split_planes* planes /* nullable */, const float* tail_w,
+                                      const float* tail_b /* nullable */, int tail_relu, void* stream);
 
 /* bf16 STORAGE of the gathered table (the reference is fp32 throughout, this is the build's own
  * reduced-traffic variant for the node-classification suite): gn_cast_bf16 rounds x W to bf16 once,

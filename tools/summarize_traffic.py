@@ -28,6 +28,11 @@ WEIGHTED = {
     # one call per gene layer: its transform (two instantiations, one per layer) and its gather (same kernel, both layers)
     "gn_graph_aggregate_f32[gcn]": (("k_col_transform<32", 0.5), ("k_col_transform<16", 0.5), ("k_col_gather", 1.0)),
     "gn_graph_aggregate_f32[bipartite]": (("gn::k_aggregate_transform<16, 16>", 1.0), ("k_aggregate_transform<16, 16>", 1.0)),
+    # the chained gene stack (layers.gene_stack_to_external): layer 1 with the gather that also fills layer 2's table, layer 2's
+    # gather alone, the external layer with the deferred 16 -> 16 transform
+    "gn_graph_aggregate_chain_f32": (("k_col_transform<32", 1.0), ("k_col_gather_next", 1.0)),
+    "gn_graph_gather_chained_f32": (("k_col_gather<", 1.0),),
+    "gn_graph_aggregate_tail_f32[bipartite]": (("gn::k_aggregate_transform_tail", 1.0), ("k_aggregate_transform_tail", 1.0)),
 }
 # (the default step runs k_rgcn_pair<3, 2, 3, true>; the two-term pass of bench.py - roofline_fast - is the <3, 2, 2, true> instantiation)
 FAST_ONLY = ("k_rgcn_pair<3, 2, 2",)
