@@ -7,12 +7,13 @@
 // element j  <->  k = 4q + j) identically for A and B, which lets A be read with one 16-byte
 // load per lane instead of four strided dwords.
 #include "common.h"
+#include "dense_route.hpp"
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kColTiles = 4;  // 16-column tiles per wave (A-fragment reuse)
+constexpr int kColTiles = gn::route::kColTiles;  // 16-column tiles per wave (A-fragment reuse)
 
 struct GemmArgs {
     const float* __restrict__ a; int64_t lda, stride_a; const int64_t* __restrict__ a_rows; int64_t a_table_rows;
@@ -318,7 +319,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32_lds(GemmArgs g, int row_tiles)
 // the path is 1e-4).  v_mfma_f32_16x16x4_f32 runs at the fp32 vector rate - 20+ us of matrix time on
 // [50000 x 128] @ [128 x 64] - the three v_mfma_f32_16x16x32_bf16 take 3/16 of that and the product becomes a stream
 // over A.  B sits in LDS as hi / lo fragments (16 bytes per lane: eight consecutive k of one column); A is read one
-// 32-deep chunk ahead (two 16-byte loads per lane) and split in registers.  GN_GEMM_EXACT=1 keeps the fp32 instruction.
+// 32-deep chunk ahead (two 16-byte loads per lane) and split in registers.  GN_DISABLE_FAST=1 keeps the fp32 instruction.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -558,27 +559,6 @@ __global__ __launch_bounds__(kSplitThreads) void k_gemm_split_lds(GemmArgs g, in
     }
 }
 
-template <int TERMS, int CT>
-gn_status launch_split(const GemmArgs& g, int row_tiles, dim3 sgrid, size_t split_bytes, int slab, hipStream_t st) {
-#define GN_SPLIT_CASE(CH)                                                                                              \
-    {                                                                                                                  \
-        gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_gemm_split_lds<CH, TERMS, CT>), 160 * 1024); \
-        if (ls != GN_OK) return ls;                                                                                    \
-        k_gemm_split_lds<CH, TERMS, CT><<<sgrid, kSplitThreads, split_bytes, st>>>(g, row_tiles, slab);                \
-    }                                                                                                                  \
-    break
-    switch (slab < g.k / 32 ? 0 : g.k / 32) {
-        case 1: GN_SPLIT_CASE(1);
-        case 2: GN_SPLIT_CASE(2);
-        case 4: GN_SPLIT_CASE(4);
-        case 8: if constexpr (CT == 4) { GN_SPLIT_CASE(8); } else { GN_SPLIT_CASE(0); }
-        default: GN_SPLIT_CASE(0);
-    }
-#undef GN_SPLIT_CASE
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
 __global__ void k_merge(float* __restrict__ dst, int64_t ld_dst, const float* __restrict__ src, int64_t ld_src,
                         const float* __restrict__ src2, int64_t ld_src2, int64_t rows, int cols, int mode) {
     const int64_t total = rows * cols;
@@ -736,8 +716,8 @@ __global__ __launch_bounds__(1024) void k_class_scores(const float* __restrict__
 // Tall and skinny: m is the gene supervertex (~2e4 rows), k1 x k2 a weight matrix (<= 64 x 32).  Every workgroup
 // takes a slice of rows into LDS and leaves its k1 x k2 partial; k_xtg_fold adds the slices in slice order
 // (bitwise reproducible; a library GEMM without split-K spends 60-100 us on these shapes).
-constexpr int kXtgSlices = 256;
-constexpr int kXtgMaxRows = 128;       // rows of a slice held in LDS at a time
+constexpr int kXtgSlices = gn::route::kXtgSlices;
+constexpr int kXtgMaxRows = gn::route::kXtgMaxRows;       // rows of a slice held in LDS at a time
 
 __global__ __launch_bounds__(256) void k_xtg_partial(const float* __restrict__ x, int64_t ld_x, const float* __restrict__ g,
                                                      int64_t ld_g, int64_t m, int k1, int k2, float* __restrict__ partial) {
@@ -785,8 +765,8 @@ __global__ __launch_bounds__(256) void k_xtg_partial(const float* __restrict__ x
 // them round-robin (A operand = x read down its columns, B = g; loads of the next chunk in flight), the waves' accumulators
 // meet in LDS and are added in wave order, the slice's sums are stored write-through, and the last slice to arrive adds all
 // slices in slice order (no fence: MI355X_MICROARCH.md's form for a few KB).  Deterministic; fp32 MFMA = fp32 FMA chains.
-constexpr int kXtgMfmaSlices = 32;       // slices the last one to arrive adds alone
-constexpr int kXtgMfmaMax = 128;         // slices of a long product (two levels: sets of kXtgSet), <= kXtgSlices - kXtgMfmaMax / kXtgSet
+constexpr int kXtgMfmaSlices = gn::route::kXtgMfmaSlices;       // slices the last one to arrive adds alone
+constexpr int kXtgMfmaMax = gn::route::kXtgMfmaMax;         // slices of a long product (two levels: sets of kXtgSet), <= kXtgSlices - kXtgMfmaMax / kXtgSet
 constexpr int kXtgSet = 16;
 
 struct XtgArgs {
@@ -1020,26 +1000,7 @@ __global__ __launch_bounds__(1024) void k_xtg_mfma(XtgArgs a) {
     xtg_mfma_body<MT, NT>(a, blockIdx.x, gridDim.x, xtg_part, &last);
 }
 
-int xtg_slices(int64_t m);
 static_assert(kXtgMfmaMax + kXtgMfmaMax / kXtgSet <= kXtgSlices && (1 + kXtgMfmaMax / kXtgSet) * 4 <= 64, "the sets' sums and tickets live in the workspace of gn_xtg_workspace_bytes");
-
-template <int MT, int NT>
-gn_status launch_xtg_mfma(const float* x, int64_t ld_x, const float* g, int64_t ld_g, int64_t m, int k1, int k2, float* out, int64_t ld_out,
-                          void* workspace, hipStream_t st) {
-    const size_t lds = (size_t)16 * MT * NT * 64 * sizeof(f32x4);
-    if (lds > 64 * 1024) {
-        const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_xtg_mfma<MT, NT>), 136 * 1024);   // (+ 4 static bytes)
-        if (ls != GN_OK) return ls;
-    }
-    // about two chunks per wave; the ticket sits behind the slices' sums
-    const int slices = xtg_slices(m);
-    float* partial = static_cast<float*>(workspace);
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(static_cast<char*>(workspace) + (size_t)kXtgSlices * k1 * k2 * sizeof(float));
-    const XtgArgs a = {x, ld_x, g, ld_g, m, k1, k2, partial, ticket, out, ld_out};
-    k_xtg_mfma<MT, NT><<<slices, 1024, lds, st>>>(a);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
 
 // ---- independent small products in ONE launch ------------------------------------------------------------------------
 // The weight gradients of a layer's backward are a handful of products of a few dozen workgroups and ~10 us each (latency
@@ -1060,6 +1021,12 @@ struct BatchOp {
 };
 struct BatchTable { BatchOp op[kBatchMax]; int n; };
 
+// The tile templates, once each: the ladder of k_dense_batch and the ladders of the launch functions expand from these.
+// (GN_DEEP_TILES names its last shape apart: the device ladder ends in it without a test.)
+#define GN_XTG_TILES(X) X(1, 1) X(2, 1) X(3, 1) X(4, 1) X(1, 2) X(2, 2) X(3, 2) X(4, 2)
+#define GN_DEEP_TILES(X, LAST) X(1, 1) X(2, 1) X(4, 1) LAST(1, 2)
+#define GN_WIDE_TILES(X) X(1, 2) X(2, 1) X(2, 2) X(1, 4) X(4, 1) X(2, 4) X(4, 2) X(4, 4)
+
 __global__ __launch_bounds__(1024) void k_dense_batch(BatchTable tab) {
     extern __shared__ f32x4 batch_lds[];
     __shared__ int last;
@@ -1073,103 +1040,16 @@ __global__ __launch_bounds__(1024) void k_dense_batch(BatchTable tab) {
     }
     if (op.kind == 0) {
         const int bx = vb % op.gx, by = vb / op.gx;
-        if (op.mt == 1 && op.nt == 1) gemm_deep_body<1, 1>(op.g, bx, by, batch_lds);
-        else if (op.mt == 2 && op.nt == 1) gemm_deep_body<2, 1>(op.g, bx, by, batch_lds);
-        else if (op.mt == 4 && op.nt == 1) gemm_deep_body<4, 1>(op.g, bx, by, batch_lds);
-        else gemm_deep_body<1, 2>(op.g, bx, by, batch_lds);
+#define GN_DEEP_BODY(MT, NT) if (op.mt == MT && op.nt == NT) gemm_deep_body<MT, NT>(op.g, bx, by, batch_lds); else
+#define GN_DEEP_LAST(MT, NT) gemm_deep_body<MT, NT>(op.g, bx, by, batch_lds);
+        GN_DEEP_TILES(GN_DEEP_BODY, GN_DEEP_LAST)
+#undef GN_DEEP_BODY
+#undef GN_DEEP_LAST
         return;
     }
 #define GN_XTG_BODY(MT, NT) if (op.mt == MT && op.nt == NT) { xtg_mfma_body<MT, NT>(op.x, vb, op.blocks, batch_lds, &last); return; }
-    GN_XTG_BODY(1, 1) GN_XTG_BODY(2, 1) GN_XTG_BODY(3, 1) GN_XTG_BODY(4, 1)
-    GN_XTG_BODY(1, 2) GN_XTG_BODY(2, 2) GN_XTG_BODY(3, 2) GN_XTG_BODY(4, 2)
+    GN_XTG_TILES(GN_XTG_BODY)
 #undef GN_XTG_BODY
-}
-
-thread_local bool batch_open = false;
-thread_local std::vector<BatchOp> batch_queue;
-
-void deep_shape(const GemmArgs& g, BatchOp& op) {
-    if (g.m <= 64) {
-        op.mt = g.m > 32 ? 4 : g.m > 16 ? 2 : 1; op.nt = 1;
-        op.gx = 1; op.blocks = (int)gn::ceil_div(g.n, 16);
-    } else {
-        op.mt = 1; op.nt = g.n > 16 ? 2 : 1;
-        op.gx = (int)gn::ceil_div(g.m, 16); op.blocks = op.gx;
-    }
-}
-
-gn_status launch_deep(const GemmArgs& g, hipStream_t st) {
-    BatchOp op;
-    deep_shape(g, op);
-    dim3 grid((unsigned)op.gx, (unsigned)(op.blocks / op.gx), 1);
-    if (op.mt == 4) k_gemm_deep<4, 1><<<grid, kDeepWaves * 64, 0, st>>>(g);
-    else if (op.mt == 2) k_gemm_deep<2, 1><<<grid, kDeepWaves * 64, 0, st>>>(g);
-    else if (op.nt == 2) k_gemm_deep<1, 2><<<grid, kDeepWaves * 64, 0, st>>>(g);
-    else k_gemm_deep<1, 1><<<grid, kDeepWaves * 64, 0, st>>>(g);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-gn_status launch_lds(const GemmArgs& g, hipStream_t st) {
-    const size_t lds_bytes = (size_t)gn::ceil_div(g.k, 16) * kColTiles * 64 * sizeof(f32x4);
-    const int row_tiles = (int)gn::ceil_div(g.m, 16);
-    dim3 lgrid((unsigned)std::min<int64_t>(gn::ceil_div(row_tiles, 4), 1024), (unsigned)gn::ceil_div(g.n, 16 * kColTiles), 1);
-    k_gemm_f32_lds<<<lgrid, 256, lds_bytes, st>>>(g, row_tiles);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-XtgArgs xtg_args(const float* x, int64_t ld_x, const float* g, int64_t ld_g, int64_t m, int k1, int k2, float* out, int64_t ld_out, void* workspace) {
-    float* partial = static_cast<float*>(workspace);
-    unsigned int* ticket = reinterpret_cast<unsigned int*>(static_cast<char*>(workspace) + (size_t)kXtgSlices * k1 * k2 * sizeof(float));
-    return XtgArgs{x, ld_x, g, ld_g, m, k1, k2, partial, ticket, out, ld_out};
-}
-int xtg_slices(int64_t m) {      // about two chunks of sixteen rows per wave; up to 40 of them are 32 (one level), more are up to 128 (two)
-    const int64_t want = gn::ceil_div(m, 16 * 16 * 2);
-    return (int)std::max<int64_t>(1, want <= 40 ? std::min<int64_t>(kXtgMfmaSlices, want) : std::min<int64_t>(kXtgMfmaMax, want));
-}
-
-gn_status launch_xtg_op(const BatchOp& op, hipStream_t st) {
-    const XtgArgs& a = op.x;
-    void* ws = a.partial;
-#define GN_XTG_CASE(MT, NT) if (op.mt == MT && op.nt == NT) return launch_xtg_mfma<MT, NT>(a.x, a.ld_x, a.g, a.ld_g, a.m, a.k1, a.k2, a.out, a.ld_out, ws, st)
-    GN_XTG_CASE(1, 1); GN_XTG_CASE(2, 1); GN_XTG_CASE(3, 1); GN_XTG_CASE(4, 1);
-    GN_XTG_CASE(1, 2); GN_XTG_CASE(2, 2); GN_XTG_CASE(3, 2); GN_XTG_CASE(4, 2);
-#undef GN_XTG_CASE
-    return gn::fail(GN_ERR_INVALID_ARG, "x^T g tile shape %d x %d", op.mt, op.nt);
-}
-
-gn_status flush_batch(hipStream_t st) {
-    std::vector<BatchOp> ops;
-    ops.swap(batch_queue);
-    for (size_t done = 0; done < ops.size();) {
-        const size_t take = std::min<size_t>(kBatchMax, ops.size() - done);
-        if (take == 1) {                                      // alone: its own kernel
-            const BatchOp& op = ops[done];
-            const gn_status rc = op.kind == 0 ? launch_deep(op.g, st) : op.kind == 1 ? launch_xtg_op(op, st) : launch_lds(op.g, st);
-            if (rc != GN_OK) return rc;
-            done += 1;
-            continue;
-        }
-        BatchTable tab;
-        tab.n = (int)take;
-        int blocks = 0;
-        size_t lds = 0;
-        for (size_t i = 0; i < take; ++i) {
-            tab.op[i] = ops[done + i];
-            tab.op[i].first = blocks;
-            blocks += tab.op[i].blocks;
-            lds = std::max(lds, (size_t)tab.op[i].lds);
-        }
-        if (lds > 64 * 1024) {
-            const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_dense_batch), 136 * 1024);   // (+ 4 static bytes)
-            if (ls != GN_OK) return ls;
-        }
-        k_dense_batch<<<blocks, 1024, lds, st>>>(tab);
-        GN_LAUNCH_CHECK();
-        done += take;
-    }
-    return GN_OK;
 }
 
 // 16 outputs per workgroup: 16 groups of threads add 16 slices each (independent loads), then the groups are added
@@ -1198,6 +1078,175 @@ __global__ __launch_bounds__(256) void k_xtg_fold(const float* __restrict__ part
     }
 }
 
+// ---- the host half: one launch function per kernel, each from the route of dense_route.hpp -----------------------------
+// (grid, tile and LDS size are the route's; the large-LDS opt-in, the launch and its check are here)
+using gn::route::GemmRoute;
+using gn::route::XtgRoute;
+using gn::route::kLdsSmall;
+
+gn_status launch_general(const GemmArgs& g, const GemmRoute& r, hipStream_t st) {
+    k_gemm_f32<<<dim3(r.grid_x, r.grid_y, r.grid_z), 256, 0, st>>>(g);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+gn_status launch_deep(const GemmArgs& g, const GemmRoute& r, hipStream_t st) {
+#define GN_DEEP_CASE(MT, NT)                                                                                           \
+    if (r.mt == MT && r.nt == NT) {                                                                                    \
+        k_gemm_deep<MT, NT><<<dim3(r.grid_x, r.grid_y, 1), kDeepWaves * 64, 0, st>>>(g);                               \
+        GN_LAUNCH_CHECK();                                                                                             \
+        return GN_OK;                                                                                                  \
+    }
+    GN_DEEP_TILES(GN_DEEP_CASE, GN_DEEP_CASE)
+#undef GN_DEEP_CASE
+    return gn::fail(GN_ERR_INVALID_ARG, "deep and narrow tile shape %d x %d", r.mt, r.nt);
+}
+
+gn_status launch_lds(const GemmArgs& g, const GemmRoute& r, hipStream_t st) {
+    k_gemm_f32_lds<<<dim3(r.grid_x, r.grid_y, 1), 256, r.lds, st>>>(g, r.row_tiles);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+template <int TERMS, int CT>
+gn_status launch_split_as(const GemmArgs& g, const GemmRoute& r, hipStream_t st) {
+#define GN_SPLIT_CASE(CH)                                                                                              \
+    {                                                                                                                  \
+        gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_gemm_split_lds<CH, TERMS, CT>), 160 * 1024); \
+        if (ls != GN_OK) return ls;                                                                                    \
+        k_gemm_split_lds<CH, TERMS, CT><<<dim3(r.grid_x, r.grid_y, 1), kSplitThreads, r.lds, st>>>(g, r.row_tiles, r.slab); \
+    }                                                                                                                  \
+    break
+    switch (r.ch) {
+        case 1: GN_SPLIT_CASE(1);
+        case 2: GN_SPLIT_CASE(2);
+        case 4: GN_SPLIT_CASE(4);
+        case 8: if constexpr (CT == 4) { GN_SPLIT_CASE(8); } else { GN_SPLIT_CASE(0); }
+        default: GN_SPLIT_CASE(0);
+    }
+#undef GN_SPLIT_CASE
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+gn_status launch_split(const GemmArgs& g, const GemmRoute& r, hipStream_t st) {
+    if (r.ct == 8) return r.terms == 2 ? launch_split_as<2, 8>(g, r, st) : launch_split_as<3, 8>(g, r, st);
+    return r.terms == 2 ? launch_split_as<2, 4>(g, r, st) : launch_split_as<3, 4>(g, r, st);
+}
+
+// The workspace of an x^T g: the slices' sums first, the one-launch kernel's ticket behind kXtgSlices of them.
+XtgArgs xtg_args(const float* x, int64_t ld_x, const float* g, int64_t ld_g, int64_t m, int k1, int k2, float* out, int64_t ld_out, void* workspace) {
+    float* partial = static_cast<float*>(workspace);
+    unsigned int* ticket = reinterpret_cast<unsigned int*>(static_cast<char*>(workspace) + (size_t)kXtgSlices * k1 * k2 * sizeof(float));
+    return XtgArgs{x, ld_x, g, ld_g, m, k1, k2, partial, ticket, out, ld_out};
+}
+
+gn_status launch_xtg_mfma(const XtgArgs& a, const XtgRoute& r, hipStream_t st) {
+#define GN_XTG_CASE(MT, NT)                                                                                            \
+    if (r.mt == MT && r.nt == NT) {                                                                                    \
+        if (r.lds > kLdsSmall) {                                                                                       \
+            const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_xtg_mfma<MT, NT>), 136 * 1024);   /* (+ 4 static bytes) */ \
+            if (ls != GN_OK) return ls;                                                                                \
+        }                                                                                                              \
+        k_xtg_mfma<MT, NT><<<r.slices, 1024, r.lds, st>>>(a);                                                          \
+        GN_LAUNCH_CHECK();                                                                                             \
+        return GN_OK;                                                                                                  \
+    }
+    GN_XTG_TILES(GN_XTG_CASE)
+#undef GN_XTG_CASE
+    return gn::fail(GN_ERR_INVALID_ARG, "x^T g tile shape %d x %d", r.mt, r.nt);   // (unreachable: k1 <= 64 and k2 <= 32 give mt <= 4, nt <= 2)
+}
+
+// the slices' sums of the two-launch kernels, added in slice order
+gn_status launch_xtg_fold(const XtgArgs& a, int slices, hipStream_t st) {
+    k_xtg_fold<<<(unsigned)gn::ceil_div(a.k1 * a.k2, 16), 256, 0, st>>>(a.partial, slices, a.k1 * a.k2, a.k2, a.out, a.ld_out);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+gn_status launch_xtg_wide(const XtgArgs& a, const XtgRoute& r, hipStream_t st) {
+#define GN_WIDE_CASE(TI, TJ)                                                                                           \
+    if (r.ti == TI && r.tj == TJ) {                                                                                    \
+        if (r.lds > kLdsSmall) {                                                                                       \
+            const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_xtg_wide<TI, TJ>), 136 * 1024);   \
+            if (ls != GN_OK) return ls;                                                                                \
+        }                                                                                                              \
+        k_xtg_wide<TI, TJ><<<r.slices, 1024, r.lds, st>>>(a);                                                          \
+        GN_LAUNCH_CHECK();                                                                                             \
+        return launch_xtg_fold(a, r.slices, st);                                                                       \
+    }
+    GN_WIDE_TILES(GN_WIDE_CASE)
+#undef GN_WIDE_CASE
+    return gn::fail(GN_ERR_INVALID_ARG, "wide x^T g tile count %d x %d", r.ti, r.tj);   // (unreachable: gn::route::xtg_wide admits these eight)
+}
+
+gn_status launch_xtg_partial(const XtgArgs& a, const XtgRoute& r, hipStream_t st) {
+    const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_xtg_partial), 160 * 1024);
+    if (ls != GN_OK) return ls;
+    k_xtg_partial<<<r.slices, 256, r.lds, st>>>(a.x, a.ld_x, a.g, a.ld_g, a.m, a.k1, a.k2, a.partial);
+    GN_LAUNCH_CHECK();
+    return launch_xtg_fold(a, r.slices, st);
+}
+
+// A queued product: its entry of the launch's table, and the route that made it (alone, it leaves through its own launch function).
+struct Queued { BatchOp op; GemmRoute gemm; XtgRoute xtg; };
+thread_local bool batch_open = false;
+thread_local std::vector<Queued> batch_queue;
+
+void queue_deep(const GemmArgs& g, const GemmRoute& r) {
+    Queued q{};
+    q.gemm = r;
+    q.op.kind = 0; q.op.g = g; q.op.mt = r.mt; q.op.nt = r.nt; q.op.lds = (int)r.lds; q.op.gx = r.gx; q.op.blocks = r.blocks;
+    batch_queue.push_back(q);
+}
+
+void queue_lds(const GemmArgs& g, const GemmRoute& r) {
+    Queued q{};
+    q.gemm = r;
+    q.op.kind = 2; q.op.g = g; q.op.mt = r.row_tiles; q.op.lds = (int)r.lds; q.op.gx = r.gx; q.op.blocks = r.blocks;
+    batch_queue.push_back(q);
+}
+
+void queue_xtg(const XtgArgs& a, const XtgRoute& r) {
+    Queued q{};
+    q.xtg = r;
+    q.op.kind = 1; q.op.x = a; q.op.mt = r.mt; q.op.nt = r.nt; q.op.lds = (int)r.lds; q.op.gx = 1; q.op.blocks = r.slices;
+    batch_queue.push_back(q);
+}
+
+gn_status flush_batch(hipStream_t st) {
+    std::vector<Queued> ops;
+    ops.swap(batch_queue);
+    for (size_t done = 0; done < ops.size();) {
+        const size_t take = std::min<size_t>(kBatchMax, ops.size() - done);
+        if (take == 1) {                                      // alone: its own kernel
+            const Queued& q = ops[done];
+            const gn_status rc = q.op.kind == 0 ? launch_deep(q.op.g, q.gemm, st) : q.op.kind == 1 ? launch_xtg_mfma(q.op.x, q.xtg, st) : launch_lds(q.op.g, q.gemm, st);
+            if (rc != GN_OK) return rc;
+            done += 1;
+            continue;
+        }
+        BatchTable tab;
+        tab.n = (int)take;
+        int blocks = 0;
+        size_t lds = 0;
+        for (size_t i = 0; i < take; ++i) {
+            tab.op[i] = ops[done + i].op;
+            tab.op[i].first = blocks;
+            blocks += tab.op[i].blocks;
+            lds = std::max(lds, (size_t)tab.op[i].lds);
+        }
+        if (lds > (size_t)kLdsSmall) {
+            const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_dense_batch), 136 * 1024);   // (+ 4 static bytes)
+            if (ls != GN_OK) return ls;
+        }
+        k_dense_batch<<<blocks, 1024, lds, st>>>(tab);
+        GN_LAUNCH_CHECK();
+        done += take;
+    }
+    return GN_OK;
+}
+
 extern "C" {
 
 gn_status gn_gemm_f32(const float* a, int64_t lda, int64_t stride_a, const int64_t* a_rows, int64_t a_table_rows,
@@ -1211,85 +1260,57 @@ gn_status gn_gemm_addend_f32(const float* a, int64_t lda, int64_t stride_a, cons
                              int64_t m, int64_t n, int64_t k, int64_t batch, const float* bias, const float* addend, int64_t ld_addend,
                              int flags, void* stream) {
     GN_REQUIRE(!addend || (batch == 1 && ld_addend >= n), "an addend goes with a single product and has rows of at least n floats");
-    const int relu = flags & GN_GEMM_RELU, fast = flags & GN_GEMM_ARITH_FAST;
-    const bool bt = (flags & GN_GEMM_B_TRANSPOSED) != 0, accumulate = (flags & GN_GEMM_ACCUMULATE) != 0, at = (flags & GN_GEMM_A_TRANSPOSED) != 0;
+    const bool bt = (flags & GN_GEMM_B_TRANSPOSED) != 0, at = (flags & GN_GEMM_A_TRANSPOSED) != 0;
     GN_REQUIRE(!at || !a_rows, "a row gather of a transposed A is not supported");
     GN_REQUIRE(m >= 0 && n >= 0 && k >= 0 && batch >= 0, "negative GEMM size");
     if (m == 0 || n == 0 || batch == 0) return GN_OK;
     GN_REQUIRE(a && b && c, "GEMM operand pointer is null");
     GN_REQUIRE(lda >= (at ? m : k) && ldb >= (bt ? k : n) && ldc >= n, "leading dimension smaller than the row length");
     GN_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "GEMM size out of range");
-    if (batch > 65535)           // a legal request beyond the grid's third dimension: the caller cuts it (as rgcn.hip does), not an argument error
-        return gn::fail(GN_ERR_UNSUPPORTED, "a batch of %lld products: one call takes 65535 at most", (long long)batch);
     GemmArgs g;
     g.a = a; g.lda = lda; g.stride_a = stride_a; g.a_rows = a_rows; g.a_table_rows = a_table_rows;
     g.b = b; g.ldb = ldb; g.stride_b = stride_b;
     g.c = c; g.ldc = ldc; g.stride_c = stride_c;
-    g.m = (int)m; g.n = (int)n; g.k = (int)k; g.bias = bias; g.relu = relu;
-    g.a_vec_ok = ((reinterpret_cast<uintptr_t>(a) & 15) == 0) && (lda % 4 == 0) && (stride_a % 4 == 0);
-    g.sbk = bt ? 1 : ldb; g.sbn = bt ? ldb : 1; g.accumulate = accumulate ? 1 : 0;
+    g.m = (int)m; g.n = (int)n; g.k = (int)k; g.bias = bias; g.relu = flags & GN_GEMM_RELU;
+    g.a_vec_ok = gn::aligned16(a) && (lda % 4 == 0) && (stride_a % 4 == 0);
+    g.sbk = bt ? 1 : ldb; g.sbn = bt ? ldb : 1; g.accumulate = (flags & GN_GEMM_ACCUMULATE) ? 1 : 0;
     g.addend = addend; g.ld_add = ld_addend;
-    g.c_vec_ok = (n % 4 == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(c) & 15) == 0) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0) &&
-                 (!addend || ((ld_addend % 4 == 0) && (reinterpret_cast<uintptr_t>(addend) & 15) == 0)) ? 1 : 0;
+    const bool c_rows4 = (n % 4 == 0) && (ldc % 4 == 0) && (!bias || gn::aligned16(bias));
+    g.c_vec_ok = c_rows4 && gn::aligned16(c) && (!addend || ((ld_addend % 4 == 0) && gn::aligned16(addend))) ? 1 : 0;
     g.sam = at ? 1 : lda; g.sak = at ? lda : 1;
-    if (flags & GN_GEMM_OUT_BF16) {
-        // c is a bf16 table: only the tall-skinny split kernel stores it (what a bf16-storage layer of the node-classification
-        // models needs); anything else is GN_ERR_UNSUPPORTED and the caller rounds a fp32 product with gn_cast_bf16
-        const bool split_path = batch == 1 && m >= 2048 && !a_rows && k >= 32 && k % 32 == 0 && g.a_vec_ok && !gn::fast_paths_disabled();
-        const bool vec = (n % 4 == 0) && (ldc % 4 == 0) && ((reinterpret_cast<uintptr_t>(c) & 7) == 0) && (!bias || (reinterpret_cast<uintptr_t>(bias) & 15) == 0);
-        if (!split_path || !vec || accumulate || addend || at)
-            return gn::fail(GN_ERR_UNSUPPORTED, "GN_GEMM_OUT_BF16: a tall-skinny product (m >= 2048, k %% 32 == 0) with n %% 4 == 0, 8-byte aligned rows, no accumulate / addend");
-        g.out_bf16 = 1; g.c_vec_ok = 1;
+
+    gn::route::GemmCall call;
+    call.m = m; call.n = n; call.k = k; call.batch = batch; call.flags = flags;
+    call.a_rows = a_rows != nullptr; call.a_vec_ok = g.a_vec_ok != 0; call.addend = addend != nullptr;
+    call.bf16_vec_ok = c_rows4 && (reinterpret_cast<uintptr_t>(c) & 7) == 0;          // (a bf16 table's rows of four are 8 bytes)
+    call.fast_disabled = gn::fast_paths_disabled();
+    call.join = batch_open && (flags & GN_GEMM_JOIN_BATCH);     // between gn_dense_batch_begin / _end: leaves with the others
+    call.compute_units = gn::compute_units();
+    const GemmRoute r = gn::route::gemm_route(call);
+
+    hipStream_t st = gn::as_stream(stream);
+    switch (r.kernel) {
+        case gn::route::Gemm::refused: break;
+        case gn::route::Gemm::deep:
+            if (r.queue) { queue_deep(g, r); return GN_OK; }
+            return launch_deep(g, r, st);
+        case gn::route::Gemm::lds:
+            if (r.queue) { queue_lds(g, r); return GN_OK; }
+            return launch_lds(g, r, st);
+        case gn::route::Gemm::split:
+            // (c as a bf16 table: what a bf16-storage layer of the node-classification models needs)
+            if (r.out_bf16) { g.out_bf16 = 1; g.c_vec_ok = 1; }
+            return launch_split(g, r, st);
+        case gn::route::Gemm::general: return launch_general(g, r, st);
     }
-    // (a TALL product with at most 32 columns - the general relational path's slab of rows times [basis ; root], 19,726 x 1,088 x 32 -
-    // is streamed by the tall-skinny split kernel below, not cut into K slices here: 43 -> 2x us for its 86 MB, round 6)
-    const bool want_split = (flags & GN_GEMM_SPLIT_KERNEL) != 0;   // (the caller's products must not change kernel - and bits - with their row count)
-    const bool tall_split = !at && (m >= 2048 || want_split) && k >= 32 && k % 32 == 0 && g.a_vec_ok;
-    if (batch == 1 && !a_rows && (m <= 64 || n <= 32) && !tall_split && (at || (k >= 256 && !gn::fast_paths_disabled()))) {
-        // deep and narrow (and every product with A given transposed): a workgroup per output tile, K over its waves
-        if (batch_open && (flags & GN_GEMM_JOIN_BATCH)) {         // between gn_dense_batch_begin / _end: leaves with the others
-            BatchOp op;
-            op.kind = 0; op.g = g; op.first = 0;
-            deep_shape(g, op);
-            op.lds = (int)((size_t)16 * op.mt * op.nt * 64 * sizeof(f32x4));
-            batch_queue.push_back(op);
-            return GN_OK;
-        }
-        return launch_deep(g, gn::as_stream(stream));
+    switch (r.why) {
+        case gn::route::Refusal::batch_limit:
+            return gn::fail(r.status, "a batch of %lld products: one call takes 65535 at most", (long long)batch);
+        case gn::route::Refusal::out_bf16:      // the caller rounds a fp32 product with gn_cast_bf16
+            return gn::fail(r.status, "GN_GEMM_OUT_BF16: a tall-skinny product (m >= 2048, k %% 32 == 0) with n %% 4 == 0, 8-byte aligned rows, no accumulate / addend");
+        default:
+            return gn::fail(r.status, "A given transposed: at most 64 rows or 32 columns of output (the deep and narrow kernel)");
     }
-    GN_REQUIRE(!at, "A given transposed: at most 64 rows or 32 columns of output (the deep and narrow kernel)");
-    const size_t lds_bytes = (size_t)gn::ceil_div(k, 16) * kColTiles * 64 * sizeof(f32x4);
-    const int row_tiles = (int)gn::ceil_div(m, 16);
-    if (batch == 1 && (m >= 2048 || want_split) && !a_rows && k >= 32 && k % 32 == 0 && g.a_vec_ok && !gn::fast_paths_disabled()) {
-        // tall-skinny, one shared B (as stored, or given transposed: the dx = g W^T of the wide layers' backward): the bf16 matrix
-        // instruction on split operands.  (Not queued in a dense batch: on 50,000 x 128 x 128 it takes a third of the fp32 instruction's time.)
-        const int terms = fast ? 2 : 3;
-        // a wave keeps 64 columns of a row tile, or 128 when the product is wider than 64 (A is then read once per 128)
-        const int ct = n > 64 ? 8 : 4;
-        // B in LDS: 2 bytes per term and element, at most 160 KB; a deeper K goes through in slabs
-        const int slab = (int)std::min<int64_t>(k / 32, std::min<int64_t>(8, (160 * 1024) / ((int64_t)ct * terms * 64 * sizeof(f32x4))));
-        const size_t split_bytes = (size_t)slab * ct * terms * 64 * sizeof(f32x4);
-        // one persistent workgroup of sixteen waves per compute unit (and column block)
-        dim3 sgrid((unsigned)std::min<int64_t>(row_tiles, gn::compute_units()), (unsigned)gn::ceil_div(n, 16 * ct), 1);
-        hipStream_t st = gn::as_stream(stream);
-        if (ct == 8) return fast ? launch_split<2, 8>(g, row_tiles, sgrid, split_bytes, slab, st) : launch_split<3, 8>(g, row_tiles, sgrid, split_bytes, slab, st);
-        return fast ? launch_split<2, 4>(g, row_tiles, sgrid, split_bytes, slab, st) : launch_split<3, 4>(g, row_tiles, sgrid, split_bytes, slab, st);
-    }
-    if (batch == 1 && m >= 256 && lds_bytes <= 64 * 1024 && !gn::fast_paths_disabled()) {      // tall-skinny on the fp32 instruction
-        if (batch_open && (flags & GN_GEMM_JOIN_BATCH) && !a_rows) {   // between gn_dense_batch_begin / _end: leaves with the others
-            BatchOp op;
-            op.kind = 2; op.g = g; op.first = 0; op.mt = row_tiles; op.nt = 0; op.lds = (int)lds_bytes;
-            op.gx = (int)std::min<int64_t>(gn::ceil_div(row_tiles, 16), 256);
-            op.blocks = op.gx * (int)gn::ceil_div(n, 16 * kColTiles);
-            batch_queue.push_back(op);
-            return GN_OK;
-        }
-        return launch_lds(g, gn::as_stream(stream));
-    }
-    dim3 grid((unsigned)gn::ceil_div(m, 64), (unsigned)gn::ceil_div(n, 16 * kColTiles), (unsigned)batch);
-    k_gemm_f32<<<grid, 256, 0, gn::as_stream(stream)>>>(g);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
 }
 
 gn_status gn_merge_f32(float* dst, int64_t ld_dst, const float* src, int64_t ld_src, const float* src2,
@@ -1348,9 +1369,7 @@ gn_status gn_class_scores_f32(const float* z, int64_t ld_z, int64_t table_rows, 
 
 
 int gn_xtg_wide_supported(int64_t m, int64_t k1, int64_t k2) {
-    if (gn::fast_paths_disabled() || m < 4096 || k1 < 64 || k2 < 32 || k1 % 64 != 0 || k2 % 32 != 0 || k1 > 256 || k2 > 128) return 0;
-    const int64_t tiles = (k1 / 64) * (k2 / 32);
-    return tiles >= 2 && tiles <= 16 && 16 % tiles == 0 ? 1 : 0;
+    return gn::route::xtg_wide(m, k1, k2, gn::fast_paths_disabled()) ? 1 : 0;
 }
 
 size_t gn_xtg_workspace_bytes(int64_t k1, int64_t k2) {
@@ -1362,60 +1381,27 @@ gn_status gn_xtg_f32(const float* x, int64_t ld_x, const float* g, int64_t ld_g,
                      int64_t ld_out, void* workspace, size_t workspace_bytes, int flags, void* stream) {
     GN_REQUIRE(m >= 0 && k1 >= 0 && k2 >= 0, "negative size");
     if (k1 == 0 || k2 == 0) return GN_OK;
-    const bool wide = gn_xtg_wide_supported(m, k1, k2) != 0;
-    if (k1 * k2 > 4096 && !wide)
+    gn::route::XtgCall call;
+    call.m = m; call.k1 = k1; call.k2 = k2; call.flags = flags;
+    call.ws_aligned4 = (reinterpret_cast<uintptr_t>(workspace) & 3) == 0;
+    call.fast_disabled = gn::fast_paths_disabled();
+    call.join = batch_open && (flags & GN_XTG_JOIN_BATCH);
+    call.compute_units = gn::compute_units();
+    const XtgRoute r = gn::route::xtg_route(call);
+    if (r.kernel == gn::route::Xtg::unsupported)
         return gn::fail(GN_ERR_UNSUPPORTED, "x^T g: %lld x %lld outputs (at most 4096, or a wide product: gn_xtg_wide_supported)", (long long)k1, (long long)k2);
     GN_REQUIRE(out && ld_out >= k2, "output pointer is null or its leading dimension too small");
     GN_REQUIRE(m == 0 || (x && g && ld_x >= k1 && ld_g >= k2), "operand pointer is null or a leading dimension too small");
     GN_REQUIRE(workspace && workspace_bytes >= gn_xtg_workspace_bytes(k1, k2), "workspace too small: need %zu bytes",
                gn_xtg_workspace_bytes(k1, k2));
+    const XtgArgs a = xtg_args(x, ld_x, g, ld_g, m, (int)k1, (int)k2, out, ld_out, workspace);
     hipStream_t st = gn::as_stream(stream);
-    if (wide) {
-        // all tiles of a row slice in one workgroup, then the fold (two launches whatever the width; never queued in a batch)
-        const int ti = (int)(k1 / 64), tj = (int)(k2 / 32), wpt = 16 / (ti * tj);
-        const int64_t chunks = gn::ceil_div(m, 16);
-        const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(kXtgSlices, gn::compute_units()), chunks / (2 * wpt)));
-        const XtgArgs a = {x, ld_x, g, ld_g, m, (int)k1, (int)k2, static_cast<float*>(workspace), nullptr, out, ld_out};
-        const size_t lds = wpt > 1 ? (size_t)16 * 8 * 64 * sizeof(f32x4) : 0;
-#define GN_WIDE_CASE(TI, TJ)                                                                                              \
-        if (ti == TI && tj == TJ) {                                                                                       \
-            if (lds > 64 * 1024) { const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(k_xtg_wide<TI, TJ>), 136 * 1024); if (ls != GN_OK) return ls; } \
-            k_xtg_wide<TI, TJ><<<slices, 1024, lds, st>>>(a);                                                             \
-        }
-        GN_WIDE_CASE(1, 2) GN_WIDE_CASE(2, 1) GN_WIDE_CASE(2, 2) GN_WIDE_CASE(1, 4) GN_WIDE_CASE(4, 1) GN_WIDE_CASE(2, 4) GN_WIDE_CASE(4, 2) GN_WIDE_CASE(4, 4)
-#undef GN_WIDE_CASE
-        GN_LAUNCH_CHECK();
-        k_xtg_fold<<<(unsigned)gn::ceil_div(k1 * k2, 16), 256, 0, st>>>(static_cast<const float*>(workspace), slices, (int)(k1 * k2), (int)k2, out, ld_out);
-        GN_LAUNCH_CHECK();
-        return GN_OK;
-    }
-    if (m > 0 && k1 <= 64 && k2 <= 32 && (flags & GN_XTG_TICKET_ZEROED) && (reinterpret_cast<uintptr_t>(workspace) & 3) == 0 &&
-        !gn::fast_paths_disabled()) {
-        const int mt = (int)gn::ceil_div(k1, 16), nt = (int)gn::ceil_div(k2, 16);
-        bool ws_free = true;                                  // a queued product owns its workspace until the batch has left
-        for (const BatchOp& q : batch_queue) ws_free = ws_free && !(q.kind == 1 && q.x.partial == workspace);
-        if (batch_open && (flags & GN_XTG_JOIN_BATCH) && ws_free) {
-            BatchOp op;
-            op.kind = 1; op.mt = mt; op.nt = nt; op.first = 0; op.gx = 1; op.blocks = xtg_slices(m);
-            op.lds = (int)((size_t)16 * mt * nt * 64 * sizeof(f32x4));
-            op.x = xtg_args(x, ld_x, g, ld_g, m, (int)k1, (int)k2, out, ld_out, workspace);
-            batch_queue.push_back(op);
-            return GN_OK;
-        }
-#define GN_XTG_CASE(MT, NT) if (mt == MT && nt == NT) return launch_xtg_mfma<MT, NT>(x, ld_x, g, ld_g, m, (int)k1, (int)k2, out, ld_out, workspace, st)
-        GN_XTG_CASE(1, 1); GN_XTG_CASE(2, 1); GN_XTG_CASE(3, 1); GN_XTG_CASE(4, 1);
-        GN_XTG_CASE(1, 2); GN_XTG_CASE(2, 2); GN_XTG_CASE(3, 2); GN_XTG_CASE(4, 2);
-#undef GN_XTG_CASE
-    }
-    const int slices = (int)std::max<int64_t>(1, std::min<int64_t>(kXtgSlices, gn::ceil_div(m, 16)));
-    const size_t lds = (size_t)kXtgMaxRows * (k1 + 1 + k2) * sizeof(float);
-    { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_xtg_partial), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
-    k_xtg_partial<<<slices, 256, lds, st>>>(x, ld_x, g, ld_g, m, (int)k1, (int)k2, static_cast<float*>(workspace));
-    GN_LAUNCH_CHECK();
-    k_xtg_fold<<<(unsigned)gn::ceil_div(k1 * k2, 16), 256, 0, st>>>(static_cast<const float*>(workspace), slices, (int)(k1 * k2), (int)k2,
-                                                                  out, ld_out);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
+    if (r.kernel == gn::route::Xtg::wide) return launch_xtg_wide(a, r, st);
+    if (r.kernel == gn::route::Xtg::partial) return launch_xtg_partial(a, r, st);
+    bool ws_free = true;                                  // a queued product owns its workspace until the batch has left
+    for (const Queued& q : batch_queue) ws_free = ws_free && !(q.op.kind == 1 && q.op.x.partial == workspace);
+    if (r.queue && ws_free) { queue_xtg(a, r); return GN_OK; }
+    return launch_xtg_mfma(a, r, st);
 }
 
 gn_status gn_dense_batch_begin(void) {

@@ -54,7 +54,7 @@ Guard by guard (csrc line numbers as of ABI 159; "formula": the size is found by
   rgcn.hip:179-181         relation slabs of 32768                           test_relational_table_path_relation_slabs[32768|32769]
   plan.hip:459             ELL rows <= 2^20                                  test_short_row_gather_at_2_to_the_20_rows
   aggregate.cuh:828        LDS-table short-row gather, rows >= 65536         test_plain_sum_at_65536_rows[65535|65536] (no query: parity only)
-  gemm.hip:1221            batch <= 65535                                    test_dense_batch_limit
+  dense_route.hpp:66       batch <= 65535                                    test_dense_batch_limit
   adam.hip:35,94           64 tensors per launch; alignment                  test_adam_tensor_counts_and_update
   class_metrics.hip:23     1024 classes                                      C = 1025 is refused in tests/test_class_metrics_host.py already
   metrics.hip              4096 scores per chunk                             tests/test_gpu_parity.py (4096 / 4097) already

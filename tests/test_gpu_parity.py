@@ -1495,6 +1495,17 @@ def test_independent_products_in_one_launch(gpu):
         single = torch.full((R, B), float("nan"), device=gpu)
         _hip.gemm(dw, basis, single, b_transposed=True, join_batch=True)
     assert torch.equal(single, alone[1])
+    # ... of each other kind too: the tall-skinny fp32 product (k % 32 != 0 keeps it off the split kernel) and the x^T g
+    ta, tb = torch.randn(256, 48, generator=gen).to(gpu), torch.randn(48, 64, generator=gen).to(gpu)
+    xx, gg = torch.randn(600, 64, generator=gen).to(gpu), torch.randn(600, 32, generator=gen).to(gpu)
+    tall = _hip.gemm(ta, tb, torch.full((256, 64), float("nan"), device=gpu))
+    with _hip.dense_batch(gpu):
+        tall_single = _hip.gemm(ta, tb, torch.full((256, 64), float("nan"), device=gpu), join_batch=True)
+    assert torch.equal(tall_single, tall) and bool(torch.isfinite(tall).all())
+    xtg = _hip.xtg(xx, gg)
+    with _hip.dense_batch(gpu):
+        xtg_single = _hip.xtg(xx, gg, join_batch=True)
+    assert torch.equal(xtg_single, xtg) and bool(torch.isfinite(xtg).all())
     with pytest.raises(ValueError):
         _hip.check(_hip.load().gn_dense_batch_end(None))      # no open batch
     with _hip.dense_batch(gpu):
