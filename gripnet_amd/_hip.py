@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 160                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 161                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -1464,7 +1464,8 @@ def metrics_plan(range_list, device):
 
 def link_metrics(pos_score, neg_score, range_list):
     """(auprc, auroc, ap), each a float64 [R] tensor on the GPU: scikit-learn's three link-prediction
-    metrics for every relation block at once (reference: one sklearn call per relation and epoch).  Asynchronous."""
+    metrics for every relation block at once (reference: one sklearn call per relation and epoch).  Asynchronous.
+    Scores are compared as fp32 values, so -0.0 and +0.0 tie; NaN and +-inf are the caller's to exclude (scikit-learn raises on them)."""
     require_gpu(pos_score, neg_score)
     pos = pos_score.detach().to(torch.float32).contiguous()
     neg = neg_score.detach().to(torch.float32).contiguous()

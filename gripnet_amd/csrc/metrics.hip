@@ -22,6 +22,7 @@
 //   4. k_metric_fold: a wave per relation adds its tiles' sums in tile order.  Bitwise reproducible, no atomics.
 // What depends on the range list only (segments, chunk / tile maps) is a PLAN (gn_link_metrics_plan_*): built once per
 // list, a planned call is asynchronous and makes 4 + rounds launches.
+// Scores are ordered as fp32 VALUES: -0.0 and +0.0 are one tied value (their bit patterns differ), denormals stay distinct.
 #include "common.h"
 
 #include <algorithm>
@@ -37,7 +38,8 @@ constexpr int kTileThreads = 256;
 size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
 __device__ __forceinline__ uint32_t descending_bits(float x) {
-    const uint32_t u = __float_as_uint(x);
+    const uint32_t b = __float_as_uint(x);
+    const uint32_t u = b == 0x80000000u ? 0u : b;                      // -0.0 ties with +0.0 (a test of the bits: no denormal mode can touch it)
     const uint32_t asc = (u & 0x80000000u) ? ~u : (u | 0x80000000u);   // monotone in x
     return ~asc;
 }

@@ -219,7 +219,8 @@ def device_negative_sampler(pos_edge_index: torch.Tensor, num_nodes: int, range_
 
 def relation_metrics(pos_score: torch.Tensor, neg_score: torch.Tensor, range_list):
     """Per-relation (auprc, auroc, ap) on the GPU, float64 [R] each: what the reference's epoch loop computes
-    with one `auprc_auroc_ap` call per relation (GripNet-pose.py:148-160).
+    with one `auprc_auroc_ap` call per relation (GripNet-pose.py:148-160).  Scores are compared as fp32 values, so -0.0 and
+    +0.0 tie; NaN and +-inf are the caller's to exclude (scikit-learn raises on them).
 
     The metrics are where an epoch synchronises anyway, so this is also where an out-of-range id seen by the decoder
     kernels since the last check becomes the reference's IndexError (the kernels write NaN scores and set a flag; see

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 160 /* 0.1.54 */
+#define GN_VERSION 161 /* 0.1.55 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -681,7 +681,8 @@ GN_API gn_status gn_link_loss_backward_f32(const float* pos_score, int64_t num_p
  * each, segmented by the same range_list ([R,2] on the host).  out is [3, R] float64 on the device:
  * row 0 area under the precision-recall curve (trapezoid, with the point recall 0 / precision 1),
  * row 1 ROC AUC, row 2 average precision, per relation, with scikit-learn's treatment of tied scores;
- * NaN for a relation without edges. */
+ * NaN for a relation without edges.  Scores are compared as fp32 values: -0.0 and +0.0 tie, denormals stay distinct;
+ * NaN and +-inf scores are the caller's to exclude (scikit-learn raises on them). */
 typedef struct gn_link_metrics_plan gn_link_metrics_plan;
 /* What depends on the range list only (the (relation, class) segments of the two score vectors, their chunk and tile maps):
  * built once per list (synchronises `stream` once); a planned call is asynchronous - chunk sort in LDS, merge rounds for the
