@@ -217,6 +217,7 @@ struct DmClassArgs {
     const uint32_t* packed; const uint32_t* own; const uint32_t* mirror; const uint32_t* rel; const int32_t* wg;
     float* out; int c0; int sigmoid, first_launch, last_launch;
     int walks;                 // batch ranges per workgroup: an XCD's workgroups walk its position sub-ranges one after the other
+    int dma;                   // the LDS image is a straight byte copy of z rows and D rows: filled by LDS-DMA (class_dma_piece)
 };
 
 // One wave step: quad q scores the pair of slot 4 q + S.  J 16-byte chunks per lane (lane l4 of the quad holds chunks
@@ -258,6 +259,27 @@ __device__ __forceinline__ void class_step(const char* __restrict__ lds, uint32_
         bcc = dpp_add<0x4E>(bcc);
         if (l4 == S) res2 = bcc;
     }
+}
+
+// One 1 KB piece of a class's LDS image - the rows of its first range, the rows of its second range, the relation rows of D,
+// back to back - by LDS-DMA: one wave instruction, the destination wave-uniform and 1 KB aligned (as gcn_blocked.hip and
+// rgcn_pair.hip use it), the source per lane.  A lane finds its source from its byte offset in the image, so a piece may
+// straddle two ranges, or the table and D; lanes outside [lo, end) are switched off.  Only where the image is a byte copy
+// of whole rows of z (RB bytes a row in memory and in LDS, column 0 first).
+template <int RB>
+__device__ __forceinline__ void class_dma_piece(float4* lds4, int p, int lane, const char* z0, const char* z1, uint32_t t0,
+                                                uint32_t t, const char* d0, int64_t ld_d_bytes, uint32_t lo, uint32_t end) {
+    const uint32_t o = (uint32_t)p * 1024u + (uint32_t)lane * 16u;
+    const char* src;
+    if (o < t) {
+        src = o < t0 ? z0 + o : z1 + (o - t0);
+    } else {
+        const uint32_t od = o - t, r = od / (uint32_t)RB;
+        src = d0 + (int64_t)r * ld_d_bytes + (od - r * (uint32_t)RB);
+    }
+    if (o >= lo && o < end)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)(lds4 + (size_t)p * 64), 16, 0, 0);
 }
 
 template <int J, int J1>
@@ -304,35 +326,92 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
         uint32_t rw0 = rel[2 * b], rw1 = rel[2 * (b + kStep)];
         uint32_t o0 = own[b * 64u], o1 = own[(b + kStep) * 64u];
         uint32_t m0 = last ? mir[b * 64u] : kNoMirror, m1 = last ? mir[(b + kStep) * 64u] : kNoMirror;
-        if (walk == 0) {
-            // the class's rows, whole: eight 16-byte loads in flight per thread; every workgroup starts at its own offset
-            const int total = rows * ROW4;
-            const int rot = (int)((blockIdx.x * 977u) % (unsigned)total);
-            for (int base = 0; base < total; base += 8 * kThreads) {
-                float4 v[8];
-                int at[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    int i = min(base + k * kThreads + tid, total - 1) + rot;
-                    i = i < total ? i : i - total;
-                    const int row = i / ROW4, c4 = i - row * ROW4;
-                    const int grow = row < r0c ? r0s + row : r1s + (row - r0c);
-                    at[k] = row * STR4 + c4;
-                    v[k] = *reinterpret_cast<const float4*>(a.z + (int64_t)grow * a.ld_z + a.c0 + 4 * c4);
+        bool dma = false;
+        if constexpr (STR4 == ROW4) dma = a.dma != 0;
+        if (dma) {
+            if constexpr (STR4 == ROW4) {
+                // The LDS image is a byte copy of the class's rows and of the range's relation rows of D: every 1 KB piece of
+                // it is requested by LDS-DMA, back to back behind the index words above - ONE memory round trip where the
+                // register-staged fill below has two rounds of rows and then D (and, as compiled, a wait behind every load).  Order: the first block's pieces and D's
+                // first (all that a pair inside the first block needs), then the second block's; inside each set the
+                // workgroup starts at its own piece and the waves take turns.
+                constexpr int RB = ROW4 * 16;
+                const char* z0 = reinterpret_cast<const char*>(a.z) + (int64_t)r0s * RB;
+                const char* z1 = reinterpret_cast<const char*>(a.z) + (int64_t)r1s * RB;
+                const char* d0 = reinterpret_cast<const char*>(a.d) + (int64_t)rel_lo * a.ld_d * 4;
+                const uint32_t t0 = (uint32_t)r0c * RB, t = (uint32_t)rows * RB, end = t + (uint32_t)nrel * RB;
+                const int np = (int)((end + 1023u) >> 10), pd = (int)(t >> 10);      // pieces; the first one that holds D
+                asm volatile("" ::: "memory");                                       // the index words are requested first
+                if (walk == 0) {
+                    const int p0 = (int)((t0 + 1023u) >> 10), pl = max(pd, p0);      // second block only: pieces [p0, pl)
+                    const int ne = p0 + np - pl, nl = pl - p0;
+                    const int rot_e = (int)((blockIdx.x * 977u) % (unsigned)max(ne, 1));
+                    const int rot_l = (int)((blockIdx.x * 977u) % (unsigned)max(nl, 1));
+                    for (int i = wave; i < ne; i += (int)kStep) {
+                        int e = i + rot_e;
+                        e = e < ne ? e : e - ne;
+                        class_dma_piece<RB>(lds4, e < p0 ? e : pl + (e - p0), lane, z0, z1, t0, t, d0, a.ld_d * 4, 0u, end);
+                    }
+                    for (int i = wave; i < nl; i += (int)kStep) {
+                        int l = i + rot_l;
+                        l = l < nl ? l : l - nl;
+                        class_dma_piece<RB>(lds4, p0 + l, lane, z0, z1, t0, t, d0, a.ld_d * 4, 0u, end);
+                    }
+#ifdef GN_STAMPS
+                    // diagnostic build: when had the first block and D landed?  Loads return in issue order, so this wave's
+                    // share of them is in once no more than its second-block pieces are outstanding.
+                    switch (wave < nl ? (nl - wave + (int)kStep - 1) / (int)kStep : 0) {
+                        case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+                        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
+                        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
+                        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
+                        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
+                        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
+                        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+                    }
+                    __builtin_amdgcn_s_barrier();
+                    GN_DM_STAMP(5);
+#endif
+                } else {
+                    __syncthreads();                              // every wave is done with the previous range's relation rows
+                    for (int p = pd + wave; p < np; p += (int)kStep)
+                        class_dma_piece<RB>(lds4, p, lane, z0, z1, t0, t, d0, a.ld_d * 4, t, end);
                 }
-#pragma unroll
-                for (int k = 0; k < 8; ++k)
-                    if (base + k * kThreads + tid < total) lds4[at[k]] = v[k];
+                // nothing reads the image before every piece - and with them the index words requested in front - is in
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();
             }
         } else {
-            __syncthreads();                                  // every wave is done with the previous range's relation rows
+            if (walk == 0) {
+                // the class's rows, whole: eight 16-byte loads in flight per thread; every workgroup starts at its own offset
+                const int total = rows * ROW4;
+                const int rot = (int)((blockIdx.x * 977u) % (unsigned)total);
+                for (int base = 0; base < total; base += 8 * kThreads) {
+                    float4 v[8];
+                    int at[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        int i = min(base + k * kThreads + tid, total - 1) + rot;
+                        i = i < total ? i : i - total;
+                        const int row = i / ROW4, c4 = i - row * ROW4;
+                        const int grow = row < r0c ? r0s + row : r1s + (row - r0c);
+                        at[k] = row * STR4 + c4;
+                        v[k] = *reinterpret_cast<const float4*>(a.z + (int64_t)grow * a.ld_z + a.c0 + 4 * c4);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k)
+                        if (base + k * kThreads + tid < total) lds4[at[k]] = v[k];
+                }
+            } else {
+                __syncthreads();                                  // every wave is done with the previous range's relation rows
+            }
+            // the relation rows of D this range's batches name
+            for (int i = tid; i < nrel * ROW4; i += kThreads) {
+                const int r = i / ROW4, c4 = i - r * ROW4;
+                dfill[i] = *reinterpret_cast<const float4*>(a.d + (int64_t)(rel_lo + r) * a.ld_d + a.c0 + 4 * c4);
+            }
+            __syncthreads();
         }
-        // the relation rows of D this range's batches name
-        for (int i = tid; i < nrel * ROW4; i += kThreads) {
-            const int r = i / ROW4, c4 = i - r * ROW4;
-            dfill[i] = *reinterpret_cast<const float4*>(a.d + (int64_t)(rel_lo + r) * a.ld_d + a.c0 + 4 * c4);
-        }
-        __syncthreads();
         if (walk == 0) GN_DM_STAMP(1);
         if (b < b_hi) {
             float cnext = (!first && o0 != kNoMirror) ? a.out[o0] : 0.f;
@@ -608,6 +687,8 @@ static gn_status plan_forward_cols(const gn_distmult_plan* plan, const float* z,
             c.packed = plan->cls_packed.p; c.own = plan->cls_own.p; c.mirror = plan->cls_mirror.p; c.rel = plan->cls_rel.p;
             c.wg = plan->cls_wg.p; c.out = out; c.c0 = (int)col_lo; c.sigmoid = apply_sigmoid;
             c.first_launch = col_lo == 0; c.last_launch = col_hi == num_features; c.walks = plan->cls_walks;
+            // (odd J: no padding between the LDS rows; z and d are 16-byte aligned and ld_d a multiple of four floats here)
+            c.dma = (J & 1) && ld_z == f && col_lo == 0;
             hipStream_t st = gn::as_stream(stream);
             switch (J * 8 + J1) {
                 case 5 * 8 + 3: return launch_class<5, 3>(plan, c, n, st);

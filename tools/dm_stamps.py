@@ -30,5 +30,9 @@ t0 = b[:, 0].min()
 names = ["entry", "ph0 barrier", "ph0 filled", "ph0 done", "ph1 barrier", "ph1 filled", "ph1 done"]
 if b[:, 4].max() == 0:                            # the row-class kernel stamps entry / table filled / wave 0 done / last wave done
     names = ["entry", "filled", "wave 0 done", "last wave done"]
+    if b[:, 5].max() > 0:                         # the LDS-DMA fill also stamps "first block + D landed" (column 5)
+        print("{:12s} mean {:6.2f} us  min {:6.2f}  max {:6.2f}".format("block 0 + D", (b[:, 5] - t0).mean(), (b[:, 5] - t0).min(), (b[:, 5] - t0).max()))
+        print("{:12s} mean {:6.2f} us  (block 0 + D landed -> all landed, per workgroup)".format("second block", (b[:, 1] - b[:, 5]).mean()))
+    print("{:12s} mean {:6.2f} us  (entry -> filled, per workgroup)".format("fill", (b[:, 1] - b[:, 0]).mean()))
 for k, n in enumerate(names):
     print("{:12s} mean {:6.1f} us  min {:6.1f}  max {:6.1f}".format(n, (b[:, k] - t0).mean(), (b[:, k] - t0).min(), (b[:, k] - t0).max()))
