@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "gripnet_hip.h"
-#include "host_layout.hpp"
+#include "host_parallel.hpp"
 
 namespace gn {
 
@@ -84,6 +84,18 @@ struct DevBuf {
             return hipSuccess;
         }
         return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+    }
+    // alloc(count), then the copy of `count` elements from the host queued on `st` (none when count is 0).  Does not wait:
+    // the caller synchronises the stream once, behind its last upload and before the host arrays die.
+    hipError_t upload(const void* host, size_t count, hipStream_t st) {
+        const hipError_t e = alloc(count);
+        if (e != hipSuccess || count == 0) return e;
+        return hipMemcpyAsync(p, host, count * sizeof(T), hipMemcpyHostToDevice, st);
+    }
+    template <typename C>
+    hipError_t upload(const C& host, hipStream_t st) {
+        static_assert(sizeof(*host.data()) == sizeof(T), "element sizes differ: use the pointer form");
+        return upload(host.data(), host.size(), st);
     }
     void release() {
         if (p) (void)hipFree(p);

@@ -27,6 +27,7 @@
 //   * a static edge list keeps what depends on the triples only in a gn_distmult_bwd_plan (end of this file): the
 //     pairing of an edge's two directions, the sort's offsets, the task lists.
 #include "common.h"
+#include "layout_decoder_bwd.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 

@@ -17,6 +17,7 @@
 //     scalar.
 // Same column phases and quad-per-edge arithmetic as the plan-less kernel: results are bitwise the same.
 #include "distmult_quad.cuh"
+#include "layout_decoder.hpp"
 
 #include <algorithm>
 #include <unordered_map>
@@ -519,16 +520,11 @@ gn_status build_distmult_plan(const V& hu, const V& hv, const V& hr, int64_t E,
         gn_layout::ClassLayout cl = gn_layout::build_class_layout(hu, hv, hr, scored, mirror_of, num_nodes, num_features, gn::compute_units());
         if (cl.ok) {
             GN_LAP(nullptr);
-            if ((he = p->cls_packed.alloc(cl.packed.size())) != hipSuccess) return bail(he);
-            if ((he = p->cls_own.alloc(cl.own.size())) != hipSuccess) return bail(he);
-            if ((he = p->cls_mirror.alloc(cl.mirror.size())) != hipSuccess) return bail(he);
-            if ((he = p->cls_rel.alloc(cl.rel32.size())) != hipSuccess) return bail(he);
-            if ((he = p->cls_wg.alloc(cl.wg.size())) != hipSuccess) return bail(he);
-            if ((he = hipMemcpyAsync(p->cls_packed.p, cl.packed.data(), cl.packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-            if ((he = hipMemcpyAsync(p->cls_own.p, cl.own.data(), cl.own.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-            if ((he = hipMemcpyAsync(p->cls_mirror.p, cl.mirror.data(), cl.mirror.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-            if ((he = hipMemcpyAsync(p->cls_rel.p, cl.rel32.data(), cl.rel32.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-            if ((he = hipMemcpyAsync(p->cls_wg.p, cl.wg.data(), cl.wg.size() * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
+            if ((he = p->cls_packed.upload(cl.packed, st)) != hipSuccess) return bail(he);
+            if ((he = p->cls_own.upload(cl.own, st)) != hipSuccess) return bail(he);
+            if ((he = p->cls_mirror.upload(cl.mirror, st)) != hipSuccess) return bail(he);
+            if ((he = p->cls_rel.upload(cl.rel32, st)) != hipSuccess) return bail(he);
+            if ((he = p->cls_wg.upload(cl.wg, st)) != hipSuccess) return bail(he);
             if ((he = hipStreamSynchronize(st)) != hipSuccess) return bail(he);
             GN_LAP("decoder: allocations + upload (sync)");
             GN_LAP(nullptr);
@@ -538,51 +534,15 @@ gn_status build_distmult_plan(const V& hu, const V& hv, const V& hr, int64_t E,
             return GN_OK;
         }
     }
-    // batches: 64 consecutive scored edges each, in list order; a batch's slots are dealt independently of the others
-    const int64_t NBs = gn::ceil_div((int64_t)scored.size(), 64);
-    std::vector<uint32_t> packed((size_t)NBs * 64), own((size_t)NBs * 64), mirror((size_t)NBs * 64);
-    std::vector<int32_t> batch_rel((size_t)NBs);
-    std::vector<uint16_t> rel16((size_t)NBs * 64);
-    gn::parallel_for(NBs, 64, [&](int64_t b0, int64_t b1) {
-        int slot_of_edge[64];
-        int64_t cu[64], cv[64], ce[64];
-        for (int64_t bi = b0; bi < b1; ++bi) {
-            const int count = (int)std::min<int64_t>(64, (int64_t)scored.size() - bi * 64);
-            for (int k = 0; k < count; ++k) { ce[k] = scored[bi * 64 + k]; cu[k] = hu[ce[k]]; cv[k] = hv[ce[k]]; }
-            gn_layout::deal_batch(cu, cv, count, slot_of_edge);
-            bool uniform = true;
-            for (int k = 1; k < count; ++k) uniform = uniform && hr[ce[k]] == hr[ce[0]];
-            const size_t s0 = (size_t)bi * 64;
-            batch_rel[bi] = uniform ? (int32_t)hr[ce[0]] : -1;
-            bool taken[64] = {false};
-            auto fill = [&](int s, int k) {
-                const int64_t e = ce[k];
-                packed[s0 + s] = (uint32_t)hu[e] | ((uint32_t)hv[e] << kNodeBits);
-                own[s0 + s] = (uint32_t)e;
-                rel16[s0 + s] = (uint16_t)hr[e];
-                mirror[s0 + s] = mirror_of[e] >= 0 ? (uint32_t)mirror_of[e] : kNoMirror;
-            };
-            for (int k = 0; k < count; ++k) { taken[slot_of_edge[k]] = true; fill(slot_of_edge[k], k); }
-            // a slot without an edge repeats the batch's first one: the same score into the same positions
-            for (int s = 0; s < 64; ++s)
-                if (!taken[s]) fill(s, 0);
-        }
-    });
-    const int64_t NB = (int64_t)batch_rel.size();
+    const gn_layout::PhaseLayout ph = gn_layout::build_phase_layout(hu, hv, hr, scored, mirror_of, kNodeBits);
+    const int64_t NB = (int64_t)ph.batch_rel.size();
     p->batches = NB;
-    if ((he = p->packed.alloc((size_t)NB * 64)) != hipSuccess) return bail(he);
-    if ((he = p->batch_rel.alloc((size_t)NB)) != hipSuccess) return bail(he);
-    if ((he = p->rel16.alloc((size_t)NB * 64)) != hipSuccess) return bail(he);
-    if ((he = p->mirror.alloc((size_t)NB * 64)) != hipSuccess) return bail(he);
-    if ((he = p->own.alloc((size_t)NB * 64)) != hipSuccess) return bail(he);
-    if (NB > 0) {
-        if ((he = hipMemcpyAsync(p->packed.p, packed.data(), (size_t)NB * 64 * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-        if ((he = hipMemcpyAsync(p->batch_rel.p, batch_rel.data(), (size_t)NB * sizeof(int32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-        if ((he = hipMemcpyAsync(p->rel16.p, rel16.data(), (size_t)NB * 64 * sizeof(uint16_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-        if ((he = hipMemcpyAsync(p->mirror.p, mirror.data(), (size_t)NB * 64 * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-        if ((he = hipMemcpyAsync(p->own.p, own.data(), (size_t)NB * 64 * sizeof(uint32_t), hipMemcpyHostToDevice, st)) != hipSuccess) return bail(he);
-        if ((he = hipStreamSynchronize(st)) != hipSuccess) return bail(he);     // host vectors go out of scope after this
-    }
+    if ((he = p->packed.upload(ph.packed, st)) != hipSuccess) return bail(he);
+    if ((he = p->batch_rel.upload(ph.batch_rel, st)) != hipSuccess) return bail(he);
+    if ((he = p->rel16.upload(ph.rel16, st)) != hipSuccess) return bail(he);
+    if ((he = p->mirror.upload(ph.mirror, st)) != hipSuccess) return bail(he);
+    if ((he = p->own.upload(ph.own, st)) != hipSuccess) return bail(he);
+    if (NB > 0 && (he = hipStreamSynchronize(st)) != hipSuccess) return bail(he);     // the host arrays go out of scope after this
     *out = p;
     return GN_OK;
 }
@@ -607,7 +567,7 @@ gn_status gn_distmult_plan_create(const int64_t* u, const int64_t* v, const int6
 #ifdef GN_LAYOUT_TIMES
     struct ExitLap { ~ExitLap() { GN_LAP("decoder: host vectors freed"); } } exit_lap;
 #endif
-    gn::ArenaHold arena;                                       // (before every host array of this build: host_layout.hpp)
+    gn::ArenaHold arena;                                       // (before every host array of this build: host_parallel.hpp)
     gn::RawVec<uint16_t> hu(E), hv(E), hr(E);
     GN_LAP("decoder: host vectors");
     if (E > 0) {

@@ -29,6 +29,7 @@
 // launch took 3.8 + 11.2 + 5.5 us per layer - the 10 MB of partial sums are flushed at one kernel boundary and read back
 // behind the next - against 19.2 / 14.7 us for the wave-per-row kernels.)
 #include "aggregate.cuh"
+#include "layout_blocked.hpp"
 
 #include <algorithm>
 #include <numeric>
@@ -466,7 +467,7 @@ extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t co
     const int R = std::max(1, std::min<int>(256 / groups, (int)gn::ceil_div(N, 64)));     // ranges of destination rows
 
     GN_LAP(nullptr);
-    gn::ArenaHold arena;                                       // (before every host array of this build: host_layout.hpp)
+    gn::ArenaHold arena;                                       // (before every host array of this build: host_parallel.hpp)
     std::vector<int32_t> rp(N + 1), col(nnz);
     GN_HIP(hipMemcpyAsync(rp.data(), plan->rowptr.p, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GN_HIP(hipMemcpyAsync(col.data(), plan->col.p, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -479,32 +480,23 @@ extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t co
     GN_LAP("blocked: host schedule");
     if (bl.failed) return gn::fail(GN_ERR_UNSUPPORTED, "internal: an edge was not scheduled");
     if (!bl.ok) return GN_OK;
-    std::vector<int32_t>& tile_off = bl.tile_off; std::vector<int32_t>& tile_rows = bl.tile_rows; std::vector<int32_t>& cell = bl.cell;
-    std::vector<float>& tile_dis = bl.tile_dis; gn::RawVec<uint16_t>& ids = bl.ids;
-    const int64_t iters_total = bl.iters_total;
     plan->blk_ok = 0;
     plan->blk_dis.release(); plan->blk_tile_off.release(); plan->blk_ids.release(); plan->blk_cell.release();
     plan->blk_tile_rows.release(); plan->blk_tile_dis.release(); plan->blk_table.release();
-    GN_HIP(plan->blk_dis.alloc(dis_host.size()));
-    GN_HIP(plan->blk_tile_off.alloc(tile_off.size()));
-    GN_HIP(plan->blk_tile_rows.alloc(tile_rows.size()));
-    GN_HIP(plan->blk_tile_dis.alloc(tile_dis.size()));
-    GN_HIP(hipMemcpyAsync(plan->blk_tile_dis.p, tile_dis.data(), tile_dis.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    GN_HIP(plan->blk_ids.alloc(ids.size() / 2));
-    GN_HIP(plan->blk_cell.alloc(cell.size()));
+    GN_HIP(plan->blk_dis.upload(dis_host, st));
+    GN_HIP(plan->blk_tile_off.upload(bl.tile_off, st));
+    GN_HIP(plan->blk_tile_rows.upload(bl.tile_rows, st));
+    GN_HIP(plan->blk_tile_dis.upload(bl.tile_dis, st));
+    GN_HIP(plan->blk_ids.upload(bl.ids.data(), bl.ids.size() / 2, st));           // (four 16-bit ids of a lane as two words)
+    GN_HIP(plan->blk_cell.upload(bl.cell, st));
     GN_HIP(plan->blk_table.alloc((size_t)rows_pad * cols));
     // rows beyond the last node stay zero for the life of the plan (padded id slots name row N): k_col_transform writes
     // zeros there, a table filled by another plan's gather (k_col_gather_next) is written at the nodes' rows only
     GN_HIP(hipMemsetAsync(plan->blk_table.p, 0, (size_t)rows_pad * cols * sizeof(float), st));
-    GN_HIP(hipMemcpyAsync(plan->blk_dis.p, dis_host.data(), dis_host.size() * sizeof(float), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->blk_tile_off.p, tile_off.data(), tile_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->blk_tile_rows.p, tile_rows.data(), tile_rows.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->blk_ids.p, ids.data(), ids.size() * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->blk_cell.p, cell.data(), cell.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     GN_HIP(hipStreamSynchronize(st));
     GN_LAP("blocked: upload");
     plan->blk_cols = (int)cols; plan->blk_cw = cw; plan->blk_rows = (int)rows_pad; plan->blk_cells = R;
-    plan->blk_iters = iters_total;
+    plan->blk_iters = bl.iters_total;
     plan->blk_ok = 1;
     return GN_OK;
 }

@@ -6,6 +6,7 @@
 // (stable sort), so per-destination sums run in the same order as the reference's sequential
 // scatter_add.  Plan construction is not on the steady-state path; it may synchronise.
 #include "common.h"
+#include "layout_rgcn_basis.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -634,26 +635,21 @@ gn_status gn_rgcn_plan_create_ex(const int64_t* src, const int64_t* dst, const i
     if (bad) return bail(gn::fail(GN_ERR_INDEX_RANGE, "edge_index holds a node id outside [0,%lld)", (long long)N));
     for (int64_t i = 0; i < N; ++i) p->max_row_nnz = std::max<int64_t>(p->max_row_nnz, rp[i + 1] - rp[i]);
     if (N > 0) {
-        // rows by in-degree, largest first (host_layout.hpp: the row pointers are on the host anyway)
+        // rows by in-degree, largest first (layout_rgcn_basis.hpp: the row pointers are on the host anyway)
         std::vector<int32_t> order;
         gn_layout::degree_order(rp, order, p->heavy_rows);
-        GN_TRY(p->row_order.alloc(N));
-        GN_TRY(hipMemcpyAsync(p->row_order.p, order.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        GN_TRY(p->row_order.upload(order, st));
         GN_TRY(hipStreamSynchronize(st));
     }
     {
-        // the general weight gradient's work items (host_layout.hpp)
+        // the general weight gradient's work items (layout_rgcn_basis.hpp)
         const gn_layout::RelDwItems dwl = gn_layout::build_rel_dw_items(ranges, lo, hi);
         p->n_dw_items = (int64_t)dwl.items.size() / 4;
         p->n_dw_parts = dwl.parts;
         p->n_dw_multi = (int64_t)dwl.multi.size() / 4;
         if (p->n_dw_items > 0) {
-            GN_TRY(p->dw_items.alloc(dwl.items.size()));
-            GN_TRY(hipMemcpyAsync(p->dw_items.p, dwl.items.data(), dwl.items.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            if (p->n_dw_multi > 0) {
-                GN_TRY(p->dw_multi.alloc(dwl.multi.size()));
-                GN_TRY(hipMemcpyAsync(p->dw_multi.p, dwl.multi.data(), dwl.multi.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-            }
+            GN_TRY(p->dw_items.upload(dwl.items, st));
+            if (p->n_dw_multi > 0) GN_TRY(p->dw_multi.upload(dwl.multi, st));
             GN_TRY(hipStreamSynchronize(st));
         }
     }

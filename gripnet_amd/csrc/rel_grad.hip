@@ -15,6 +15,7 @@
 // part to arrive adds in part order (write-through stores, atomic ticket, sc1 loads): no float atomics, the same bits every
 // run.
 #include "common.h"
+#include "layout_rel_grad.hpp"
 
 #include <type_traits>
 
@@ -352,17 +353,12 @@ gn_status gn_rel_grad_plan_create(const gn_graph_plan* sums, int64_t num_nodes, 
     p->num_nodes = num_nodes; p->num_relations = num_relations; p->edges = sums->nnz;
     p->groups = L.groups; p->scratch_slots = L.scratch_slots; p->entries = (int)(L.entry.size() / 4);
     p->units = L.units;
-    auto up = [&](auto& buf, const auto& v) -> hipError_t {
-        hipError_t e = buf.alloc(v.size());
-        if (e != hipSuccess || v.empty()) return e;
-        return hipMemcpyAsync(buf.p, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice, st);
-    };
-    hipError_t e = up(p->src, L.src);
-    if (e == hipSuccess) e = up(p->ids, L.ids);
-    if (e == hipSuccess) e = up(p->entry, L.entry);
-    if (e == hipSuccess) e = up(p->wave_cnt, L.wave_cnt);
-    if (e == hipSuccess) e = up(p->wg_off, L.wg_off);
-    if (e == hipSuccess) e = up(p->wave_u0, L.wave_u0);
+    hipError_t e = p->src.upload(L.src, st);
+    if (e == hipSuccess) e = p->ids.upload(L.ids, st);
+    if (e == hipSuccess) e = p->entry.upload(L.entry, st);
+    if (e == hipSuccess) e = p->wave_cnt.upload(L.wave_cnt, st);
+    if (e == hipSuccess) e = p->wg_off.upload(L.wg_off, st);
+    if (e == hipSuccess) e = p->wave_u0.upload(L.wave_u0, st);
     if (e == hipSuccess) e = p->scratch.alloc((size_t)std::max(1, L.scratch_slots) * kRelMaxOutputs);
     if (e == hipSuccess) e = p->ticket.alloc((size_t)num_relations);
     if (e == hipSuccess) e = hipMemsetAsync(p->ticket.p, 0, (size_t)num_relations * 4, st);

@@ -14,6 +14,7 @@
 // the root term, the bias and the activation.  Workspace: the slab (<= 256 MB) + the stacked weights, independent of
 // R and N; the edges come from the plan's destination-major list (key = relation * N + source), 4 bytes per edge.
 #include "common.h"
+#include "layout_rgcn_basis.hpp"
 
 namespace {
 

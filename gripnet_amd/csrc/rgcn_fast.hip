@@ -24,6 +24,7 @@
 // L2-resident.  The matrix-core time of (1), 2 N_tile x in x out flops per item at the fp32 MFMA
 // rate (256 flop/clk/CU), is the larger cost below ~10^4 edges per relation.
 #include "common.h"
+#include "layout_util.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -732,9 +733,7 @@ gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, co
     const int n_pieces = (int)piece_first.size();
     const int groups = std::min(groups0, std::max(n_pieces, 1));
     // longest-processing-time assignment of pieces to the persistent workgroups
-    std::vector<int> order(n_pieces);
-    std::iota(order.begin(), order.end(), 0);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return piece_cost[x] > piece_cost[y]; });
+    const std::vector<int> order = gn_layout::descending_order<int>(n_pieces, [&](int x) { return piece_cost[x]; });
     std::vector<std::vector<int32_t>> bins(groups);
     {
         std::vector<std::pair<int64_t, int>> heap;   // min-heap over (load, group)
@@ -828,10 +827,8 @@ gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, co
         wg_begin[gidx + 1] = (int32_t)work.size();
     }
 
-    GN_HIP(plan->wg_begin.alloc(groups + 1));
-    GN_HIP(plan->wg_items.alloc(work.size() * (sizeof(WorkDesc) / sizeof(int32_t))));
-    GN_HIP(hipMemcpyAsync(plan->wg_begin.p, wg_begin.data(), (groups + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->wg_items.p, work.data(), work.size() * sizeof(WorkDesc), hipMemcpyHostToDevice, st));
+    GN_HIP(plan->wg_begin.upload(wg_begin, st));
+    GN_HIP(plan->wg_items.upload(work.data(), work.size() * (sizeof(WorkDesc) / sizeof(int32_t)), st));
     GN_HIP(hipStreamSynchronize(st));       // host vectors go out of scope after this
     GN_LAP("  lds: emit + descriptors (sync)");
     plan->n_seg = n_items;

@@ -20,6 +20,7 @@
 // hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi in fp32 accumulators, dropping terms below 2^-24 of |p||x| - the same
 // order as fp32's own rounding.  GN_RGCN_ARITH_FAST keeps two terms and three products (<= 2^-16 per product).
 #include "common.h"
+#include "layout_rgcn_pair.hpp"
 
 #include <rocprim/rocprim.hpp>
 
@@ -764,13 +765,7 @@ gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const 
     plan->pair_ok = 0;
     const int64_t N = plan->num_nodes, R = plan->num_relations, E = plan->shard_edges;
     if (pair_disabled() || N < 1 || R < 1) return GN_OK;
-    int cus = 256;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-    }
+    const int cus = gn::compute_units();
     const int chunks = (int)gn::ceil_div(N, 32), kpad = chunks * 32;
     const int D = (int)gn::ceil_div(N, cus);
     if (D > kMaxD || chunks > kMaxChunks || chunks > 24) return GN_OK;            // up to 768 nodes
@@ -779,7 +774,7 @@ gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const 
     const int G = (int)std::min<int64_t>(N, cus);
 
     GN_LAP(nullptr);
-    gn::ArenaHold arena;                                       // (before every host array of this build: host_layout.hpp)
+    gn::ArenaHold arena;                                       // (before every host array of this build: host_parallel.hpp)
     Scratch tmp;
     GN_HIP(tmp.reserve((size_t)24 * (size_t)E + (size_t)4 * (size_t)N * kpad + (size_t)8 * (size_t)(N + R) + ((size_t)1 << 20)));
     int64_t* starts_dev;
@@ -805,9 +800,7 @@ gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const 
     GN_LAP("  pair: allocations + out-degrees (sync)");
     std::vector<int32_t> perm(kpad, (int32_t)N), kpos(N);
     {
-        std::vector<int32_t> order(N);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return outdeg[x] > outdeg[y]; });
+        const std::vector<int32_t> order = gn_layout::descending_order<int32_t>(N, [&](int32_t x) { return outdeg[x]; });
         for (int64_t k = 0; k < N; ++k) { perm[k] = order[k]; kpos[order[k]] = (int32_t)k; }
     }
     std::vector<int32_t> rp((size_t)N * kpad + 1, 0);
@@ -836,28 +829,18 @@ gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const 
     gn_layout::PairLayout pl = gn_layout::build_pair_layout(N, R, chunks, kpad, G, D, rp, rels, perm);
     GN_LAP("  pair: host layout");
     if (!pl.ok) return GN_OK;
-    gn::RawVec<uint32_t>& stream = pl.stream; std::vector<uint32_t>& first = pl.wave_first; std::vector<uint32_t>& desc = pl.desc;
-    std::vector<uint32_t>& wave_units = pl.wave_units; std::vector<uint32_t>& wave_desc = pl.wave_desc;
-    std::vector<int32_t>& wg_dst = pl.wg_dst;
-    const size_t total = (size_t)pl.blocks * 16;
-    GN_HIP(plan->pair_stream.alloc(stream.size()));
-    GN_HIP(plan->pair_wave_first.alloc(first.size()));
-    GN_HIP(plan->pair_desc.alloc(desc.size()));
-    GN_HIP(plan->pair_wave_units.alloc(wave_units.size()));
-    GN_HIP(plan->pair_wave_desc.alloc(wave_desc.size()));
-    GN_HIP(plan->pair_wg_dst.alloc(wg_dst.size()));
-    GN_HIP(hipMemcpyAsync(plan->pair_stream.p, stream.data(), stream.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->pair_wave_first.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->pair_desc.p, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->pair_wave_units.p, wave_units.data(), wave_units.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->pair_wave_desc.p, wave_desc.data(), wave_desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GN_HIP(hipMemcpyAsync(plan->pair_wg_dst.p, wg_dst.data(), wg_dst.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    GN_HIP(plan->pair_stream.upload(pl.stream, st));
+    GN_HIP(plan->pair_wave_first.upload(pl.wave_first, st));
+    GN_HIP(plan->pair_desc.upload(pl.desc, st));
+    GN_HIP(plan->pair_wave_units.upload(pl.wave_units, st));
+    GN_HIP(plan->pair_wave_desc.upload(pl.wave_desc, st));
+    GN_HIP(plan->pair_wg_dst.upload(pl.wg_dst, st));
     GN_HIP(hipStreamSynchronize(st));
     GN_LAP("  pair: upload (sync)");
     plan->pair_groups = G;
     plan->pair_d = D;
     plan->pair_chunks = chunks;
-    plan->pair_blocks = (int64_t)(total / 16);
+    plan->pair_blocks = pl.blocks;
     plan->pair_ok = 1;
     return GN_OK;
 }

@@ -1,11 +1,15 @@
-// Runs the pure host-side layout code of the plan builders (gripnet_amd/csrc/host_layout.hpp) on random inputs, once on one
+// Runs the pure host-side layout code of the plan builders (gripnet_amd/csrc/host_layout.hpp, the umbrella over
+// host_parallel.hpp, layout_util.hpp and one layout_*.hpp per plan) on random inputs, once on one
 // builder thread and once on sixteen, under the sanitizer this file was compiled with (make -C gripnet_amd/csrc SAN=asan
 // or SAN=tsan; tests/test_host_layout.py builds and runs both).  Checks that every edge lands in exactly one slot and that
 // a plan does not depend on the thread count.  No HIP, no GPU.
+// `digest` as the first argument prints an FNV-1a hash of every output array of every case instead, on 1 and on 16 threads:
+// two trees lay out the same plans when the program, built against each tree's host_layout.hpp, prints the same lines.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <initializer_list>
 #include <random>
 #include <thread>
 #include <utility>
@@ -28,11 +32,27 @@ void set_threads(int n) {
     setenv("GN_PLAN_THREADS", buf, 1);
 }
 
+// ---- digest mode -----------------------------------------------------------------------------------------------------
+bool g_digest = false;
+
+template <typename V>
+uint64_t fnv(const V& v) {
+    uint64_t h = 1469598103934665603ull;
+    for (const auto& x : v) h = (h ^ (uint64_t)x) * 1099511628211ull;
+    return h;
+}
+
+void emit(const char* name, std::initializer_list<uint64_t> hashes) {
+    if (!g_digest) return;
+    std::printf("%s", name);
+    for (uint64_t h : hashes) std::printf(" %016llx", (unsigned long long)h);
+    std::printf("\n");
+}
+
 // ---- decoder: pairing + row classes ------------------------------------------------------------------------------------
-gn_layout::ClassLayout decoder_case(int64_t n, int R, int64_t e_dir, int64_t features, unsigned seed, bool check,
-                                   int64_t window_bytes = gn_layout::kClsWindowBytes, bool expect_ok = true) {
+// a bidirectional list of R relations, relation r with e_dir / (r + 1) random pairs
+void decoder_list(int64_t n, int R, int64_t e_dir, unsigned seed, std::vector<int64_t>& hu, std::vector<int64_t>& hv, std::vector<int64_t>& hr) {
     std::mt19937_64 rng(seed);
-    std::vector<int64_t> hu, hv, hr;
     for (int r = 0; r < R; ++r) {
         const int64_t cnt = std::max<int64_t>(1, e_dir / (r + 1));
         std::vector<int64_t> u(cnt), v(cnt);
@@ -40,6 +60,12 @@ gn_layout::ClassLayout decoder_case(int64_t n, int R, int64_t e_dir, int64_t fea
         for (int64_t k = 0; k < cnt; ++k) { hu.push_back(u[k]); hv.push_back(v[k]); hr.push_back(r); }
         for (int64_t k = 0; k < cnt; ++k) { hu.push_back(v[k]); hv.push_back(u[k]); hr.push_back(r); }   // to_bidirection
     }
+}
+
+gn_layout::ClassLayout decoder_case(int64_t n, int R, int64_t e_dir, int64_t features, unsigned seed, bool check,
+                                   int64_t window_bytes = gn_layout::kClsWindowBytes, bool expect_ok = true) {
+    std::vector<int64_t> hu, hv, hr;
+    decoder_list(n, R, e_dir, seed, hu, hv, hr);
     const int64_t E = (int64_t)hu.size();
     gn::RawVec<int64_t> mirror_of;
     gn::RawVec<char> covered;
@@ -100,6 +126,123 @@ gn_layout::ClassLayout decoder_case(int64_t n, int R, int64_t e_dir, int64_t fea
     }
     return L;
 }
+
+// ---- decoder: column-phase batches ------------------------------------------------------------------------------------------
+#if __has_include("layout_decoder.hpp")
+using gn_layout::PhaseLayout;
+using gn_layout::build_phase_layout;
+#else
+// (a tree from before build_phase_layout: the same loop as it stood in build_distmult_plan, for the digest comparison)
+struct PhaseLayout {
+    std::vector<uint32_t> packed, own, mirror;
+    std::vector<int32_t> batch_rel;
+    std::vector<uint16_t> rel16;
+};
+template <typename V>
+PhaseLayout build_phase_layout(const V& hu, const V& hv, const V& hr, const gn::RawVec<int64_t>& scored,
+                               const gn::RawVec<int64_t>& mirror_of, int node_bits) {
+    const int kNodeBits = node_bits;
+    const uint32_t kNoMirror = gn_layout::kNoMirror;
+    const int64_t NBs = gn::ceil_div((int64_t)scored.size(), 64);
+    std::vector<uint32_t> packed((size_t)NBs * 64), own((size_t)NBs * 64), mirror((size_t)NBs * 64);
+    std::vector<int32_t> batch_rel((size_t)NBs);
+    std::vector<uint16_t> rel16((size_t)NBs * 64);
+    gn::parallel_for(NBs, 64, [&](int64_t b0, int64_t b1) {
+        int slot_of_edge[64];
+        int64_t cu[64], cv[64], ce[64];
+        for (int64_t bi = b0; bi < b1; ++bi) {
+            const int count = (int)std::min<int64_t>(64, (int64_t)scored.size() - bi * 64);
+            for (int k = 0; k < count; ++k) { ce[k] = scored[bi * 64 + k]; cu[k] = hu[ce[k]]; cv[k] = hv[ce[k]]; }
+            gn_layout::deal_batch(cu, cv, count, slot_of_edge);
+            bool uniform = true;
+            for (int k = 1; k < count; ++k) uniform = uniform && hr[ce[k]] == hr[ce[0]];
+            const size_t s0 = (size_t)bi * 64;
+            batch_rel[bi] = uniform ? (int32_t)hr[ce[0]] : -1;
+            bool taken[64] = {false};
+            auto fill = [&](int s, int k) {
+                const int64_t e = ce[k];
+                packed[s0 + s] = (uint32_t)hu[e] | ((uint32_t)hv[e] << kNodeBits);
+                own[s0 + s] = (uint32_t)e;
+                rel16[s0 + s] = (uint16_t)hr[e];
+                mirror[s0 + s] = mirror_of[e] >= 0 ? (uint32_t)mirror_of[e] : kNoMirror;
+            };
+            for (int k = 0; k < count; ++k) { taken[slot_of_edge[k]] = true; fill(slot_of_edge[k], k); }
+            for (int s = 0; s < 64; ++s)
+                if (!taken[s]) fill(s, 0);
+        }
+    });
+    PhaseLayout L;
+    L.packed.swap(packed); L.own.swap(own); L.mirror.swap(mirror); L.batch_rel.swap(batch_rel); L.rel16.swap(rel16);
+    return L;
+}
+#endif
+
+// Every position of the list is written exactly once, as a scored edge's own position or as its mirror (the empty slots of
+// a ragged last batch repeat the batch's first edge: the same score into the same positions); a batch's relation is -1 or
+// that of all its slots.  `slots`: deal_batch over the same batches, on its own.
+PhaseLayout phase_case(int64_t n, int R, int64_t e_dir, unsigned seed, std::vector<int>& slots) {
+    std::vector<int64_t> hu, hv, hr;
+    decoder_list(n, R, e_dir, seed, hu, hv, hr);
+    const int64_t E = (int64_t)hu.size();
+    gn::RawVec<int64_t> mirror_of;
+    gn::RawVec<char> covered;
+    gn_layout::pair_mirrors(hu, hv, hr, 13, mirror_of, covered);
+    const gn::RawVec<int64_t> scored = gn_layout::scored_edges(covered);
+    const int64_t S = (int64_t)scored.size(), NB = gn::ceil_div(S, 64);
+    slots.assign((size_t)NB * 64, -1);
+    for (int64_t b = 0; b < NB; ++b) {
+        int64_t cu[64], cv[64];
+        const int count = (int)std::min<int64_t>(64, S - b * 64);
+        for (int k = 0; k < count; ++k) { cu[k] = hu[scored[b * 64 + k]]; cv[k] = hv[scored[b * 64 + k]]; }
+        gn_layout::deal_batch(cu, cv, count, slots.data() + b * 64);
+        bool used[64] = {false};
+        for (int k = 0; k < count; ++k) { CHECK(slots[b * 64 + k] >= 0 && slots[b * 64 + k] < 64 && !used[slots[b * 64 + k]]); used[slots[b * 64 + k]] = true; }
+    }
+    const PhaseLayout L = build_phase_layout(hu, hv, hr, scored, mirror_of, 13);
+    CHECK((int64_t)L.batch_rel.size() == NB && L.packed.size() == (size_t)NB * 64 && L.own.size() == (size_t)NB * 64 &&
+          L.mirror.size() == (size_t)NB * 64 && L.rel16.size() == (size_t)NB * 64);
+    std::vector<int> written((size_t)E, 0), slots_of((size_t)E, 0);
+    for (int64_t b = 0; b < NB; ++b)
+        for (int s = 0; s < 64; ++s) {
+            const size_t at = (size_t)b * 64 + s;
+            const uint32_t e = L.own[at];
+            CHECK(e < (uint32_t)E && !covered[e]);
+            CHECK(L.packed[at] == ((uint32_t)hu[e] | (uint32_t)hv[e] << 13) && L.rel16[at] == (uint16_t)hr[e]);
+            CHECK(L.mirror[at] == (mirror_of[e] >= 0 ? (uint32_t)mirror_of[e] : gn_layout::kNoMirror));
+            CHECK(L.batch_rel[b] == -1 || L.batch_rel[b] == (int32_t)L.rel16[at]);
+            if (slots_of[e]++ > 0) { CHECK(b == NB - 1 && (int64_t)e == scored[(size_t)b * 64]); continue; }   // (an empty slot of the ragged batch)
+            written[e]++;
+            if (L.mirror[at] != gn_layout::kNoMirror) { CHECK(L.mirror[at] < (uint32_t)E); written[L.mirror[at]]++; }
+        }
+    for (int64_t e = 0; e < E; ++e) CHECK(written[e] == 1);
+    int64_t repeats = 0;
+    for (int64_t e = 0; e < E; ++e) repeats += std::max(0, slots_of[e] - 1);
+    CHECK(repeats == NB * 64 - S);
+    return L;
+}
+
+#if __has_include("layout_util.hpp")
+// largest_remainder_shares: the shares add up to the total, every live entry has its minimum, and an input whose minimum
+// shares already exceed the total ends (nobody can give one back) with the minimum for everybody.
+void shares_case() {
+    const double want[4] = {5.3, 0.0, 2.9, 7.8};
+    const std::vector<int> a = gn_layout::largest_remainder_shares(want, 4, 16, 1);
+    CHECK(a.size() == 4 && a[0] + a[1] + a[2] + a[3] == 16 && a[1] == 0 && a[0] >= 5 && a[2] >= 2 && a[3] >= 7);
+    const double skew[3] = {15.9, 0.05, 0.05};                    // the minimum of the small ones comes out of the large one
+    const std::vector<int> b = gn_layout::largest_remainder_shares(skew, 3, 16, 1);
+    CHECK(b[0] + b[1] + b[2] == 16 && b[1] >= 1 && b[2] >= 1);
+    const double tight[3] = {0.7, 0.7, 0.6};                     // three live entries, two to give: 1 + 1 + 1 > 2 and every share is 1
+    const std::vector<int> c = gn_layout::largest_remainder_shares(tight, 3, 2, 1);
+    CHECK(c[0] == 1 && c[1] == 1 && c[2] == 1);
+    const std::vector<int> none = gn_layout::largest_remainder_shares(want, 0, 16, 1);
+    CHECK(none.empty());
+    const double dead[2] = {0.0, 0.0};                           // nobody to give to
+    const std::vector<int> d = gn_layout::largest_remainder_shares(dead, 2, 4, 1);
+    CHECK(d[0] == 0 && d[1] == 0);
+}
+#else
+void shares_case() {}
+#endif
 
 // ---- relational layer: destination-major streams --------------------------------------------------------------------------
 gn_layout::PairLayout pair_case(int64_t N, int64_t R, int64_t E, unsigned seed, bool check) {
@@ -237,6 +380,7 @@ bool same(const V& a, const V& b) { return a == b; }
 // balance_batch64: a permutation of the batch, never more access cycles than the input order, close to the 32 of a perfect split
 void balance_case(unsigned seed) {
     std::mt19937 rng(seed);
+    std::vector<int> all_orders;
     for (int round = 0; round < 200; ++round) {
         uint8_t cls[64];
         const int skew = round % 5;                      // 0: uniform classes; else: one class rare / absent
@@ -250,18 +394,20 @@ void balance_case(unsigned seed) {
         int order[64], ident[64];
         for (int i = 0; i < 64; ++i) { order[i] = -1; ident[i] = i; }
         gn_layout::balance_batch64(cls, order);
+        all_orders.insert(all_orders.end(), order, order + 64);
         bool seen[64] = {false};
         for (int i = 0; i < 64; ++i) {
             if (order[i] < 0 || order[i] >= 64 || seen[order[i]]) { std::fprintf(stderr, "balance_batch64: not a permutation\n"); std::exit(1); }
             seen[order[i]] = true;
         }
         const int before = gn_layout::batch64_access_cycles(cls, ident), after = gn_layout::batch64_access_cycles(cls, order);
-        if (round < 5 && seed == 5) std::printf("balance_batch64 (class mix %d): %d -> %d LDS cycles per batch (32 = no conflict)\n", skew, before, after);
+        if (round < 5 && seed == 5 && !g_digest) std::printf("balance_batch64 (class mix %d): %d -> %d LDS cycles per batch (32 = no conflict)\n", skew, before, after);
         if (after > before || (skew == 0 && after > 56)) {
             std::fprintf(stderr, "balance_batch64: %d -> %d cycles (round %d)\n", before, after, round);
             std::exit(1);
         }
     }
+    emit("balance_batch64", {fnv(all_orders)});
 }
 
 // ---- relational layer of any size: degree order, weight-gradient items ----------------------------------------------------------
@@ -288,6 +434,7 @@ void general_case(int64_t N, int64_t R, int64_t E, unsigned seed) {
         if (i < heavy) CHECK(d > gn_layout::kBasisHeavyEdges);                             // the heavy rows lead the order
     }
     CHECK(heavy == heavy_ref);
+    emit("degree_order", {fnv(order), (uint64_t)heavy});
     // relation ranges (a hub relation, empty relations), the whole list and two shards' edge ranges
     std::vector<int64_t> ranges((size_t)(2 * R));
     int64_t at = 0;
@@ -302,6 +449,7 @@ void general_case(int64_t N, int64_t R, int64_t E, unsigned seed) {
     for (auto& c : cuts) {
         const gn_layout::RelDwItems L = gn_layout::build_rel_dw_items(ranges, c[0], c[1]);
         CHECK(L.ok && L.items.size() % 4 == 0 && L.multi.size() % 4 == 0);
+        emit("rel_dw_items", {fnv(L.items), fnv(L.multi), (uint64_t)L.parts});
         // the items tile [lo, hi) exactly, in order, inside their relation's range, at most kRelDwItemEdges edges each
         int64_t pos = c[0], slots = 0;
         for (size_t i = 0; i < L.items.size(); i += 4) {
@@ -318,7 +466,7 @@ void general_case(int64_t N, int64_t R, int64_t E, unsigned seed) {
     }
 }
 
-// After a fork the child has none of the parent's parked builder threads (host_layout.hpp, WorkerPool): its first parallel pass
+// After a fork the child has none of the parent's parked builder threads (host_parallel.hpp, WorkerPool): its first parallel pass
 // must make its own instead of waiting for threads that do not exist there.
 int fork_case() {
     set_threads(16);
@@ -338,25 +486,95 @@ int fork_case() {
     return 0;
 }
 
-int main(int argc, char** argv) {
-    if (argc > 1 && std::strcmp(argv[1], "fork") == 0) return fork_case();
+// The cases main() runs, each on 1 and on 16 threads.
+// (decoder: two giant relations; one relation; a long tail of small relations - more of them per workgroup than its D cache
+// holds: not taken, as before)
+const struct { int64_t n; int R; int64_t e; int64_t f; bool ok; } kDecoderCases[] = {
+    {645, 40, 20000, 80, true}, {200, 7, 3000, 80, true}, {645, 3, 50000, 48, true}, {30, 2, 5, 16, true},
+    {645, 200, 150000, 80, true}, {645, 2, 300000, 80, true}, {645, 1, 200000, 80, true}, {645, 964, 60000, 80, false}};
+const int64_t kWindowCases[] = {(int64_t)8 << 10, (int64_t)40 << 10};     // an XCD's position range walked in several sub-ranges
+const struct { int64_t n; int R; int64_t e; } kPhaseCases[] = {{645, 40, 20000}, {645, 7, 3000}, {30, 2, 5}};   // (the last: fewer than 64 scored edges)
+const struct { int64_t N, R, E; } kPairCases[] = {{645, 30, 60000}, {200, 5, 9000}, {1, 1, 300}, {300, 964, 20000}};
+const struct { int64_t N; int deg, R; } kBlockedCases[] = {{5000, 16, 32}, {700, 3, 11}, {19081, 38, 32}};
+const struct { int64_t n, R, E; int groups; } kRelGradCases[] = {{645, 40, 200000, 256}, {100, 7, 5000, 256}, {37, 3, 10, 8}, {300, 964, 60000, 64}};
+
+void general_cases() {
     balance_case(5);
     general_case(20000, 600, 300000, 21);
     general_case(50, 3, 40, 22);
     general_case(1, 1, 1500, 23);
-    // (two giant relations; one relation; a long tail of small relations - more of them per workgroup than its D cache holds: not
-    // taken, as before)
-    struct { int64_t n; int R; int64_t e; int64_t f; bool ok; } dec[] = {{645, 40, 20000, 80, true}, {200, 7, 3000, 80, true}, {645, 3, 50000, 48, true},
-                                                                     {30, 2, 5, 16, true}, {645, 200, 150000, 80, true}, {645, 2, 300000, 80, true},
-                                                                     {645, 1, 200000, 80, true}, {645, 964, 60000, 80, false}};
-    for (auto& c : dec) {
+}
+
+// One line per case: its name, then the hash of every output array (and of its scalars).
+void digest_all(int threads) {
+    set_threads(threads);
+    std::printf("threads %d\n", threads);
+    general_cases();
+    char name[96];
+    for (auto& c : kDecoderCases) {
+        const gn_layout::ClassLayout L = decoder_case(c.n, c.R, c.e, c.f, 7, true, gn_layout::kClsWindowBytes, c.ok);
+        std::snprintf(name, sizeof name, "decoder %lld/%d/%lld/%lld", (long long)c.n, c.R, (long long)c.e, (long long)c.f);
+        emit(name, {fnv(L.packed), fnv(L.own), fnv(L.mirror), fnv(L.rel32), fnv(L.wg), (uint64_t)L.ok, (uint64_t)L.groups, (uint64_t)L.walks, (uint64_t)L.batches});
+    }
+    for (int64_t window : kWindowCases) {
+        const gn_layout::ClassLayout L = decoder_case(645, 40, 20000, 80, 9, true, window);
+        std::snprintf(name, sizeof name, "window %lld", (long long)window);
+        emit(name, {fnv(L.packed), fnv(L.own), fnv(L.mirror), fnv(L.rel32), fnv(L.wg), (uint64_t)L.ok, (uint64_t)L.groups, (uint64_t)L.walks, (uint64_t)L.batches});
+    }
+    for (auto& c : kPhaseCases) {
+        std::vector<int> slots;
+        const PhaseLayout L = phase_case(c.n, c.R, c.e, 7, slots);
+        std::snprintf(name, sizeof name, "deal_batch %lld/%d/%lld", (long long)c.n, c.R, (long long)c.e);
+        emit(name, {fnv(slots)});
+        std::snprintf(name, sizeof name, "phase %lld/%d/%lld", (long long)c.n, c.R, (long long)c.e);
+        emit(name, {fnv(L.packed), fnv(L.own), fnv(L.mirror), fnv(L.batch_rel), fnv(L.rel16)});
+    }
+    for (auto& c : kPairCases) {
+        const gn_layout::PairLayout L = pair_case(c.N, c.R, c.E, 11, true);
+        std::snprintf(name, sizeof name, "pair %lld/%lld/%lld", (long long)c.N, (long long)c.R, (long long)c.E);
+        emit(name, {fnv(L.stream), fnv(L.wave_first), fnv(L.desc), fnv(L.wave_units), fnv(L.wave_desc), fnv(L.wg_dst), (uint64_t)L.blocks});
+    }
+    for (auto& c : kBlockedCases) {
+        const gn_layout::BlockedLayout L = blocked_case(c.N, c.deg, c.R, 13, true);
+        std::snprintf(name, sizeof name, "blocked %lld/%d/%d", (long long)c.N, c.deg, c.R);
+        std::vector<uint32_t> dis_bits(L.tile_dis.size());
+        std::memcpy(dis_bits.data(), L.tile_dis.data(), dis_bits.size() * sizeof(uint32_t));
+        emit(name, {fnv(L.tile_off), fnv(L.tile_rows), fnv(L.cell), fnv(dis_bits), fnv(L.ids), (uint64_t)L.iters_total});
+    }
+    for (auto& c : kRelGradCases) {
+        const gn_layout::RelGradLayout L = rel_grad_case(c.n, c.R, c.E, c.groups, 17, true);
+        std::snprintf(name, sizeof name, "rel_grad %lld/%lld/%lld/%d", (long long)c.n, (long long)c.R, (long long)c.E, c.groups);
+        emit(name, {fnv(L.src), fnv(L.ids), fnv(L.entry), fnv(L.wave_cnt), fnv(L.wg_off), fnv(L.wave_u0), (uint64_t)L.groups,
+                    (uint64_t)L.scratch_slots, (uint64_t)L.units});
+    }
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::strcmp(argv[1], "fork") == 0) return fork_case();
+    if (argc > 1 && std::strcmp(argv[1], "digest") == 0) {
+        g_digest = true;
+        digest_all(1);
+        digest_all(16);
+        return 0;
+    }
+    general_cases();
+    shares_case();
+    for (auto& c : kDecoderCases) {
         set_threads(1);
         gn_layout::ClassLayout a = decoder_case(c.n, c.R, c.e, c.f, 7, true, gn_layout::kClsWindowBytes, c.ok);
         set_threads(16);
         gn_layout::ClassLayout b = decoder_case(c.n, c.R, c.e, c.f, 7, true, gn_layout::kClsWindowBytes, c.ok);
         CHECK(same(a.packed, b.packed) && same(a.own, b.own) && same(a.mirror, b.mirror) && same(a.rel32, b.rel32) && same(a.wg, b.wg));
     }
-    // the builders' host arena (host_layout.hpp): the same plan with its large arrays out of the kept block - the first hold finds no
+    for (auto& c : kPhaseCases) {
+        std::vector<int> slots;
+        set_threads(1);
+        const PhaseLayout a = phase_case(c.n, c.R, c.e, 7, slots);
+        set_threads(16);
+        const PhaseLayout b = phase_case(c.n, c.R, c.e, 7, slots);
+        CHECK(same(a.packed, b.packed) && same(a.own, b.own) && same(a.mirror, b.mirror) && same(a.batch_rel, b.batch_rel) && same(a.rel16, b.rel16));
+    }
+    // the builders' host arena (host_parallel.hpp): the same plan with its large arrays out of the kept block - the first hold finds no
     // block (everything by malloc, the demand noted), the later ones are served from it; a second builder meanwhile gets malloc
     {
         set_threads(16);
@@ -382,13 +600,12 @@ int main(int argc, char** argv) {
             other.join();
         }
     }
-    for (int64_t window : {(int64_t)8 << 10, (int64_t)40 << 10}) {     // an XCD's position range walked in several sub-ranges
+    for (int64_t window : kWindowCases) {
         set_threads(16);
         gn_layout::ClassLayout w = decoder_case(645, 40, 20000, 80, 9, true, window);
         CHECK(w.walks == (window == ((int64_t)8 << 10) ? 8 : 3));
     }
-    struct { int64_t N, R, E; } pr[] = {{645, 30, 60000}, {200, 5, 9000}, {1, 1, 300}, {300, 964, 20000}};
-    for (auto& c : pr) {
+    for (auto& c : kPairCases) {
         set_threads(1);
         gn_layout::PairLayout a = pair_case(c.N, c.R, c.E, 11, true);
         set_threads(16);
@@ -396,16 +613,14 @@ int main(int argc, char** argv) {
         CHECK(same(a.stream, b.stream) && same(a.desc, b.desc) && same(a.wave_first, b.wave_first) && same(a.wave_units, b.wave_units) &&
               same(a.wave_desc, b.wave_desc) && same(a.wg_dst, b.wg_dst));
     }
-    struct { int64_t N; int deg, R; } bk[] = {{5000, 16, 32}, {700, 3, 11}, {19081, 38, 32}};
-    for (auto& c : bk) {
+    for (auto& c : kBlockedCases) {
         set_threads(1);
         gn_layout::BlockedLayout a = blocked_case(c.N, c.deg, c.R, 13, true);
         set_threads(16);
         gn_layout::BlockedLayout b = blocked_case(c.N, c.deg, c.R, 13, true);
         CHECK(same(a.ids, b.ids) && same(a.tile_off, b.tile_off) && same(a.tile_rows, b.tile_rows) && same(a.cell, b.cell));
     }
-    struct { int64_t n, R, E; int groups; } rg[] = {{645, 40, 200000, 256}, {100, 7, 5000, 256}, {37, 3, 10, 8}, {300, 964, 60000, 64}};
-    for (auto& c : rg) {
+    for (auto& c : kRelGradCases) {
         set_threads(1);
         gn_layout::RelGradLayout a = rel_grad_case(c.n, c.R, c.E, c.groups, 17, true);
         set_threads(16);
