@@ -5,12 +5,15 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "gripnet_hip.h"
@@ -49,6 +52,12 @@ inline gn_status fail(gn_status code, const char* fmt, ...) {
 
 #define GN_LAUNCH_CHECK() GN_HIP(hipGetLastError())
 
+#define GN_OK_OR_RETURN(call)           \
+    do {                                \
+        const gn_status _s = (call);    \
+        if (_s != GN_OK) return _s;     \
+    } while (0)
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -72,18 +81,44 @@ inline bool fast_paths_disabled() {
     return e && e[0] == '1';
 }
 
-// Device buffer owned by a plan.
+// Every device allocation of the library goes through these two, so that gn_device_blocks_live() counts exactly what the
+// plans (DevBuf) and their builders (Scratch) hold.
+inline std::atomic<int64_t>& device_blocks_live() {
+    static std::atomic<int64_t> live{0};
+    return live;
+}
+inline hipError_t device_malloc(void** p, size_t bytes) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) device_blocks_live().fetch_add(1, std::memory_order_relaxed);
+    return e;
+}
+inline void device_free(void* p) {
+    (void)hipFree(p);
+    device_blocks_live().fetch_sub(1, std::memory_order_relaxed);
+}
+
+// Device buffer owned by a plan (or by a scope): freed by its destructor, movable, not copyable.  A plan struct is destroyed
+// by `delete`, a create function holds the plan in a std::unique_ptr until it hands it out - no list of buffers anywhere.
 template <typename T>
 struct DevBuf {
     T* p = nullptr;
     size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+        return *this;
+    }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
+    // releases what the buffer held, then allocates `count` elements (nothing when count is 0)
     hipError_t alloc(size_t count) {
-        n = count;
-        if (count == 0) {
-            p = nullptr;
-            return hipSuccess;
-        }
-        return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+        release();
+        if (count == 0) return hipSuccess;
+        const hipError_t e = device_malloc(reinterpret_cast<void**>(&p), count * sizeof(T));
+        if (e == hipSuccess) n = count; else p = nullptr;
+        return e;
     }
     // alloc(count), then the copy of `count` elements from the host queued on `st` (none when count is 0).  Does not wait:
     // the caller synchronises the stream once, behind its last upload and before the host arrays die.
@@ -98,11 +133,13 @@ struct DevBuf {
         return upload(host.data(), host.size(), st);
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) device_free(p);
         p = nullptr;
         n = 0;
     }
 };
+static_assert(!std::is_copy_constructible<DevBuf<int32_t>>::value && std::is_move_constructible<DevBuf<int32_t>>::value,
+              "a DevBuf has one owner");
 
 // Scoped device scratch of a plan builder, carved out of a few large blocks: a builder asks for ten to twenty arrays, and a
 // hipMalloc / hipFree pair per array (the free waits for the device and unmaps) was a third of a relational plan's build
@@ -117,7 +154,7 @@ struct Scratch {
     Scratch& operator=(const Scratch&) = delete;
     ~Scratch() {
         GN_LAP(nullptr);
-        for (void* b : blocks) (void)hipFree(b);
+        for (void* b : blocks) device_free(b);
         GN_LAP("  scratch: frees");
     }
     // `reserve_bytes`: what the builder knows it will ask for in total (one block then serves all of it)
@@ -137,13 +174,30 @@ struct Scratch {
   private:
     hipError_t open(size_t bytes) {
         void* b = nullptr;
-        const hipError_t e = hipMalloc(&b, bytes);
+        const hipError_t e = device_malloc(&b, bytes);
         if (e != hipSuccess) return e;
         blocks.push_back(b);
         at = static_cast<char*>(b); left = bytes;
         return hipSuccess;
     }
 };
+
+// starts[R + 1] of a range_list [R][2] that must tile [0, E) in relation order (starts[R] = E).  bad_row: the first row that does
+// not begin where the one before it ended or that ends before it begins, -1 when every row is in place; covered: where the rows
+// in place ended - E when the list tiles [0, E).
+struct RangeTiling {
+    int64_t bad_row = -1, covered = 0;
+};
+inline RangeTiling range_starts(const int64_t* ranges, int64_t R, int64_t E, std::vector<int64_t>& starts) {
+    starts.assign((size_t)R + 1, E);
+    RangeTiling t;
+    for (int64_t r = 0; r < R; ++r) {
+        if (ranges[2 * r] != t.covered || ranges[2 * r + 1] < t.covered) { t.bad_row = r; break; }
+        starts[r] = t.covered;
+        t.covered = ranges[2 * r + 1];
+    }
+    return t;
+}
 
 // Grid size for a memory-bound grid-stride kernel: enough blocks to fill 256 CUs, capped.
 inline int stream_grid(int64_t work_items, int block, int max_blocks = 256 * 8) {
@@ -228,14 +282,11 @@ struct gn_rgcn_plan {
     gn::DevBuf<int32_t> dw_multi;  // [n_dw_multi][4] relations of several parts: (relation, first slot, parts, 0)
     int64_t n_dw_multi = 0;
     // LDS-resident path (rgcn_fast.hip): work items = (relation, source tile, <= chunk edges)
-    gn::DevBuf<int32_t> seg_rel;    // [n_items] relation of each work item
-    gn::DevBuf<int32_t> item_tile;  // [n_items] source tile of each work item
     gn::DevBuf<int32_t> seg_begin;  // [n_items * buckets + 1] bucket offsets into packed
     gn::DevBuf<uint32_t> packed;    // [shard_edges] (dst << 16 | src - tile base), bucket-sorted inside an item
     gn::DevBuf<int32_t> wg_begin;   // [groups + 1] ranges into wg_items
     gn::DevBuf<int32_t> wg_items;   // item ids per persistent workgroup
-    int64_t n_seg = 0;
-    int fast_groups = 0, fast_ts = 0, fast_ts_pad = 0;
+    int fast_groups = 0, fast_ts = 0;
     size_t fast_lds_bytes = 0;
     int fast_cols = 32;             // output columns per workgroup of the LDS-resident kernel (32, or 16 = column halves)
     int fast_ok = 0;

@@ -28,8 +28,7 @@
 //     pairing of an edge's two directions, the sort's offsets, the task lists.
 #include "common.h"
 #include "layout_decoder_bwd.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "plan_device.cuh"
 
 #include <unordered_map>
 #include <vector>
@@ -95,11 +94,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 
-int bits_for(int64_t n) {
-    int b = 1;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
+using gn::bits_for;
 
 // mode 0: key = u, a = v, b = r;   mode 1: key = v, a = u, b = r;   mode 2: key = r, a = u, b = v.
 // Edges with an id outside its table get key = num_keys (sorted past the last row, never read).
@@ -1172,14 +1167,6 @@ struct gn_distmult_bwd_plan {
 
 namespace {
 
-void bwd_plan_free(gn_distmult_bwd_plan* p) {
-    if (!p) return;
-    p->eu.release(); p->ev.release(); p->er.release(); p->own.release(); p->mir.release();
-    p->offsets.release(); p->he_taskptr.release(); p->pr_taskptr.release(); p->he_tasks.release(); p->pr_tasks.release();
-    p->he_static.release(); p->pr_static.release();
-    delete p;
-}
-
 struct PlanWs { size_t g, he, pr, partial, total; };
 PlanWs plan_ws(const gn_distmult_bwd_plan* p, int64_t f) {
     PlanWs w;
@@ -1445,31 +1432,24 @@ extern "C" gn_status gn_distmult_bwd_plan_create(const int64_t* u, const int64_t
                                 take_in_order(&own[(size_t)b0], order); take_in_order(&mir[(size_t)b0], order);
                             });
     }
-    gn_distmult_bwd_plan* p = new (std::nothrow) gn_distmult_bwd_plan();
+    std::unique_ptr<gn_distmult_bwd_plan> p(new (std::nothrow) gn_distmult_bwd_plan());
     GN_REQUIRE(p != nullptr, "out of host memory");
     p->e_list = E; p->e = P; p->n = num_nodes; p->r = num_relations;
     if (p->e > 0) {
-        auto up = [&](auto& buf, const auto& host) -> hipError_t {
-            hipError_t err = buf.alloc(host.size());
-            if (err != hipSuccess) return err;
-            return hipMemcpyAsync(buf.p, host.data(), host.size() * sizeof(host[0]), hipMemcpyHostToDevice, st);
-        };
-        hipError_t err = hipSuccess;
-        if ((err = up(p->eu, eu)) != hipSuccess || (err = up(p->ev, ev)) != hipSuccess || (err = up(p->er, er)) != hipSuccess ||
-            (err = up(p->own, own)) != hipSuccess || (err = up(p->mir, mir)) != hipSuccess ||
-            (err = hipStreamSynchronize(st)) != hipSuccess) {
-            bwd_plan_free(p);
-            return gn::fail(GN_ERR_HIP, "decoder gradient plan upload failed: %s", hipGetErrorString(err));
-        }
-        gn_status rc = build_bwd_plan(p, st);
-        if (rc == GN_OK) rc = balance_static_records(p, st);
-        if (rc != GN_OK) { bwd_plan_free(p); return rc; }
+        GN_HIP(p->eu.upload(eu, st));
+        GN_HIP(p->ev.upload(ev, st));
+        GN_HIP(p->er.upload(er, st));
+        GN_HIP(p->own.upload(own, st));
+        GN_HIP(p->mir.upload(mir, st));
+        GN_HIP(hipStreamSynchronize(st));
+        GN_OK_OR_RETURN(build_bwd_plan(p.get(), st));
+        GN_OK_OR_RETURN(balance_static_records(p.get(), st));
     }
-    *out = p;
+    *out = p.release();
     return GN_OK;
 }
 
-extern "C" void gn_distmult_bwd_plan_destroy(gn_distmult_bwd_plan* plan) { bwd_plan_free(plan); }
+extern "C" void gn_distmult_bwd_plan_destroy(gn_distmult_bwd_plan* plan) { delete plan; }
 
 extern "C" size_t gn_distmult_bwd_plan_workspace_bytes(const gn_distmult_bwd_plan* plan, int64_t num_features) {
     if (!plan || num_features <= 0 || plan->e == 0) return 0;

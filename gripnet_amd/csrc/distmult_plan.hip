@@ -506,13 +506,8 @@ gn_status build_distmult_plan(const V& hu, const V& hv, const V& hr, int64_t E,
     gn_layout::pair_mirrors(hu, hv, hr, kNodeBits, mirror_of, covered);
     const gn::RawVec<int64_t> scored = gn_layout::scored_edges(covered);
     GN_LAP("decoder: scored list");
-    gn_distmult_plan* p = new gn_distmult_plan();
+    std::unique_ptr<gn_distmult_plan> p(new gn_distmult_plan());
     p->num_edges = E; p->num_nodes = num_nodes; p->num_relations = num_relations; p->batches = 0;
-    auto bail = [&](hipError_t e) {
-        gn_distmult_plan_destroy(p);
-        return gn::fail(GN_ERR_HIP, "DistMult plan upload failed: %s", hipGetErrorString(e));
-    };
-    hipError_t he;
     // The row-class encoding first (round 6): when it exists, the column-phase encoding below is never read by a launch of the
     // decoder's own width (a call with columns the row-class kernel has no instantiation for is refused with GN_ERR_UNSUPPORTED
     // and the caller scores the raw list) - and its dealing was a quarter of the plan's build time.
@@ -520,30 +515,30 @@ gn_status build_distmult_plan(const V& hu, const V& hv, const V& hr, int64_t E,
         gn_layout::ClassLayout cl = gn_layout::build_class_layout(hu, hv, hr, scored, mirror_of, num_nodes, num_features, gn::compute_units());
         if (cl.ok) {
             GN_LAP(nullptr);
-            if ((he = p->cls_packed.upload(cl.packed, st)) != hipSuccess) return bail(he);
-            if ((he = p->cls_own.upload(cl.own, st)) != hipSuccess) return bail(he);
-            if ((he = p->cls_mirror.upload(cl.mirror, st)) != hipSuccess) return bail(he);
-            if ((he = p->cls_rel.upload(cl.rel32, st)) != hipSuccess) return bail(he);
-            if ((he = p->cls_wg.upload(cl.wg, st)) != hipSuccess) return bail(he);
-            if ((he = hipStreamSynchronize(st)) != hipSuccess) return bail(he);
+            GN_HIP(p->cls_packed.upload(cl.packed, st));
+            GN_HIP(p->cls_own.upload(cl.own, st));
+            GN_HIP(p->cls_mirror.upload(cl.mirror, st));
+            GN_HIP(p->cls_rel.upload(cl.rel32, st));
+            GN_HIP(p->cls_wg.upload(cl.wg, st));
+            GN_HIP(hipStreamSynchronize(st));
             GN_LAP("decoder: allocations + upload (sync)");
             GN_LAP(nullptr);
             p->cls_features = (int)num_features; p->cls_groups = cl.groups; p->cls_batches = cl.batches; p->cls_walks = cl.walks;
             p->cls_ok = 1;
-            *out = p;
+            *out = p.release();
             return GN_OK;
         }
     }
     const gn_layout::PhaseLayout ph = gn_layout::build_phase_layout(hu, hv, hr, scored, mirror_of, kNodeBits);
     const int64_t NB = (int64_t)ph.batch_rel.size();
     p->batches = NB;
-    if ((he = p->packed.upload(ph.packed, st)) != hipSuccess) return bail(he);
-    if ((he = p->batch_rel.upload(ph.batch_rel, st)) != hipSuccess) return bail(he);
-    if ((he = p->rel16.upload(ph.rel16, st)) != hipSuccess) return bail(he);
-    if ((he = p->mirror.upload(ph.mirror, st)) != hipSuccess) return bail(he);
-    if ((he = p->own.upload(ph.own, st)) != hipSuccess) return bail(he);
-    if (NB > 0 && (he = hipStreamSynchronize(st)) != hipSuccess) return bail(he);     // the host arrays go out of scope after this
-    *out = p;
+    GN_HIP(p->packed.upload(ph.packed, st));
+    GN_HIP(p->batch_rel.upload(ph.batch_rel, st));
+    GN_HIP(p->rel16.upload(ph.rel16, st));
+    GN_HIP(p->mirror.upload(ph.mirror, st));
+    GN_HIP(p->own.upload(ph.own, st));
+    if (NB > 0) GN_HIP(hipStreamSynchronize(st));     // the host arrays go out of scope after this
+    *out = p.release();
     return GN_OK;
 }
 
@@ -570,56 +565,37 @@ gn_status gn_distmult_plan_create(const int64_t* u, const int64_t* v, const int6
     gn::ArenaHold arena;                                       // (before every host array of this build: host_parallel.hpp)
     gn::RawVec<uint16_t> hu(E), hv(E), hr(E);
     GN_LAP("decoder: host vectors");
-    if (E > 0) {
+    unsigned long long first = ~0ull;
+    if (E > 0) {                                               // (the two device buffers are freed before the host layout starts)
         gn::DevBuf<uint16_t> narrow;
         gn::DevBuf<unsigned long long> bad;
-        auto give_up = [&](hipError_t e) {
-            narrow.release(); bad.release();
-            return gn::fail(GN_ERR_HIP, "DistMult plan: reading the edge list failed: %s", hipGetErrorString(e));
-        };
-        hipError_t he;
-        if ((he = narrow.alloc((size_t)3 * E)) != hipSuccess) return give_up(he);
-        if ((he = bad.alloc(1)) != hipSuccess) return give_up(he);
-        unsigned long long first = ~0ull;
-        if ((he = hipMemsetAsync(bad.p, 0xff, sizeof(unsigned long long), st)) != hipSuccess) return give_up(he);
+        GN_HIP(narrow.alloc((size_t)3 * E));
+        GN_HIP(bad.alloc(1));
+        GN_HIP(hipMemsetAsync(bad.p, 0xff, sizeof(unsigned long long), st));
         k_narrow_triples<<<gn::stream_grid(E, 256), 256, 0, st>>>(u, v, edge_type, E, num_nodes, num_relations, narrow.p, narrow.p + E,
                                                                   narrow.p + 2 * E, bad.p);
-        if ((he = hipGetLastError()) != hipSuccess) return give_up(he);
-        if ((he = hipMemcpyAsync(&first, bad.p, sizeof(first), hipMemcpyDeviceToHost, st)) != hipSuccess) return give_up(he);
-        if ((he = hipMemcpyAsync(hu.data(), narrow.p, E * sizeof(uint16_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return give_up(he);
-        if ((he = hipMemcpyAsync(hv.data(), narrow.p + E, E * sizeof(uint16_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return give_up(he);
-        if ((he = hipMemcpyAsync(hr.data(), narrow.p + 2 * E, E * sizeof(uint16_t), hipMemcpyDeviceToHost, st)) != hipSuccess) return give_up(he);
-        if ((he = hipStreamSynchronize(st)) != hipSuccess) return give_up(he);
+        GN_LAUNCH_CHECK();
+        GN_HIP(hipMemcpyAsync(&first, bad.p, sizeof(first), hipMemcpyDeviceToHost, st));
+        GN_HIP(hipMemcpyAsync(hu.data(), narrow.p, E * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        GN_HIP(hipMemcpyAsync(hv.data(), narrow.p + E, E * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        GN_HIP(hipMemcpyAsync(hr.data(), narrow.p + 2 * E, E * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+        GN_HIP(hipStreamSynchronize(st));
         GN_LAP("decoder: narrow + D2H (sync)");
-        narrow.release(); bad.release();
-        GN_LAP("decoder: frees");
-        if (first != ~0ull) {
-            int64_t t[3] = {0, 0, 0};
-            GN_HIP(hipMemcpy(&t[0], u + first, sizeof(int64_t), hipMemcpyDeviceToHost));
-            GN_HIP(hipMemcpy(&t[1], v + first, sizeof(int64_t), hipMemcpyDeviceToHost));
-            GN_HIP(hipMemcpy(&t[2], edge_type + first, sizeof(int64_t), hipMemcpyDeviceToHost));
-            return gn::fail(GN_ERR_INDEX_RANGE, "edge %lld = (%lld, %lld, type %lld) is outside [0,%lld) x [0,%lld) x [0,%lld)",
-                            (long long)first, (long long)t[0], (long long)t[1], (long long)t[2], (long long)num_nodes,
-                            (long long)num_nodes, (long long)num_relations);
-        }
+    }
+    GN_LAP("decoder: frees");
+    if (first != ~0ull) {
+        int64_t t[3] = {0, 0, 0};
+        GN_HIP(hipMemcpy(&t[0], u + first, sizeof(int64_t), hipMemcpyDeviceToHost));
+        GN_HIP(hipMemcpy(&t[1], v + first, sizeof(int64_t), hipMemcpyDeviceToHost));
+        GN_HIP(hipMemcpy(&t[2], edge_type + first, sizeof(int64_t), hipMemcpyDeviceToHost));
+        return gn::fail(GN_ERR_INDEX_RANGE, "edge %lld = (%lld, %lld, type %lld) is outside [0,%lld) x [0,%lld) x [0,%lld)",
+                        (long long)first, (long long)t[0], (long long)t[1], (long long)t[2], (long long)num_nodes,
+                        (long long)num_nodes, (long long)num_relations);
     }
     return build_distmult_plan(hu, hv, hr, E, num_nodes, num_relations, num_features, st, out);
 }
 
-void gn_distmult_plan_destroy(gn_distmult_plan* p) {
-    if (!p) return;
-    p->packed.release();
-    p->batch_rel.release();
-    p->rel16.release();
-    p->mirror.release();
-    p->own.release();
-    p->cls_packed.release();
-    p->cls_own.release();
-    p->cls_mirror.release();
-    p->cls_rel.release();
-    p->cls_wg.release();
-    delete p;
-}
+void gn_distmult_plan_destroy(gn_distmult_plan* p) { delete p; }
 
 int64_t gn_distmult_plan_edges(const gn_distmult_plan* plan) { return plan ? plan->num_edges : -1; }
 

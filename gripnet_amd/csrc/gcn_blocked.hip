@@ -481,8 +481,6 @@ extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t co
     if (bl.failed) return gn::fail(GN_ERR_UNSUPPORTED, "internal: an edge was not scheduled");
     if (!bl.ok) return GN_OK;
     plan->blk_ok = 0;
-    plan->blk_dis.release(); plan->blk_tile_off.release(); plan->blk_ids.release(); plan->blk_cell.release();
-    plan->blk_tile_rows.release(); plan->blk_tile_dis.release(); plan->blk_table.release();
     GN_HIP(plan->blk_dis.upload(dis_host, st));
     GN_HIP(plan->blk_tile_off.upload(bl.tile_off, st));
     GN_HIP(plan->blk_tile_rows.upload(bl.tile_rows, st));

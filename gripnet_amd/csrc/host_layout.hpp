@@ -10,5 +10,6 @@
 #include "layout_decoder_bwd.hpp"
 #include "layout_rgcn_pair.hpp"
 #include "layout_rgcn_basis.hpp"
+#include "layout_rgcn_fast.hpp"
 #include "layout_blocked.hpp"
 #include "layout_rel_grad.hpp"

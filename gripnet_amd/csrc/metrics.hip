@@ -355,10 +355,6 @@ struct gn_link_metrics_plan {
     gn::DevBuf<int32_t> big_tile_prefix;  // [n_big + 1]
     gn::DevBuf<uint8_t> is_big;           // [2 R]: the segment's sorted keys end in the buffer the last merge round wrote
     gn::DevBuf<int32_t> chunk_seg, tile_seg, big_tile_owner;   // owner of every chunk / tile / merge tile (a load instead of a search per workgroup)
-    ~gn_link_metrics_plan() {
-        start.release(); chunk_prefix.release(); tile_prefix.release(); big_seg.release(); big_tile_prefix.release(); is_big.release();
-        chunk_seg.release(); tile_seg.release(); big_tile_owner.release();
-    }
 };
 
 namespace {
@@ -383,16 +379,10 @@ gn_status gn_link_metrics_plan_create(const int64_t* range_list_host, int64_t R,
     *out = nullptr;
     GN_REQUIRE(R >= 1 && E >= 0 && 2 * E < (1ll << 31) && 2 * R < (1ll << 30), "bad size (R=%lld, E=%lld)", (long long)R, (long long)E);
     GN_REQUIRE(range_list_host != nullptr, "range_list is null");
-    std::vector<int64_t> start(R + 1);
-    int64_t cursor = 0;
-    for (int64_t r = 0; r < R; ++r) {
-        GN_REQUIRE(range_list_host[2 * r] == cursor && range_list_host[2 * r + 1] >= cursor,
-                   "range_list must tile [0,E) in relation order (row %lld)", (long long)r);
-        start[r] = cursor;
-        cursor = range_list_host[2 * r + 1];
-    }
-    GN_REQUIRE(cursor == E, "range_list covers %lld edges, %lld scores given", (long long)cursor, (long long)E);
-    start[R] = E;
+    std::vector<int64_t> start;
+    const gn::RangeTiling tiling = gn::range_starts(range_list_host, R, E, start);
+    GN_REQUIRE(tiling.bad_row < 0, "range_list must tile [0,E) in relation order (row %lld)", (long long)tiling.bad_row);
+    GN_REQUIRE(tiling.covered == E, "range_list covers %lld edges, %lld scores given", (long long)tiling.covered, (long long)E);
     const int S = (int)(2 * R);
     std::vector<int32_t> chunk_prefix(S + 1, 0), tile_prefix(S + 1, 0), big_seg, big_tile_prefix(1, 0);
     std::vector<uint8_t> is_big(S, 0);
@@ -408,24 +398,12 @@ gn_status gn_link_metrics_plan_create(const int64_t* range_list_host, int64_t R,
             max_chunks = std::max(max_chunks, ch);
         }
     }
-    gn_link_metrics_plan* p = new gn_link_metrics_plan();
+    std::unique_ptr<gn_link_metrics_plan> p(new gn_link_metrics_plan());
     p->R = R; p->E = E; p->chunks = chunk_prefix[S]; p->tiles = tile_prefix[S];
     p->n_big = (int)big_seg.size(); p->big_tiles = big_tile_prefix.back();
     while ((1ll << p->rounds) < max_chunks) ++p->rounds;
     if (p->rounds & 1) for (int32_t s : big_seg) is_big[s] = 1;   // an odd number of ping-pong rounds ends in the second buffer
     hipStream_t st = gn::as_stream(stream);
-    auto bail = [&](hipError_t e, const char* what) { delete p; return gn::fail(GN_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e)); };
-#define GN_UP(buf, vec)                                                                                                  \
-    do {                                                                                                                 \
-        hipError_t e_ = p->buf.alloc(std::max<size_t>((vec).size(), 1));                                                 \
-        if (e_ != hipSuccess) return bail(e_, "hipMalloc");                                                              \
-        if (!(vec).empty()) {                                                                                            \
-            e_ = hipMemcpyAsync(p->buf.p, (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, st);      \
-            if (e_ != hipSuccess) return bail(e_, "hipMemcpyAsync");                                                     \
-        }                                                                                                                \
-    } while (0)
-    GN_UP(start, start); GN_UP(chunk_prefix, chunk_prefix); GN_UP(tile_prefix, tile_prefix);
-    GN_UP(big_seg, big_seg); GN_UP(big_tile_prefix, big_tile_prefix); GN_UP(is_big, is_big);
     std::vector<int32_t> chunk_seg, tile_seg, big_tile_owner;
     for (int s2 = 0; s2 < S; ++s2) {
         chunk_seg.insert(chunk_seg.end(), chunk_prefix[s2 + 1] - chunk_prefix[s2], s2);
@@ -433,11 +411,20 @@ gn_status gn_link_metrics_plan_create(const int64_t* range_list_host, int64_t R,
     }
     for (size_t b2 = 0; b2 + 1 < big_tile_prefix.size(); ++b2)
         big_tile_owner.insert(big_tile_owner.end(), big_tile_prefix[b2 + 1] - big_tile_prefix[b2], (int32_t)b2);
-    GN_UP(chunk_seg, chunk_seg); GN_UP(tile_seg, tile_seg); GN_UP(big_tile_owner, big_tile_owner);
-#undef GN_UP
-    hipError_t e = hipStreamSynchronize(st);                  // the vectors above are the sources of asynchronous copies
-    if (e != hipSuccess) return bail(e, "hipStreamSynchronize");
-    *out = p;
+    // (a list may be empty - no segment of several chunks, no edges: its buffer still holds one element, so that the kernels
+    // are handed a pointer they may form addresses from)
+    for (std::vector<int32_t>* v : {&big_seg, &chunk_seg, &tile_seg, &big_tile_owner}) v->resize(std::max<size_t>(v->size(), 1));
+    GN_HIP(p->start.upload(start, st));
+    GN_HIP(p->chunk_prefix.upload(chunk_prefix, st));
+    GN_HIP(p->tile_prefix.upload(tile_prefix, st));
+    GN_HIP(p->big_seg.upload(big_seg, st));
+    GN_HIP(p->big_tile_prefix.upload(big_tile_prefix, st));
+    GN_HIP(p->is_big.upload(is_big, st));
+    GN_HIP(p->chunk_seg.upload(chunk_seg, st));
+    GN_HIP(p->tile_seg.upload(tile_seg, st));
+    GN_HIP(p->big_tile_owner.upload(big_tile_owner, st));
+    GN_HIP(hipStreamSynchronize(st));                         // the vectors above are the sources of asynchronous copies
+    *out = p.release();
     return GN_OK;
 }
 

@@ -11,8 +11,7 @@
 // pairs of the block, with replacement); not the same random stream (numpy's global RNG cannot be
 // replayed on the device, and the reference's own stream changes with every call).
 #include "common.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
+#include "plan_device.cuh"
 
 #include <vector>
 
@@ -50,6 +49,7 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x) {     // splitmix64 finali
     return x ^ (x >> 31);
 }
 
+// (the general sampling kernel's own search: plan construction uses gn::last_start_le)
 __device__ __forceinline__ int relation_of(const int64_t* __restrict__ starts, int R, int64_t e) {
     int a = 0, b = R;                                       // last r with starts[r] <= e
     while (b - a > 1) {
@@ -65,18 +65,8 @@ __global__ void k_pair_keys(const int64_t* __restrict__ u, const int64_t* __rest
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
         const int64_t uu = u[e], vv = v[e];
         if ((uint64_t)uu >= (uint64_t)n || (uint64_t)vv >= (uint64_t)n) { atomicOr(err, 1); keys[e] = ~0ull; continue; }
-        keys[e] = ((uint64_t)relation_of(starts, R, e) << 40) | (uint64_t)(uu * n + vv);
+        keys[e] = ((uint64_t)gn::last_start_le(starts, R, e) << 40) | (uint64_t)(uu * n + vv);
     }
-}
-
-// The radix sort of (relation << 40 | u * n + v) pair keys, shared by the sampler and the known-pair set of the ranking
-// kernels: `end_bit` bounds the key bits that can differ; `*scratch` is the caller's to free once the stream has passed.
-hipError_t sort_pair_keys(uint64_t* raw, uint64_t* sorted, int64_t E, int end_bit, void** scratch, hipStream_t st) {
-    size_t bytes = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, bytes, raw, sorted, (size_t)E, 0, end_bit, st);
-    if (e == hipSuccess) e = hipMalloc(scratch, bytes ? bytes : 1);
-    if (e == hipSuccess) e = rocprim::radix_sort_keys(*scratch, bytes, raw, sorted, (size_t)E, 0, end_bit, st);
-    return e;
 }
 
 // Known pairs: the relation comes with every edge (any order, duplicates allowed) instead of from a range list.
@@ -98,12 +88,7 @@ __global__ void k_known_rows(const uint64_t* __restrict__ keys, int64_t E, int64
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t <= rows; t += (int64_t)gridDim.x * blockDim.x) {
         if (t == rows) { rowptr[t] = (int32_t)E; continue; }
         const uint64_t target = ((uint64_t)(t / n) << 40) | (uint64_t)((t % n) * n);
-        int64_t lo = 0, hi = E;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (keys[mid] < target) lo = mid + 1; else hi = mid;
-        }
-        rowptr[t] = (int32_t)lo;
+        rowptr[t] = gn::lower_bound(keys, (int)E, target);
     }
 }
 
@@ -144,7 +129,7 @@ __global__ void k_narrow_keys(const uint64_t* __restrict__ keys, const int64_t* 
                               uint32_t* __restrict__ keys32, uint16_t* __restrict__ rel16) {
     for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
         keys32[e] = (uint32_t)(keys[e] & 0xFFFFFFFFull);
-        rel16[e] = (uint16_t)relation_of(starts, R, e);
+        rel16[e] = (uint16_t)gn::last_start_le(starts, R, e);
     }
 }
 
@@ -356,6 +341,47 @@ gn_status launch_sample(const gn_negative_sampler* s, uint64_t seed, int64_t* ou
     return GN_OK;
 }
 
+// The narrow encoding of a sampler whose sorted keys are in place, then (while they fit) the bitmap and the tasks.
+gn_status build_narrow_encodings(gn_negative_sampler* s, const std::vector<int64_t>& starts, hipStream_t st) {
+    const int64_t E = s->num_edges, N = s->num_nodes, R = s->num_relations;
+    GN_HIP(s->keys32.alloc(E + 8));                          // (the task kernel stages whole 16-byte words)
+    GN_HIP(s->rel16.alloc(E));
+    k_narrow_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(s->keys.p, s->starts.p, (int)R, E, s->keys32.p, s->rel16.p);
+    GN_LAUNCH_CHECK();
+    s->narrow = 1;
+    const int64_t words = ((N * N + 31) / 32 + 3) & ~(int64_t)3;
+    if (R * words * 4 > kBitmapBytes) return GN_OK;
+    GN_HIP(s->bitmap.alloc(R * words));
+    GN_HIP(hipMemsetAsync(s->bitmap.p, 0, (size_t)(R * words) * sizeof(uint32_t), st));
+    k_fill_bitmap<<<gn::stream_grid(E, 256), 256, 0, st>>>(s->keys32.p, s->rel16.p, E, words, s->bitmap.p);
+    GN_LAUNCH_CHECK();
+    s->words = words;
+    if (sampler_tasks_disabled()) return GN_OK;
+    std::vector<int32_t> tasks;
+    int64_t most = 0;
+    for (int pass = 1; pass >= 0; --pass)               // the large relations first
+        for (int64_t r = 0; r < R; ++r) {
+            const int64_t len = starts[r + 1] - starts[r];
+            const int kind = len > kTaskMaxIds ? 1 : 0;
+            if (kind != pass) continue;
+            if (!kind) most = std::max(most, len);
+            const int64_t slice = kind ? kTaskSliceBits : kTaskSliceIds;
+            for (int64_t a = starts[r]; a < starts[r + 1]; a += slice) {
+                const int32_t d[8] = {(int32_t)r, (int32_t)a, (int32_t)std::min(starts[r + 1], a + slice), kind,
+                                      (int32_t)starts[r], (int32_t)len, 0, 0};
+                tasks.insert(tasks.end(), d, d + 8);
+            }
+        }
+    if (tasks.empty()) return GN_OK;
+    const size_t described = tasks.size();
+    tasks.push_back(0);                                   // the arrival counter of the stepped draw
+    GN_HIP(s->tasks.upload(tasks, st));
+    GN_HIP(hipStreamSynchronize(st));                     // `tasks` leaves scope
+    s->num_tasks = (int64_t)(described / 8);
+    s->task_lds = (size_t)(most + 8) * 4;                  // (up to three words of alignment in front)
+    return GN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,104 +395,37 @@ gn_status gn_negative_sampler_create(const int64_t* u, const int64_t* v, const i
     GN_REQUIRE(range_list_host != nullptr, "range_list is null");
     if (N >= (1ll << 20) || R >= (1ll << 23))
         return gn::fail(GN_ERR_UNSUPPORTED, "sampler keys hold 2^20 nodes and 2^23 relations at most");
-    std::vector<int64_t> starts(R + 1);
-    int64_t cursor = 0;
-    for (int64_t r = 0; r < R; ++r) {
-        if (range_list_host[2 * r] != cursor || range_list_host[2 * r + 1] < cursor)
-            return gn::fail(GN_ERR_INVALID_ARG, "range_list must tile [0,E) in relation order (row %lld)", (long long)r);
-        starts[r] = cursor;
-        cursor = range_list_host[2 * r + 1];
-    }
-    if (cursor != E) return gn::fail(GN_ERR_INVALID_ARG, "range_list covers %lld edges but edge_index has %lld",
-                                     (long long)cursor, (long long)E);
-    starts[R] = E;
+    std::vector<int64_t> starts;
+    const gn::RangeTiling tiling = gn::range_starts(range_list_host, R, E, starts);
+    GN_REQUIRE(tiling.bad_row < 0, "range_list must tile [0,E) in relation order (row %lld)", (long long)tiling.bad_row);
+    GN_REQUIRE(tiling.covered == E, "range_list covers %lld edges but edge_index has %lld", (long long)tiling.covered, (long long)E);
     hipStream_t st = gn::as_stream(stream);
-    gn_negative_sampler* s = new gn_negative_sampler();
+    std::unique_ptr<gn_negative_sampler> s(new gn_negative_sampler());
     s->num_edges = E; s->num_nodes = N; s->num_relations = R;
-    auto bail = [&](gn_status code) { gn_negative_sampler_destroy(s); return code; };
-#define GN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(gn::fail(GN_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e))); } while (0)
-    GN_TRY(s->keys.alloc(E));
-    GN_TRY(s->starts.alloc(R + 1));
-    GN_TRY(hipMemcpyAsync(s->starts.p, starts.data(), (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    uint64_t* raw = nullptr;
-    int32_t* err = nullptr;
-    void* scratch = nullptr;
+    GN_HIP(s->keys.alloc(E));
+    GN_HIP(s->starts.upload(starts, st));
+    gn::Scratch tmp;
     int32_t bad = 0;
     if (E > 0) {
-        GN_TRY(hipMalloc(reinterpret_cast<void**>(&raw), E * sizeof(uint64_t)));
-        hipError_t e2 = hipMalloc(reinterpret_cast<void**>(&err), sizeof(int32_t));
-        if (e2 != hipSuccess) { (void)hipFree(raw); return bail(gn::fail(GN_ERR_HIP, "hipMalloc failed")); }
-        (void)hipMemsetAsync(err, 0, sizeof(int32_t), st);
+        uint64_t* raw;
+        int32_t* err;
+        GN_HIP(tmp.get(&raw, E));
+        GN_HIP(tmp.get(&err, 1));
+        GN_HIP(hipMemsetAsync(err, 0, sizeof(int32_t), st));
         k_pair_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(u, v, s->starts.p, (int)R, E, N, raw, err);
-        hipError_t e3 = sort_pair_keys(raw, s->keys.p, E, 64, &scratch, st);
-        if (e3 == hipSuccess && N < (1ll << 16) && R < (1ll << 16) && E < (1ll << 31) && !gn::fast_paths_disabled()) {
-            e3 = s->keys32.alloc(E + 8);                     // (the task kernel stages whole 16-byte words)
-            if (e3 == hipSuccess) e3 = s->rel16.alloc(E);
-            if (e3 == hipSuccess) {
-                k_narrow_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(s->keys.p, s->starts.p, (int)R, E, s->keys32.p, s->rel16.p);
-                e3 = hipGetLastError();
-                s->narrow = 1;
-            }
-            const int64_t words = ((N * N + 31) / 32 + 3) & ~(int64_t)3;
-            if (e3 == hipSuccess && R * words * 4 <= kBitmapBytes) {
-                e3 = s->bitmap.alloc(R * words);
-                if (e3 == hipSuccess) e3 = hipMemsetAsync(s->bitmap.p, 0, (size_t)(R * words) * sizeof(uint32_t), st);
-                if (e3 == hipSuccess) {
-                    k_fill_bitmap<<<gn::stream_grid(E, 256), 256, 0, st>>>(s->keys32.p, s->rel16.p, E, words, s->bitmap.p);
-                    e3 = hipGetLastError();
-                    s->words = words;
-                }
-                if (e3 == hipSuccess && !sampler_tasks_disabled()) {
-                    std::vector<int32_t> tasks;
-                    int64_t most = 0;
-                    for (int pass = 1; pass >= 0; --pass)               // the large relations first
-                        for (int64_t r = 0; r < R; ++r) {
-                            const int64_t len = starts[r + 1] - starts[r];
-                            const int kind = len > kTaskMaxIds ? 1 : 0;
-                            if (kind != pass) continue;
-                            if (!kind) most = std::max(most, len);
-                            const int64_t slice = kind ? kTaskSliceBits : kTaskSliceIds;
-                            for (int64_t a = starts[r]; a < starts[r + 1]; a += slice) {
-                                const int32_t d[8] = {(int32_t)r, (int32_t)a, (int32_t)std::min(starts[r + 1], a + slice), kind,
-                                                      (int32_t)starts[r], (int32_t)len, 0, 0};
-                                tasks.insert(tasks.end(), d, d + 8);
-                            }
-                        }
-                    if (!tasks.empty()) {
-                        const size_t described = tasks.size();
-                        tasks.push_back(0);                                   // the arrival counter of the stepped draw
-                        e3 = s->tasks.alloc(tasks.size());
-                        if (e3 == hipSuccess) e3 = hipMemcpyAsync(s->tasks.p, tasks.data(), tasks.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
-                        if (e3 == hipSuccess) e3 = hipStreamSynchronize(st);   // `tasks` leaves scope
-                        s->num_tasks = (int64_t)(described / 8);
-                        s->task_lds = (size_t)(most + 8) * 4;                  // (up to three words of alignment in front)
-                    }
-                }
-            }
-        }
-        if (e3 == hipSuccess) e3 = hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e3 == hipSuccess) e3 = hipStreamSynchronize(st);
-        (void)hipFree(raw); (void)hipFree(err); if (scratch) (void)hipFree(scratch);
-        if (e3 != hipSuccess) return bail(gn::fail(GN_ERR_HIP, "sampler construction failed: %s", hipGetErrorString(e3)));
-    } else {
-        GN_TRY(hipStreamSynchronize(st));
+        GN_LAUNCH_CHECK();
+        GN_OK_OR_RETURN(gn::sort_keys(tmp, raw, s->keys.p, (size_t)E, 64, st));
+        if (N < (1ll << 16) && R < (1ll << 16) && E < (1ll << 31) && !gn::fast_paths_disabled())
+            GN_OK_OR_RETURN(build_narrow_encodings(s.get(), starts, st));
+        GN_HIP(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-#undef GN_TRY
-    if (bad) return bail(gn::fail(GN_ERR_INDEX_RANGE, "edge_index holds a node id outside [0,%lld)", (long long)N));
-    *out = s;
+    GN_HIP(hipStreamSynchronize(st));                         // `starts` and the scratch leave scope
+    if (bad) return gn::fail(GN_ERR_INDEX_RANGE, "edge_index holds a node id outside [0,%lld)", (long long)N);
+    *out = s.release();
     return GN_OK;
 }
 
-void gn_negative_sampler_destroy(gn_negative_sampler* s) {
-    if (!s) return;
-    s->keys.release();
-    s->starts.release();
-    s->keys32.release();
-    s->rel16.release();
-    s->bitmap.release();
-    s->tasks.release();
-    delete s;
-}
+void gn_negative_sampler_destroy(gn_negative_sampler* s) { delete s; }
 
 gn_status gn_negative_sampler_sample(const gn_negative_sampler* s, uint64_t seed, int64_t* out_u, int64_t* out_v,
                                      int32_t* error_flag, void* stream) {
@@ -504,61 +463,40 @@ gn_status gn_known_pairs_create(const int64_t* u, const int64_t* v, const int64_
     if (N >= (1ll << 20) || R >= (1ll << 23) || R * N >= (1ll << 31) || E >= (1ll << 31))
         return gn::fail(GN_ERR_UNSUPPORTED, "known pairs hold 2^20 nodes, 2^23 relations, 2^31 rows (R * n) and 2^31 pairs at most");
     hipStream_t st = gn::as_stream(stream);
-    gn_known_pairs* k = new gn_known_pairs();
+    std::unique_ptr<gn_known_pairs> k(new gn_known_pairs());
     k->num_edges = E; k->num_nodes = N; k->num_relations = R;
     const int64_t rows = R * N;
-    uint64_t *raw = nullptr, *keys = nullptr;
-    int32_t* err = nullptr;
-    void* scratch = nullptr;
+    gn::Scratch tmp;
+    uint64_t* keys = nullptr;
     int32_t bad = 0;
-    hipError_t e = k->rowptr.alloc(rows + 1);
-    if (e == hipSuccess) e = k->partners.alloc(E);
-    if (e == hipSuccess && E > 0) {
+    GN_HIP(k->rowptr.alloc(rows + 1));
+    GN_HIP(k->partners.alloc(E));
+    if (E > 0) {
         int end_bit = 40;                                     // the bits a valid key can set
         while ((1ll << (end_bit - 40)) < R) ++end_bit;
-        e = hipMalloc(reinterpret_cast<void**>(&raw), E * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&keys), E * sizeof(uint64_t));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&err), sizeof(int32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(err, 0, sizeof(int32_t), st);
-        if (e == hipSuccess) {
-            k_known_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(u, v, edge_type, E, N, R, raw, err);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = sort_pair_keys(raw, keys, E, end_bit, &scratch, st);
-        if (e == hipSuccess) {
-            k_known_partners<<<gn::stream_grid(E, 256), 256, 0, st>>>(keys, E, N, k->partners.p);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+        uint64_t* raw;
+        int32_t* err;
+        GN_HIP(tmp.get(&raw, E));
+        GN_HIP(tmp.get(&keys, E));
+        GN_HIP(tmp.get(&err, 1));
+        GN_HIP(hipMemsetAsync(err, 0, sizeof(int32_t), st));
+        k_known_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(u, v, edge_type, E, N, R, raw, err);
+        GN_LAUNCH_CHECK();
+        GN_OK_OR_RETURN(gn::sort_keys(tmp, raw, keys, (size_t)E, end_bit, st));
+        k_known_partners<<<gn::stream_grid(E, 256), 256, 0, st>>>(keys, E, N, k->partners.p);
+        GN_LAUNCH_CHECK();
+        GN_HIP(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     }
-    if (e == hipSuccess) {
-        if (E > 0) k_known_rows<<<gn::stream_grid(rows + 1, 256), 256, 0, st>>>(keys, E, N, rows, k->rowptr.p);
-        else k_known_rows<<<gn::stream_grid(rows + 1, 256), 256, 0, st>>>(nullptr, 0, N, rows, k->rowptr.p);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (raw) (void)hipFree(raw);
-    if (keys) (void)hipFree(keys);
-    if (err) (void)hipFree(err);
-    if (scratch) (void)hipFree(scratch);
-    if (e != hipSuccess) {
-        gn_known_pairs_destroy(k);
-        return gn::fail(GN_ERR_HIP, "known-pairs construction failed: %s", hipGetErrorString(e));
-    }
-    if (bad) {
-        gn_known_pairs_destroy(k);
+    k_known_rows<<<gn::stream_grid(rows + 1, 256), 256, 0, st>>>(keys, E, N, rows, k->rowptr.p);
+    GN_LAUNCH_CHECK();
+    GN_HIP(hipStreamSynchronize(st));
+    if (bad)
         return gn::fail(GN_ERR_INDEX_RANGE, "known pairs: a node id outside [0,%lld) or a relation id outside [0,%lld)",
                         (long long)N, (long long)R);
-    }
-    *out = k;
+    *out = k.release();
     return GN_OK;
 }
 
-void gn_known_pairs_destroy(gn_known_pairs* k) {
-    if (!k) return;
-    k->rowptr.release();
-    k->partners.release();
-    delete k;
-}
+void gn_known_pairs_destroy(gn_known_pairs* k) { delete k; }
 
 }  // extern "C"

@@ -7,9 +7,7 @@
 // scatter_add.  Plan construction is not on the steady-state path; it may synchronise.
 #include "common.h"
 #include "layout_rgcn_basis.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "plan_device.cuh"
 
 #include <algorithm>
 #include <mutex>
@@ -73,16 +71,6 @@ namespace {
 
 using gn::DevBuf;
 
-// ---- small device helpers ------------------------------------------------------------------
-__device__ __forceinline__ int lower_bound_i32(const int32_t* a, int n, int v) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // keep[e] = 1 for valid non-loop edges; last_loop[i] = largest e with src=dst=i (or -1).
 __global__ void k_mark_edges(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t E,
                              int64_t n_src, int64_t n_dst, int drop_loops, int32_t* __restrict__ keep,
@@ -128,11 +116,6 @@ __global__ void k_compact(const int64_t* __restrict__ src, const int64_t* __rest
             iota[p] = p;
         }
     }
-}
-
-__global__ void k_rowptr(const int32_t* __restrict__ sorted_dst, int nnz, int rows, int32_t* __restrict__ rowptr) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i <= rows) rowptr[i] = lower_bound_i32(sorted_dst, nnz, i);
 }
 
 // deg[i] = sum of weights into i in stored order (+ extra), dis = deg^-1/2 with inf -> 0.
@@ -190,12 +173,7 @@ __global__ void k_expand_rows(const int32_t* __restrict__ rowptr, int rows, int 
                               int32_t* __restrict__ iota) {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= nnz) return;
-    int lo = 0, hi = rows;                 // last row with rowptr[row] <= p
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (rowptr[mid] <= p) lo = mid; else hi = mid;
-    }
-    row_of[p] = lo;
+    row_of[p] = gn::last_start_le(rowptr, rows, p);
     iota[p] = p;
 }
 
@@ -209,26 +187,8 @@ __global__ void k_fill_transpose(const int32_t* __restrict__ perm, const int32_t
     t_coef[q] = coef[p];
 }
 
-int bits_for(int64_t n) {
-    int b = 1;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
-
+using gn::bits_for;
 using Temp = gn::Scratch;   // scoped device scratch for plan construction (common.h)
-
-gn_status sort_by_dst(Temp& tmp, const int32_t* keys_in, int32_t* keys_out, const int32_t* vals_in,
-                      int32_t* vals_out, int64_t n, int64_t key_range, hipStream_t st) {
-    if (n == 0) return GN_OK;
-    size_t bytes = 0;
-    GN_HIP(rocprim::radix_sort_pairs(nullptr, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0,
-                                     bits_for(key_range), st));
-    char* scratch = nullptr;
-    GN_HIP(tmp.get(&scratch, bytes));
-    GN_HIP(rocprim::radix_sort_pairs(scratch, bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, 0,
-                                     bits_for(key_range), st));
-    return GN_OK;
-}
 
 gn_status build_graph_plan(const int64_t* src, const int64_t* dst, const float* w, int64_t E, int64_t n_src,
                            int64_t n_dst, bool gcn, int improved, hipStream_t st, gn_graph_plan* plan,
@@ -247,13 +207,7 @@ gn_status build_graph_plan(const int64_t* src, const int64_t* dst, const float* 
     k_mark_edges<<<gn::stream_grid(E + 1, 256), 256, 0, st>>>(src, dst, E, n_src, n_dst, gcn ? 1 : 0, keep,
                                                              last_loop, err);
     GN_LAUNCH_CHECK();
-    {
-        size_t bytes = 0;
-        GN_HIP(rocprim::exclusive_scan(nullptr, bytes, keep, pos, 0, (size_t)(E + 1), rocprim::plus<int32_t>(), st));
-        char* scratch = nullptr;
-        GN_HIP(tmp.get(&scratch, bytes));
-        GN_HIP(rocprim::exclusive_scan(scratch, bytes, keep, pos, 0, (size_t)(E + 1), rocprim::plus<int32_t>(), st));
-    }
+    GN_OK_OR_RETURN(gn::exclusive_scan_i32(tmp, keep, pos, (size_t)(E + 1), st));
     int32_t kept = 0, bad = 0;
     GN_HIP(hipMemcpyAsync(&kept, pos + E, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GN_HIP(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -279,8 +233,7 @@ gn_status build_graph_plan(const int64_t* src, const int64_t* dst, const float* 
                                                                    keep, pos, last_loop, src2, dst2, w2, iota);
         GN_LAUNCH_CHECK();
     }
-    gn_status s = sort_by_dst(tmp, dst2, sorted_dst, iota, perm, nnz, n_dst, st);
-    if (s != GN_OK) return s;
+    GN_OK_OR_RETURN(gn::sort_pairs(tmp, dst2, sorted_dst, iota, perm, (size_t)nnz, bits_for(n_dst), st));
 
     plan->input_edges = E;
     plan->nnz = nnz;
@@ -290,8 +243,7 @@ gn_status build_graph_plan(const int64_t* src, const int64_t* dst, const float* 
     GN_HIP(plan->rowptr.alloc(n_dst + 1));
     GN_HIP(plan->col.alloc(nnz + 8));                   // (k_aggregate_lds_table reads a row's ids eight at a time)
     GN_HIP(plan->coef.alloc(nnz));
-    k_rowptr<<<(int)gn::ceil_div(n_dst + 1, 256), 256, 0, st>>>(sorted_dst, (int)nnz, (int)n_dst, plan->rowptr.p);
-    GN_LAUNCH_CHECK();
+    GN_OK_OR_RETURN(gn::first_at_least(sorted_dst, nnz, n_dst, plan->rowptr.p, st));
     if (n_dst > 0) {
         k_degree<<<(int)gn::ceil_div(n_dst, 256), 256, 0, st>>>(plan->rowptr.p, perm, w2, (int)n_dst,
                                                                gcn ? 0.0f : 1.0f, dis);
@@ -348,27 +300,6 @@ __global__ void k_build_ell(const int32_t* __restrict__ rowptr, const int32_t* _
     ell_coef[t] = live ? (coef ? coef[at] : 1.0f) : 0.f;
 }
 
-void free_graph_plan(gn_graph_plan* p) {
-    p->ell_col.release();
-    p->ell_coef.release();
-    p->rowptr.release();
-    p->col.release();
-    p->coef.release();
-    p->ref_edge_index.release();
-    p->ref_norm.release();
-    p->t_rowptr.release();
-    p->t_col.release();
-    p->t_coef.release();
-    p->dis.release();
-    p->blk_dis.release();
-    p->blk_tile_off.release();
-    p->blk_ids.release();
-    p->blk_cell.release();
-    p->blk_tile_rows.release();
-    p->blk_tile_dis.release();
-    p->blk_table.release();
-}
-
 // ---- RGCN ------------------------------------------------------------------------------------
 // In-degree of every destination.  A supervertex of a few hundred nodes under millions of edges (PoSE: 645 under 2 M)
 // puts thousands of atomic adds on every counter: each workgroup counts into an LDS histogram first when the counters
@@ -402,11 +333,7 @@ __global__ void k_rel_keys(const int64_t* __restrict__ src, const int64_t* __res
                            const int64_t* __restrict__ range_start, int R, int64_t lo, int64_t hi, int64_t N,
                            int32_t* __restrict__ dst32, uint32_t* __restrict__ key, int32_t* __restrict__ err) {
     for (int64_t e = lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < hi; e += (int64_t)gridDim.x * blockDim.x) {
-        int a = 0, b = R;  // last r with range_start[r] <= e
-        while (b - a > 1) {
-            int mid = (a + b) >> 1;
-            if (range_start[mid] <= e) a = mid; else b = mid;
-        }
+        const int a = gn::last_start_le(range_start, R, e);
         int64_t s = src[e], d = dst[e];
         bool ok = (uint64_t)s < (uint64_t)N && (uint64_t)d < (uint64_t)N;
         if (!ok) { atomicOr(err, 1); s = 0; d = 0; }
@@ -419,15 +346,17 @@ __global__ void k_rel_keys(const int64_t* __restrict__ src, const int64_t* __res
 
 // Implemented in rgcn_fast.hip: relation-major segments for the LDS-resident path.
 gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst,
-                                      const std::vector<int64_t>& ranges_host, hipStream_t st);
+                                      const int64_t* starts_dev, hipStream_t st);
 
 // Implemented in rgcn_pair.hip: per-workgroup destination rows and per-wave streams of the destination-major path.
+// (`starts_dev`: the [R + 1] range starts on the device, built once by gn_rgcn_plan_create_ex; its scratch outlives both calls)
 gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst,
-                                  const std::vector<int64_t>& ranges, hipStream_t st);
+                                  const int64_t* starts_dev, hipStream_t st);
 
 extern "C" {
 
 int gn_version(void) { return GN_VERSION; }
+int64_t gn_device_blocks_live(void) { return gn::device_blocks_live().load(std::memory_order_relaxed); }
 const char* gn_last_error(void) { return gn::error_buffer(); }
 
 gn_status gn_gcn_plan_create(const int64_t* src, const int64_t* dst, const float* w, int64_t E, int64_t N,
@@ -438,10 +367,9 @@ gn_status gn_gcn_plan_create(const int64_t* src, const int64_t* dst, const float
     GN_REQUIRE(E == 0 || (src && dst), "edge pointers are null");
     if (E + N >= ((int64_t)1 << 31) || N >= ((int64_t)1 << 31))
         return gn::fail(GN_ERR_UNSUPPORTED, "graph too large for the int32 plan encoding");
-    gn_graph_plan* p = new gn_graph_plan();
-    gn_status s = build_graph_plan(src, dst, w, E, N, N, true, improved, gn::as_stream(stream), p);
-    if (s != GN_OK) { free_graph_plan(p); delete p; return s; }
-    *out = p;
+    std::unique_ptr<gn_graph_plan> p(new gn_graph_plan());
+    GN_OK_OR_RETURN(build_graph_plan(src, dst, w, E, N, N, true, improved, gn::as_stream(stream), p.get()));
+    *out = p.release();
     return GN_OK;
 }
 
@@ -453,23 +381,20 @@ gn_status gn_bipartite_plan_create(const int64_t* src, const int64_t* dst, const
     GN_REQUIRE(E == 0 || (src && dst), "edge pointers are null");
     if (E >= ((int64_t)1 << 31) || n_src >= ((int64_t)1 << 31) || n_tgt >= ((int64_t)1 << 31))
         return gn::fail(GN_ERR_UNSUPPORTED, "graph too large for the int32 plan encoding");
-    gn_graph_plan* p = new gn_graph_plan();
-    gn_status s = build_graph_plan(src, dst, w, E, n_src, n_tgt, false, 0, gn::as_stream(stream), p);
-    if (s != GN_OK) { free_graph_plan(p); delete p; return s; }
+    hipStream_t st = gn::as_stream(stream);
+    std::unique_ptr<gn_graph_plan> p(new gn_graph_plan());
+    GN_OK_OR_RETURN(build_graph_plan(src, dst, w, E, n_src, n_tgt, false, 0, st, p.get()));
     // short rows (the external layer: 645 targets of ~29 edges): the padded layout as well
     if (p->rows > 0 && p->rows <= (1 << 20) && p->max_row_nnz <= 64 && p->nnz > 0 && !gn::fast_paths_disabled()) {
-        hipError_t he = p->ell_col.alloc((size_t)p->rows * 64);
-        if (he == hipSuccess) he = p->ell_coef.alloc((size_t)p->rows * 64);
-        if (he != hipSuccess) { free_graph_plan(p); delete p; return gn::fail(GN_ERR_HIP, "padded rows: %s", hipGetErrorString(he)); }
-        k_build_ell<<<(int)gn::ceil_div(p->rows * 64, 256), 256, 0, gn::as_stream(stream)>>>(p->rowptr.p, p->col.p, p->coef.p, (int)p->rows,
-                                                                                            p->ell_col.p, p->ell_coef.p);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(gn::as_stream(stream)) != hipSuccess) {
-            free_graph_plan(p); delete p;
-            return gn::fail(GN_ERR_HIP, "padded rows: the layout kernel failed");
-        }
+        GN_HIP(p->ell_col.alloc((size_t)p->rows * 64));
+        GN_HIP(p->ell_coef.alloc((size_t)p->rows * 64));
+        k_build_ell<<<(int)gn::ceil_div(p->rows * 64, 256), 256, 0, st>>>(p->rowptr.p, p->col.p, p->coef.p, (int)p->rows,
+                                                                         p->ell_col.p, p->ell_coef.p);
+        GN_LAUNCH_CHECK();
+        GN_HIP(hipStreamSynchronize(st));
         p->ell_ok = 1;
     }
-    *out = p;
+    *out = p.release();
     return GN_OK;
 }
 
@@ -481,18 +406,13 @@ gn_status gn_sum_plan_create(const int64_t* src, const int64_t* dst, const float
     GN_REQUIRE(E == 0 || (src && dst), "edge pointers are null");
     if (E >= ((int64_t)1 << 31) || n_src >= ((int64_t)1 << 31) || n_dst >= ((int64_t)1 << 31))
         return gn::fail(GN_ERR_UNSUPPORTED, "graph too large for the int32 plan encoding");
-    gn_graph_plan* p = new gn_graph_plan();
-    gn_status s = build_graph_plan(src, dst, w, E, n_src, n_dst, false, 0, gn::as_stream(stream), p, true);
-    if (s != GN_OK) { free_graph_plan(p); delete p; return s; }
-    *out = p;
+    std::unique_ptr<gn_graph_plan> p(new gn_graph_plan());
+    GN_OK_OR_RETURN(build_graph_plan(src, dst, w, E, n_src, n_dst, false, 0, gn::as_stream(stream), p.get(), true));
+    *out = p.release();
     return GN_OK;
 }
 
-void gn_graph_plan_destroy(gn_graph_plan* plan) {
-    if (!plan) return;
-    free_graph_plan(plan);
-    delete plan;
-}
+void gn_graph_plan_destroy(gn_graph_plan* plan) { delete plan; }
 
 int64_t gn_graph_plan_input_edges(const gn_graph_plan* plan) { return plan ? plan->input_edges : -1; }
 int64_t gn_graph_plan_nnz(const gn_graph_plan* plan) { return plan ? plan->nnz : -1; }
@@ -527,13 +447,11 @@ gn_status gn_graph_plan_build_transpose(gn_graph_plan* plan, void* stream) {
         k_expand_rows<<<g, 256, 0, st>>>(plan->rowptr.p, (int)rows, (int)nnz, row_of, iota);
         GN_LAUNCH_CHECK();
         // stable sort by source: inside a source row the destinations keep the CSR (= reference) order
-        gn_status s = sort_by_dst(tmp, plan->col.p, sorted_src, iota, perm, nnz, srcs, st);
-        if (s != GN_OK) return s;
+        GN_OK_OR_RETURN(gn::sort_pairs(tmp, plan->col.p, sorted_src, iota, perm, (size_t)nnz, bits_for(srcs), st));
         k_fill_transpose<<<g, 256, 0, st>>>(perm, row_of, plan->coef.p, (int)nnz, plan->t_col.p, plan->t_coef.p);
         GN_LAUNCH_CHECK();
     }
-    k_rowptr<<<(int)gn::ceil_div(srcs + 1, 256), 256, 0, st>>>(sorted_src, (int)nnz, (int)srcs, plan->t_rowptr.p);
-    GN_LAUNCH_CHECK();
+    GN_OK_OR_RETURN(gn::first_at_least(sorted_src, nnz, srcs, plan->t_rowptr.p, st));
     GN_HIP(hipStreamSynchronize(st));       // scratch is freed on return
     plan->has_transpose = 1;
     return GN_OK;
@@ -568,78 +486,63 @@ gn_status gn_rgcn_plan_create_ex(const int64_t* src, const int64_t* dst, const i
             GN_HIP(hipStreamSynchronize(st));
         }
     }
-    int64_t cursor = 0;
-    for (int64_t r = 0; r < R; ++r) {
-        if (ranges[2 * r] != cursor || ranges[2 * r + 1] < ranges[2 * r])
-            return gn::fail(GN_ERR_INVALID_ARG, "range_list must tile [0,E) in relation order (row %lld is [%lld,%lld), expected start %lld)",
-                            (long long)r, (long long)ranges[2 * r], (long long)ranges[2 * r + 1], (long long)cursor);
-        cursor = ranges[2 * r + 1];
-    }
-    if (cursor != E)
-        return gn::fail(GN_ERR_INVALID_ARG, "range_list covers %lld edges but edge_index has %lld", (long long)cursor,
-                        (long long)E);
+    std::vector<int64_t> starts;
+    const gn::RangeTiling tiling = gn::range_starts(ranges.data(), R, E, starts);
+    if (const int64_t r = tiling.bad_row; r >= 0)
+        return gn::fail(GN_ERR_INVALID_ARG, "range_list must tile [0,E) in relation order (row %lld is [%lld,%lld), expected start %lld)",
+                        (long long)r, (long long)ranges[2 * r], (long long)ranges[2 * r + 1], (long long)tiling.covered);
+    GN_REQUIRE(tiling.covered == E, "range_list covers %lld edges but edge_index has %lld", (long long)tiling.covered, (long long)E);
 
     GN_LAP(nullptr);
-    gn_rgcn_plan* p = new gn_rgcn_plan();
-    auto bail = [&](gn_status s) { gn_rgcn_plan_destroy(p); return s; };
-#define GN_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return bail(gn::fail(GN_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e))); } while (0)
+    std::unique_ptr<gn_rgcn_plan> p(new gn_rgcn_plan());
     p->input_edges = E; p->edge_lo = lo; p->edge_hi = hi; p->shard_edges = hi - lo;
     p->num_nodes = N; p->num_relations = R;
     Temp tmp;
-    GN_TRY(tmp.reserve((size_t)24 * (size_t)(hi - lo) + (size_t)8 * (size_t)(N + R) + ((size_t)1 << 20)));
+    GN_HIP(tmp.reserve((size_t)24 * (size_t)(hi - lo) + (size_t)8 * (size_t)(N + R) + ((size_t)1 << 20)));
     int32_t *cnt, *err, *dst32, *sorted_dst;
     int64_t* starts_dev;
     uint32_t* key;
-    GN_TRY(tmp.get(&cnt, N));
-    GN_TRY(tmp.get(&err, 1));
-    GN_TRY(tmp.get(&dst32, p->shard_edges));
-    GN_TRY(tmp.get(&sorted_dst, p->shard_edges));
-    GN_TRY(tmp.get(&key, p->shard_edges));
-    GN_TRY(tmp.get(&starts_dev, R + 1));
-    GN_TRY(hipMemsetAsync(cnt, 0, (N ? N : 1) * sizeof(int32_t), st));
-    GN_TRY(hipMemsetAsync(err, 0, sizeof(int32_t), st));
-    std::vector<int64_t> starts(R + 1, E);
-    for (int64_t r = 0; r < R; ++r) starts[r] = ranges[2 * r];
-    GN_TRY(hipMemcpyAsync(starts_dev, starts.data(), (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    GN_TRY(p->indeg.alloc(N));
-    GN_TRY(p->rowptr.alloc(N + 1));
-    GN_TRY(p->key.alloc(p->shard_edges));
+    GN_HIP(tmp.get(&cnt, N));
+    GN_HIP(tmp.get(&err, 1));
+    GN_HIP(tmp.get(&dst32, p->shard_edges));
+    GN_HIP(tmp.get(&sorted_dst, p->shard_edges));
+    GN_HIP(tmp.get(&key, p->shard_edges));
+    GN_HIP(tmp.get(&starts_dev, R + 1));
+    GN_HIP(hipMemsetAsync(cnt, 0, (N ? N : 1) * sizeof(int32_t), st));
+    GN_HIP(hipMemsetAsync(err, 0, sizeof(int32_t), st));
+    GN_HIP(hipMemcpyAsync(starts_dev, starts.data(), (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    GN_HIP(p->indeg.alloc(N));
+    GN_HIP(p->rowptr.alloc(N + 1));
+    GN_HIP(p->key.alloc(p->shard_edges));
     if (E > 0) {
         k_indegree<<<gn::stream_grid(E, 256), 256, 0, st>>>(dst, E, N, cnt, err);
-        GN_TRY(hipGetLastError());
+        GN_LAUNCH_CHECK();
     }
     if (N > 0) {
         k_i32_to_f32<<<(int)gn::ceil_div(N, 256), 256, 0, st>>>(cnt, (int)N, p->indeg.p);
-        GN_TRY(hipGetLastError());
+        GN_LAUNCH_CHECK();
     }
     if (p->shard_edges > 0) {
         k_rel_keys<<<gn::stream_grid(p->shard_edges, 256), 256, 0, st>>>(src, dst, starts_dev, (int)R, lo, hi, N,
                                                                         dst32, key, err);
-        GN_TRY(hipGetLastError());
-        size_t bytes = 0;
-        GN_TRY(rocprim::radix_sort_pairs(nullptr, bytes, dst32, sorted_dst, key, p->key.p, (size_t)p->shard_edges, 0,
-                                         bits_for(N), st));
-        char* scratch = nullptr;
-        GN_TRY(tmp.get(&scratch, bytes));
-        GN_TRY(rocprim::radix_sort_pairs(scratch, bytes, dst32, sorted_dst, key, p->key.p, (size_t)p->shard_edges, 0,
-                                         bits_for(N), st));
+        GN_LAUNCH_CHECK();
+        GN_OK_OR_RETURN(gn::sort_pairs(tmp, dst32, sorted_dst, key, p->key.p, (size_t)p->shard_edges, bits_for(N), st));
     }
-    k_rowptr<<<(int)gn::ceil_div(N + 1, 256), 256, 0, st>>>(sorted_dst, (int)p->shard_edges, (int)N, p->rowptr.p);
-    GN_TRY(hipGetLastError());
+    GN_OK_OR_RETURN(gn::first_at_least(sorted_dst, p->shard_edges, N, p->rowptr.p, st));
     int32_t bad = 0;
     std::vector<int32_t> rp(N + 1);
-    GN_TRY(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GN_TRY(hipMemcpyAsync(rp.data(), p->rowptr.p, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    GN_TRY(hipStreamSynchronize(st));
+    GN_HIP(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipMemcpyAsync(rp.data(), p->rowptr.p, (N + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipStreamSynchronize(st));
     GN_LAP("rgcn: keys + sort + rowptr (sync)");
-    if (bad) return bail(gn::fail(GN_ERR_INDEX_RANGE, "edge_index holds a node id outside [0,%lld)", (long long)N));
+    if (bad) return gn::fail(GN_ERR_INDEX_RANGE, "edge_index holds a node id outside [0,%lld)", (long long)N);
     for (int64_t i = 0; i < N; ++i) p->max_row_nnz = std::max<int64_t>(p->max_row_nnz, rp[i + 1] - rp[i]);
     if (N > 0) {
         // rows by in-degree, largest first (layout_rgcn_basis.hpp: the row pointers are on the host anyway)
         std::vector<int32_t> order;
         gn_layout::degree_order(rp, order, p->heavy_rows);
-        GN_TRY(p->row_order.upload(order, st));
-        GN_TRY(hipStreamSynchronize(st));
+        GN_HIP(p->row_order.upload(order, st));
+        GN_HIP(hipStreamSynchronize(st));
     }
     {
         // the general weight gradient's work items (layout_rgcn_basis.hpp)
@@ -648,49 +551,25 @@ gn_status gn_rgcn_plan_create_ex(const int64_t* src, const int64_t* dst, const i
         p->n_dw_parts = dwl.parts;
         p->n_dw_multi = (int64_t)dwl.multi.size() / 4;
         if (p->n_dw_items > 0) {
-            GN_TRY(p->dw_items.upload(dwl.items, st));
-            if (p->n_dw_multi > 0) GN_TRY(p->dw_multi.upload(dwl.multi, st));
-            GN_TRY(hipStreamSynchronize(st));
+            GN_HIP(p->dw_items.upload(dwl.items, st));
+            if (p->n_dw_multi > 0) GN_HIP(p->dw_multi.upload(dwl.multi, st));
+            GN_HIP(hipStreamSynchronize(st));
         }
     }
     GN_LAP("rgcn: row order + dw items");
     if (!(flags & GN_RGCN_PLAN_LIGHT)) {
         // the encodings of the LDS-resident kernels (host-side schedules: most of the build time); a light plan serves every
         // forward on the general O(E) path, from the device-sorted key list above alone
-        gn_status fs = gn_rgcn_build_fast_segments(p, src, dst, ranges, st);
-        if (fs != GN_OK) return bail(fs);
+        GN_OK_OR_RETURN(gn_rgcn_build_fast_segments(p.get(), src, dst, starts_dev, st));
         GN_LAP("rgcn: LDS-accumulator segments (total)");
-        fs = gn_rgcn_build_pair_plan(p, src, dst, ranges, st);
-        if (fs != GN_OK) return bail(fs);
+        GN_OK_OR_RETURN(gn_rgcn_build_pair_plan(p.get(), src, dst, starts_dev, st));
         GN_LAP("rgcn: destination-major units (total)");
     }
-#undef GN_TRY
-    *out = p;
+    *out = p.release();
     return GN_OK;
 }
 
-void gn_rgcn_plan_destroy(gn_rgcn_plan* p) {
-    if (!p) return;
-    p->indeg.release();
-    p->rowptr.release();
-    p->key.release();
-    p->row_order.release();
-    p->dw_items.release();
-    p->dw_multi.release();
-    p->seg_rel.release();
-    p->item_tile.release();
-    p->seg_begin.release();
-    p->packed.release();
-    p->wg_begin.release();
-    p->wg_items.release();
-    p->pair_stream.release();
-    p->pair_wave_first.release();
-    p->pair_desc.release();
-    p->pair_wave_units.release();
-    p->pair_wave_desc.release();
-    p->pair_wg_dst.release();
-    delete p;
-}
+void gn_rgcn_plan_destroy(gn_rgcn_plan* p) { delete p; }
 
 int64_t gn_rgcn_plan_input_edges(const gn_rgcn_plan* plan) { return plan ? plan->input_edges : -1; }
 

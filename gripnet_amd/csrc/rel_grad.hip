@@ -349,34 +349,25 @@ gn_status gn_rel_grad_plan_create(const gn_graph_plan* sums, int64_t num_nodes, 
     GN_HIP(hipStreamSynchronize(st));
     const gn_layout::RelGradLayout L = gn_layout::build_rel_grad_layout(rowptr.data(), col.data(), num_nodes, num_relations, gn::compute_units());
     if (!L.ok) return gn::fail(GN_ERR_UNSUPPORTED, "the (relation, source) layout does not fit its index types");
-    gn_rel_grad_plan* p = new gn_rel_grad_plan();
+    std::unique_ptr<gn_rel_grad_plan> p(new gn_rel_grad_plan());
     p->num_nodes = num_nodes; p->num_relations = num_relations; p->edges = sums->nnz;
     p->groups = L.groups; p->scratch_slots = L.scratch_slots; p->entries = (int)(L.entry.size() / 4);
     p->units = L.units;
-    hipError_t e = p->src.upload(L.src, st);
-    if (e == hipSuccess) e = p->ids.upload(L.ids, st);
-    if (e == hipSuccess) e = p->entry.upload(L.entry, st);
-    if (e == hipSuccess) e = p->wave_cnt.upload(L.wave_cnt, st);
-    if (e == hipSuccess) e = p->wg_off.upload(L.wg_off, st);
-    if (e == hipSuccess) e = p->wave_u0.upload(L.wave_u0, st);
-    if (e == hipSuccess) e = p->scratch.alloc((size_t)std::max(1, L.scratch_slots) * kRelMaxOutputs);
-    if (e == hipSuccess) e = p->ticket.alloc((size_t)num_relations);
-    if (e == hipSuccess) e = hipMemsetAsync(p->ticket.p, 0, (size_t)num_relations * 4, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                   // the host vectors go out of scope
-    if (e != hipSuccess) {
-        gn_rel_grad_plan_destroy(p);
-        return gn::fail(GN_ERR_HIP, "building the weight-gradient plan failed: %s", hipGetErrorString(e));
-    }
-    *out = p;
+    GN_HIP(p->src.upload(L.src, st));
+    GN_HIP(p->ids.upload(L.ids, st));
+    GN_HIP(p->entry.upload(L.entry, st));
+    GN_HIP(p->wave_cnt.upload(L.wave_cnt, st));
+    GN_HIP(p->wg_off.upload(L.wg_off, st));
+    GN_HIP(p->wave_u0.upload(L.wave_u0, st));
+    GN_HIP(p->scratch.alloc((size_t)std::max(1, L.scratch_slots) * kRelMaxOutputs));
+    GN_HIP(p->ticket.alloc((size_t)num_relations));
+    GN_HIP(hipMemsetAsync(p->ticket.p, 0, (size_t)num_relations * 4, st));
+    GN_HIP(hipStreamSynchronize(st));                   // the host vectors go out of scope
+    *out = p.release();
     return GN_OK;
 }
 
-void gn_rel_grad_plan_destroy(gn_rel_grad_plan* p) {
-    if (!p) return;
-    p->src.release(); p->ids.release(); p->entry.release(); p->wave_cnt.release(); p->wg_off.release(); p->wave_u0.release();
-    p->scratch.release(); p->ticket.release();
-    delete p;
-}
+void gn_rel_grad_plan_destroy(gn_rel_grad_plan* p) { delete p; }
 
 int gn_rel_weight_grad_supported(const gn_rel_grad_plan* plan, int64_t in_features, int64_t out_features) {
     if (!plan || gn::fast_paths_disabled()) return 0;

@@ -24,10 +24,8 @@
 // L2-resident.  The matrix-core time of (1), 2 N_tile x in x out flops per item at the fp32 MFMA
 // rate (256 flop/clk/CU), is the larger cost below ~10^4 edges per relation.
 #include "common.h"
-#include "layout_util.hpp"
-
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
+#include "layout_rgcn_fast.hpp"
+#include "plan_device.cuh"
 
 #include <algorithm>
 #include <numeric>
@@ -40,10 +38,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kFout = 32;                  // out_features of the layer this path is built for
 constexpr int kLpr = kFout / 4;            // float4 per full feature row (slab layout, finalisation)
 constexpr int kNB = 128;                   // destination slots per item = edges in flight per workgroup
-constexpr int kGroups = 256;               // persistent workgroups = CUs of an MI355X
-constexpr int kChunk = 4096;               // packed words per work item = LDS edge buffer (16 KB)
-constexpr int kItemEdges = kChunk - 3 * 128; // edges per work item: every slot list is padded to 4 words
-constexpr int kItemOverhead = 2048;        // H-tile cost in edge equivalents (LPT balancing)
+constexpr int kChunk = gn_layout::kFastChunk;     // packed words per work item = LDS edge buffer (16 KB)
+static_assert(gn_layout::kFastItemEdges == kChunk - 3 * kNB, "every slot list of an item is padded to 4 words");
 constexpr size_t kLdsBudget = 159 * 1024;
 constexpr size_t kLdsHalfBudget = 80 * 1024 - 512;   // two workgroups per CU (allocation granularity left over)
 constexpr int kMaxRowTilesPerWave = 3;
@@ -84,10 +80,7 @@ FastGeom geometry(int64_t n) {
     return g;
 }
 
-// One work item as the kernel reads it (32 bytes, wave-uniform scalar load).
-struct alignas(32) WorkDesc {
-    int32_t rel, tile, start, count, item, pad0, pad1, pad2;
-};
+using WorkDesc = gn_layout::FastWorkDesc;   // one work item as the kernel reads it (layout_rgcn_fast.hpp)
 
 struct FastArgs {
     const float* x; int64_t ld_x; int n;
@@ -111,6 +104,7 @@ struct FastDims { int64_t ld_x; int n; int ts; int groups; };
 
 #ifdef GN_STAMPS
 // Diagnostic build only (make STAMPS=1): per-workgroup phase times, never part of the product library.
+constexpr int kGroups = gn_layout::kFastGroups;
 __device__ unsigned long long g_stamps[2 * kGroups][8];
 __device__ unsigned long long g_wave_stamps[2 * kGroups][16][4];   // per wave: gather, top, trips, mfma
 #define GN_STAMP(var) unsigned long long var = __builtin_amdgcn_s_memtime()
@@ -499,36 +493,12 @@ __global__ void k_seg_keys(const int64_t* __restrict__ src, const int64_t* __res
                            const int64_t* __restrict__ range_start, int R, int64_t lo, int64_t hi, int ts, int tiles,
                            uint32_t* __restrict__ key, uint32_t* __restrict__ packed) {
     for (int64_t e = lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < hi; e += (int64_t)gridDim.x * blockDim.x) {
-        int a = 0, b = R;
-        while (b - a > 1) {
-            int mid = (a + b) >> 1;
-            if (range_start[mid] <= e) a = mid; else b = mid;
-        }
+        const int a = gn::last_start_le(range_start, R, e);
         const int s = (int)src[e], d = (int)dst[e];          // validated by the general plan builder
         const int tile = s / ts;
         key[e - lo] = (uint32_t)(a * tiles + tile);
         packed[e - lo] = ((uint32_t)d << 16) | (uint32_t)(s - tile * ts);
     }
-}
-
-__global__ void k_lower_bounds_u32(const uint32_t* __restrict__ sorted, int n, int count, int32_t* __restrict__ out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > count) return;
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (sorted[mid] < (uint32_t)i) lo = mid + 1; else hi = mid;
-    }
-    out[i] = lo;
-}
-
-__device__ __forceinline__ int item_of(const int32_t* __restrict__ item_begin, int n_items, int p) {
-    int a = 0, b = n_items;
-    while (b - a > 1) {
-        int mid = (a + b) >> 1;
-        if (item_begin[mid] <= p) a = mid; else b = mid;
-    }
-    return a;
 }
 
 // item_id[p] = work item that holds position p;  cnt[item, dst] += 1
@@ -537,7 +507,7 @@ __global__ void k_item_dst_counts(const uint32_t* __restrict__ packed, const int
                                   int32_t* __restrict__ cnt) {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const int it = item_of(item_begin, n_items, p);
+    const int it = gn::last_start_le(item_begin, n_items, p);
     item_id[p] = it;
     atomicAdd(&cnt[(int64_t)it * nodes + (packed[p] >> 16)], 1);
 }
@@ -578,12 +548,7 @@ __global__ void k_slot_offsets(const uint64_t* __restrict__ sorted, int n, int n
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i > n_items * kNB) return;
     const uint64_t target = ((uint64_t)(i / kNB) << 32) | ((uint64_t)(i % kNB) << 16);
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (sorted[mid] < target) lo = mid + 1; else hi = mid;
-    }
-    out[i] = lo;
+    out[i] = gn::lower_bound(sorted, n, target);
 }
 
 // sz[i] = length of slot list i rounded up to whole groups of 4 words (0 for the terminator)
@@ -608,32 +573,8 @@ __global__ void k_emit_padded(const uint64_t* __restrict__ key2_sorted, const ui
     out[pad_off[sg] + pos] = (packed_sorted[p] & 0x7fffffffu) | (end ? kEndFlag : 0u);
 }
 
-int bits_for(int64_t n) {
-    int b = 1;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
-
 using gn::Scratch;   // scoped device scratch (common.h)
-
-template <typename K, typename V>
-gn_status sort_pairs(Scratch& tmp, const K* kin, K* kout, const V* vin, V* vout, size_t n, int bits, hipStream_t st) {
-    size_t bytes = 0;
-    GN_HIP(rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0, bits, st));
-    char* scratch = nullptr;
-    GN_HIP(tmp.get(&scratch, bytes));
-    GN_HIP(rocprim::radix_sort_pairs(scratch, bytes, kin, kout, vin, vout, n, 0, bits, st));
-    return GN_OK;
-}
-
-gn_status sort_keys(Scratch& tmp, const uint64_t* kin, uint64_t* kout, size_t n, int bits, hipStream_t st) {
-    size_t bytes = 0;
-    GN_HIP(rocprim::radix_sort_keys(nullptr, bytes, kin, kout, n, 0, bits, st));
-    char* scratch = nullptr;
-    GN_HIP(tmp.get(&scratch, bytes));
-    GN_HIP(rocprim::radix_sort_keys(scratch, bytes, kin, kout, n, 0, bits, st));
-    return GN_OK;
-}
+using gn::bits_for;
 
 template <int FIN, int RT, int COLS>
 gn_status launch_main(const FastArgs& a, int groups, size_t lds_bytes, hipStream_t st) {
@@ -661,100 +602,48 @@ gn_status launch_main_cols(const FastArgs& a, int cols, int groups, size_t lds_b
                          : launch_main_rt<FIN, kFout / 2>(a, groups, lds_bytes, st);
 }
 
-}  // namespace
-
-// Builds the relation-major work items of the shard.  Leaves plan->fast_ok = 0 when the graph
-// does not qualify (too many nodes for the LDS accumulator, too many relations for the key).
-gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst,
-                                      const std::vector<int64_t>& ranges, hipStream_t st) {
-    plan->fast_ok = 0;
-    const int64_t N = plan->num_nodes, R = plan->num_relations, E = plan->shard_edges;
-    if (gn::fast_paths_disabled() || N < 1 || N > 32767 || R < 1 || E < 1) return GN_OK;
-    const FastGeom g = geometry(N);
-    if (g.tiles == 0 || R * g.tiles >= (1 << 20)) return GN_OK;
-
-    Scratch tmp;
-    GN_HIP(tmp.reserve((size_t)48 * (size_t)E + (size_t)8 * (size_t)(R * g.tiles + R) + ((size_t)1 << 20)));
-    int64_t* starts_dev;
-    uint32_t *key, *key_sorted, *packed, *packed_sorted;
+// ---- the plan's device stages (the host schedule between them: layout_rgcn_fast.hpp) ----
+// The shard's edges as packed words sorted by (relation, source tile); seg = the segments' offsets, on the host.  Synchronises.
+gn_status sort_segments(Scratch& tmp, const gn_rgcn_plan* plan, const FastGeom& g, const int64_t* src, const int64_t* dst,
+                        const int64_t* starts_dev, hipStream_t st, uint32_t** packed_sorted, std::vector<int32_t>& seg) {
+    const int64_t R = plan->num_relations, E = plan->shard_edges;
+    const int n_seg = (int)(R * g.tiles);
+    uint32_t *key, *key_sorted, *packed;
     int32_t* seg_off;
-    GN_HIP(tmp.get(&starts_dev, R + 1));
     GN_HIP(tmp.get(&key, E));
     GN_HIP(tmp.get(&key_sorted, E));
     GN_HIP(tmp.get(&packed, E));
-    GN_HIP(tmp.get(&packed_sorted, E));
-    const int n_seg = (int)(R * g.tiles);
+    GN_HIP(tmp.get(packed_sorted, E));
     GN_HIP(tmp.get(&seg_off, n_seg + 1));
-    std::vector<int64_t> starts(R + 1, plan->input_edges);
-    for (int64_t r = 0; r < R; ++r) starts[r] = ranges[2 * r];
-    GN_HIP(hipMemcpyAsync(starts_dev, starts.data(), (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
     k_seg_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(src, dst, starts_dev, (int)R, plan->edge_lo, plan->edge_hi,
                                                        g.ts, g.tiles, key, packed);
     GN_LAUNCH_CHECK();
-    gn_status s = sort_pairs(tmp, key, key_sorted, packed, packed_sorted, (size_t)E, bits_for(n_seg), st);
-    if (s != GN_OK) return s;
-    k_lower_bounds_u32<<<(int)gn::ceil_div(n_seg + 1, 256), 256, 0, st>>>(key_sorted, (int)E, n_seg, seg_off);
-    GN_LAUNCH_CHECK();
-    std::vector<int32_t> seg(n_seg + 1);
+    GN_OK_OR_RETURN(gn::sort_pairs(tmp, key, key_sorted, packed, *packed_sorted, (size_t)E, bits_for(n_seg), st));
+    GN_OK_OR_RETURN(gn::first_at_least(key_sorted, E, n_seg, seg_off, st));
+    seg.resize((size_t)n_seg + 1);
     GN_HIP(hipMemcpyAsync(seg.data(), seg_off, (n_seg + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
-    GN_LAP("  lds: segment keys + sort (sync)");
+    return GN_OK;
+}
 
-    // work items: every non-empty (relation, tile) segment, cut into chunks of <= kItemEdges edges
-    std::vector<int32_t> item_rel, item_tile, item_begin;
-    for (int sg = 0; sg < n_seg; ++sg) {
-        for (int32_t b = seg[sg]; b < seg[sg + 1]; b += kItemEdges) {
-            item_rel.push_back(sg / g.tiles);
-            item_tile.push_back(sg % g.tiles);
-            item_begin.push_back(b);
-        }
-    }
-    const int n_items = (int)item_rel.size();
-    item_begin.push_back((int32_t)E);
-    if ((int64_t)n_items * kNB >= (1ll << 31) || (int64_t)n_items * N >= (1ll << 31)) return GN_OK;
-    // Balancing unit = piece: up to `piece_chunks` consecutive items of one (relation, tile) segment.
-    // A workgroup that runs them back to back builds the segment's H tile once.
-    int64_t total_cost = 0;
-    for (int sg = 0; sg < n_seg; ++sg)
-        if (seg[sg + 1] > seg[sg]) total_cost += kItemOverhead + (seg[sg + 1] - seg[sg]);
-    const int groups0 = std::min(kGroups, std::max(n_items, 1));
-    const int64_t piece_cap = std::max<int64_t>(kItemOverhead + kItemEdges, total_cost / groups0 / 4);
-    const int piece_chunks = (int)std::max<int64_t>(1, (piece_cap - kItemOverhead) / kItemEdges);
-    std::vector<int32_t> piece_first, piece_count;
-    std::vector<int64_t> piece_cost;
-    for (int i = 0; i < n_items;) {
-        int jn = i + 1;
-        while (jn < n_items && jn - i < piece_chunks && item_rel[jn] == item_rel[i] && item_tile[jn] == item_tile[i]) ++jn;
-        piece_first.push_back(i);
-        piece_count.push_back(jn - i);
-        piece_cost.push_back((int64_t)kItemOverhead + (item_begin[jn] - item_begin[i]));
-        i = jn;
-    }
-    const int n_pieces = (int)piece_first.size();
-    const int groups = std::min(groups0, std::max(n_pieces, 1));
-    // longest-processing-time assignment of pieces to the persistent workgroups
-    const std::vector<int> order = gn_layout::descending_order<int>(n_pieces, [&](int x) { return piece_cost[x]; });
-    std::vector<std::vector<int32_t>> bins(groups);
-    {
-        std::vector<std::pair<int64_t, int>> heap;   // min-heap over (load, group)
-        for (int gidx = 0; gidx < groups; ++gidx) heap.emplace_back(0, gidx);
-        auto cmp = [](const std::pair<int64_t, int>& x, const std::pair<int64_t, int>& y) { return x > y; };
-        std::make_heap(heap.begin(), heap.end(), cmp);
-        for (int pc : order) {
-            std::pop_heap(heap.begin(), heap.end(), cmp);
-            auto& top = heap.back();
-            for (int k = 0; k < piece_count[pc]; ++k) bins[top.second].push_back(piece_first[pc] + k);
-            top.first += piece_cost[pc];
-            std::push_heap(heap.begin(), heap.end(), cmp);
-        }
-    }
-    GN_LAP("  lds: items, pieces, LPT (host)");
-    // destination -> slot assignment inside every item, balanced by edge count
+// Inside every item the destinations dealt to the kNB slots, heaviest first (balanced by edge count), and the edges sorted by
+// (item, slot, destination); every slot list padded to whole groups of 4 words: plan->seg_begin = the padded offsets,
+// item_pad = those of the items, on the host.  Synchronises.
+struct SlotLists {
+    uint64_t* key2_sorted;    // [E] (item << 32) | (slot << 16) | dst
+    uint32_t* packed_slot;    // [E] the packed words in that order
+    int32_t* slot_off;        // [n_items * kNB + 1] unpadded offsets of the slot lists
+};
+
+gn_status build_slot_lists(Scratch& tmp, gn_rgcn_plan* plan, const std::vector<int32_t>& item_begin, uint32_t* packed_sorted,
+                           hipStream_t st, SlotLists& sl, std::vector<int32_t>& item_pad) {
+    const int64_t N = plan->num_nodes, E = plan->shard_edges;
+    const int n_items = (int)item_begin.size() - 1, n_slots = n_items * kNB;
     const int64_t cells = (int64_t)n_items * N;
     // (everything the rest of the build asks for in one more block of the scratch)
     GN_HIP(tmp.reserve((size_t)cells * 40 + (size_t)E * 40 + (size_t)n_items * (kNB + 1) * 8 + ((size_t)2 << 20)));
-    int32_t *item_begin_dev, *item_id, *cnt;
-    uint64_t *rkey, *rkey_sorted, *key2, *key2_sorted;
+    int32_t *item_begin_dev, *item_id, *cnt, *pad_sz;
+    uint64_t *rkey, *rkey_sorted, *key2;
     uint8_t* slot_of;
     GN_HIP(tmp.get(&item_begin_dev, n_items + 1));
     GN_HIP(tmp.get(&item_id, E));
@@ -763,7 +652,7 @@ gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, co
     GN_HIP(tmp.get(&rkey_sorted, cells));
     GN_HIP(tmp.get(&slot_of, cells));
     GN_HIP(tmp.get(&key2, E));
-    GN_HIP(tmp.get(&key2_sorted, E));
+    GN_HIP(tmp.get(&sl.key2_sorted, E));
     GN_HIP(hipMemcpyAsync(item_begin_dev, item_begin.data(), (n_items + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
     GN_HIP(hipMemsetAsync(cnt, 0, cells * sizeof(int32_t), st));
     k_item_dst_counts<<<(int)gn::ceil_div(E, 256), 256, 0, st>>>(packed_sorted, item_begin_dev, n_items, (int)E, (int)N,
@@ -771,70 +660,73 @@ gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, co
     GN_LAUNCH_CHECK();
     k_rank_keys<<<(int)gn::ceil_div(cells, 256), 256, 0, st>>>(cnt, cells, (int)N, rkey);
     GN_LAUNCH_CHECK();
-    s = sort_keys(tmp, rkey, rkey_sorted, (size_t)cells, 32 + bits_for(n_items), st);
-    if (s != GN_OK) return s;
+    GN_OK_OR_RETURN(gn::sort_keys(tmp, rkey, rkey_sorted, (size_t)cells, 32 + bits_for(n_items), st));
     k_deal_slots<<<(int)gn::ceil_div(cells, 256), 256, 0, st>>>(rkey_sorted, cells, (int)N, slot_of);
     GN_LAUNCH_CHECK();
     k_item_keys<<<(int)gn::ceil_div(E, 256), 256, 0, st>>>(packed_sorted, item_id, slot_of, (int)E, (int)N, key2);
     GN_LAUNCH_CHECK();
-    uint32_t* packed_slot;
-    int32_t *slot_off, *pad_sz;
-    const int n_slots = n_items * kNB;
-    GN_HIP(tmp.get(&packed_slot, E));
-    GN_HIP(tmp.get(&slot_off, n_slots + 1));
+    GN_HIP(tmp.get(&sl.packed_slot, E));
+    GN_HIP(tmp.get(&sl.slot_off, n_slots + 1));
     GN_HIP(tmp.get(&pad_sz, n_slots + 1));
-    s = sort_pairs(tmp, key2, key2_sorted, packed_sorted, packed_slot, (size_t)E, 32 + bits_for(n_items), st);
-    if (s != GN_OK) return s;
-    k_slot_offsets<<<(int)gn::ceil_div((int64_t)n_slots + 1, 256), 256, 0, st>>>(key2_sorted, (int)E, n_items, slot_off);
+    GN_OK_OR_RETURN(gn::sort_pairs(tmp, key2, sl.key2_sorted, packed_sorted, sl.packed_slot, (size_t)E, 32 + bits_for(n_items), st));
+    k_slot_offsets<<<(int)gn::ceil_div((int64_t)n_slots + 1, 256), 256, 0, st>>>(sl.key2_sorted, (int)E, n_items, sl.slot_off);
     GN_LAUNCH_CHECK();
-    // every slot list padded to whole groups of 4 words: padded offsets = exclusive scan of the sizes
-    k_pad_sizes<<<(int)gn::ceil_div((int64_t)n_slots + 1, 256), 256, 0, st>>>(slot_off, n_slots, pad_sz);
+    // padded offsets = exclusive scan of the padded sizes
+    k_pad_sizes<<<(int)gn::ceil_div((int64_t)n_slots + 1, 256), 256, 0, st>>>(sl.slot_off, n_slots, pad_sz);
     GN_LAUNCH_CHECK();
     GN_HIP(plan->seg_begin.alloc((size_t)n_slots + 1));
-    {
-        size_t bytes = 0;
-        GN_HIP(rocprim::exclusive_scan(nullptr, bytes, pad_sz, plan->seg_begin.p, 0, (size_t)n_slots + 1,
-                                       rocprim::plus<int32_t>(), st));
-        char* scratch = nullptr;
-        GN_HIP(tmp.get(&scratch, bytes));
-        GN_HIP(rocprim::exclusive_scan(scratch, bytes, pad_sz, plan->seg_begin.p, 0, (size_t)n_slots + 1,
-                                       rocprim::plus<int32_t>(), st));
-    }
-    std::vector<int32_t> item_pad(n_items + 1);
+    GN_OK_OR_RETURN(gn::exclusive_scan_i32(tmp, pad_sz, plan->seg_begin.p, (size_t)n_slots + 1, st));
+    item_pad.resize((size_t)n_items + 1);
     GN_HIP(hipMemcpy2DAsync(item_pad.data(), sizeof(int32_t), plan->seg_begin.p, kNB * sizeof(int32_t), sizeof(int32_t),
                             (size_t)n_items + 1, hipMemcpyDeviceToHost, st));
     GN_HIP(hipStreamSynchronize(st));
-    GN_LAP("  lds: slots, two sorts, scan (sync)");
-    const int64_t padded = item_pad[n_items];
+    return GN_OK;
+}
+
+// plan->packed: every edge word at its padded position (padding word: dst 0, src 0, no flag).  Queued, no wait.
+gn_status emit_packed(gn_rgcn_plan* plan, const SlotLists& sl, int64_t padded, hipStream_t st) {
+    const int64_t E = plan->shard_edges;
     GN_HIP(plan->packed.alloc(padded + 8));
-    GN_HIP(hipMemsetAsync(plan->packed.p, 0, (padded + 8) * sizeof(uint32_t), st));   // padding word: dst 0, src 0, no flag
-    k_emit_padded<<<(int)gn::ceil_div(E, 256), 256, 0, st>>>(key2_sorted, packed_slot, slot_off, plan->seg_begin.p, (int)E,
+    GN_HIP(hipMemsetAsync(plan->packed.p, 0, (padded + 8) * sizeof(uint32_t), st));
+    k_emit_padded<<<(int)gn::ceil_div(E, 256), 256, 0, st>>>(sl.key2_sorted, sl.packed_slot, sl.slot_off, plan->seg_begin.p, (int)E,
                                                             plan->packed.p);
     GN_LAUNCH_CHECK();
-    // per workgroup: all items of one source tile together (the X fragments stay in registers),
-    // relation order inside a tile (W_r reuse in L2)
-    std::vector<int32_t> wg_begin(groups + 1, 0);
-    std::vector<WorkDesc> work;
-    work.reserve(n_items);
-    for (int gidx = 0; gidx < groups; ++gidx) {
-        std::sort(bins[gidx].begin(), bins[gidx].end(), [&](int32_t x, int32_t y) {
-            return item_tile[x] != item_tile[y] ? item_tile[x] < item_tile[y] : x < y;
-        });
-        for (int32_t it : bins[gidx]) {
-            WorkDesc w = {item_rel[it], item_tile[it], item_pad[it], item_pad[it + 1] - item_pad[it], it, 0, 0, 0};
-            work.push_back(w);
-        }
-        wg_begin[gidx + 1] = (int32_t)work.size();
-    }
+    return GN_OK;
+}
 
-    GN_HIP(plan->wg_begin.upload(wg_begin, st));
-    GN_HIP(plan->wg_items.upload(work.data(), work.size() * (sizeof(WorkDesc) / sizeof(int32_t)), st));
+}  // namespace
+
+// Builds the relation-major work items of the shard.  Leaves plan->fast_ok = 0 when the graph
+// does not qualify (too many nodes for the LDS accumulator, too many relations for the key).
+gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst,
+                                      const int64_t* starts_dev, hipStream_t st) {
+    plan->fast_ok = 0;
+    const int64_t N = plan->num_nodes, R = plan->num_relations, E = plan->shard_edges;
+    if (gn::fast_paths_disabled() || N < 1 || N > 32767 || R < 1 || E < 1) return GN_OK;
+    const FastGeom g = geometry(N);
+    if (g.tiles == 0 || R * g.tiles >= (1 << 20)) return GN_OK;
+
+    Scratch tmp;
+    GN_HIP(tmp.reserve((size_t)48 * (size_t)E + (size_t)8 * (size_t)(R * g.tiles + R) + ((size_t)1 << 20)));
+    uint32_t* packed_sorted;
+    std::vector<int32_t> seg, item_pad;
+    GN_OK_OR_RETURN(sort_segments(tmp, plan, g, src, dst, starts_dev, st, &packed_sorted, seg));
+    GN_LAP("  lds: segment keys + sort (sync)");
+    // (n_items * kNB and n_items * N are 32-bit indices of the stages below)
+    const gn_layout::FastItems items = gn_layout::build_fast_items(seg, g.tiles, E, INT32_MAX / std::max<int64_t>(kNB, N));
+    if (items.groups == 0) return GN_OK;
+    GN_LAP("  lds: items, pieces, LPT (host)");
+    SlotLists sl;
+    GN_OK_OR_RETURN(build_slot_lists(tmp, plan, items.item_begin, packed_sorted, st, sl, item_pad));
+    GN_LAP("  lds: slots, two sorts, scan (sync)");
+    GN_OK_OR_RETURN(emit_packed(plan, sl, item_pad.back(), st));
+    const gn_layout::FastWork work = gn_layout::build_fast_work(items, item_pad);      // (while the device emits)
+    GN_HIP(plan->wg_begin.upload(work.wg_begin, st));
+    GN_HIP(plan->wg_items.upload(work.desc, st));
     GN_HIP(hipStreamSynchronize(st));       // host vectors go out of scope after this
     GN_LAP("  lds: emit + descriptors (sync)");
-    plan->n_seg = n_items;
-    plan->fast_groups = groups;
+    plan->fast_groups = items.groups;
     plan->fast_ts = g.ts;
-    plan->fast_ts_pad = g.ts;
     plan->fast_lds_bytes = g.lds_bytes;
     plan->fast_cols = g.cols;
     plan->fast_ok = 1;

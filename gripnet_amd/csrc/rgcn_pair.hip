@@ -21,8 +21,7 @@
 // order as fp32's own rounding.  GN_RGCN_ARITH_FAST keeps two terms and three products (<= 2^-16 per product).
 #include "common.h"
 #include "layout_rgcn_pair.hpp"
-
-#include <rocprim/rocprim.hpp>
+#include "plan_device.cuh"
 
 #include <numeric>
 
@@ -690,34 +689,12 @@ __global__ void k_pair_keys(const int64_t* __restrict__ src, const int64_t* __re
                             const int64_t* __restrict__ starts, int R, int64_t lo, int64_t hi, int kpad,
                             const int32_t* __restrict__ kpos, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     for (int64_t e = lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < hi; e += (int64_t)gridDim.x * blockDim.x) {
-        int a = 0, b = R;                                                      // relation of edge e: last start <= e
-        while (b - a > 1) {
-            const int mid = (a + b) >> 1;
-            if (starts[mid] <= e) a = mid; else b = mid;
-        }
         key[e - lo] = (uint32_t)(dst[e] * kpad + kpos[src[e]]);
-        val[e - lo] = (uint32_t)a;
+        val[e - lo] = (uint32_t)gn::last_start_le(starts, R, e);               // relation of edge e
     }
-}
-
-__global__ void k_pair_rowptr(const uint32_t* __restrict__ sorted, int n, int64_t count, int32_t* __restrict__ out) {
-    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i > count) return;
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (sorted[mid] < (uint32_t)i) lo = mid + 1; else hi = mid;
-    }
-    out[i] = lo;
 }
 
 using gn::Scratch;   // scoped device scratch (common.h)
-
-int bits_for(int64_t n) {
-    int b = 1;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
 
 bool pair_disabled() { return gn::fast_paths_disabled(); }     // (a kernel is chosen by flag, GN_RGCN_PATH_*; GN_DISABLE_FAST=1 turns every fast path off)
 
@@ -761,7 +738,7 @@ gn_status dispatch_pair(const gn_rgcn_plan* plan, const PairArgs& a, int nt, int
 // Builds the per-workgroup destination lists and per-wave streams of the shard.  Leaves plan->pair_ok = 0 when the graph
 // does not qualify (too many nodes for three rows per compute unit, an att table beyond the LDS, nothing to do).
 gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst,
-                                  const std::vector<int64_t>& ranges, hipStream_t st) {
+                                  const int64_t* starts_dev, hipStream_t st) {
     plan->pair_ok = 0;
     const int64_t N = plan->num_nodes, R = plan->num_relations, E = plan->shard_edges;
     if (pair_disabled() || N < 1 || R < 1) return GN_OK;
@@ -777,10 +754,8 @@ gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const 
     gn::ArenaHold arena;                                       // (before every host array of this build: host_parallel.hpp)
     Scratch tmp;
     GN_HIP(tmp.reserve((size_t)24 * (size_t)E + (size_t)4 * (size_t)N * kpad + (size_t)8 * (size_t)(N + R) + ((size_t)1 << 20)));
-    int64_t* starts_dev;
     int32_t *outdeg_dev, *kpos_dev, *rowptr_dev;
     uint32_t *key, *key_sorted, *val, *val_sorted;
-    GN_HIP(tmp.get(&starts_dev, R + 1));
     GN_HIP(tmp.get(&outdeg_dev, N));
     GN_HIP(tmp.get(&kpos_dev, N));
     GN_HIP(tmp.get(&key, E));
@@ -806,20 +781,12 @@ gn_status gn_rgcn_build_pair_plan(gn_rgcn_plan* plan, const int64_t* src, const 
     std::vector<int32_t> rp((size_t)N * kpad + 1, 0);
     std::vector<uint32_t> rels(E);
     if (E > 0) {
-        std::vector<int64_t> starts(R + 1, plan->input_edges);
-        for (int64_t r = 0; r < R; ++r) starts[r] = ranges[2 * r];
-        GN_HIP(hipMemcpyAsync(starts_dev, starts.data(), (R + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
         GN_HIP(hipMemcpyAsync(kpos_dev, kpos.data(), N * sizeof(int32_t), hipMemcpyHostToDevice, st));
         k_pair_keys<<<gn::stream_grid(E, 256), 256, 0, st>>>(src, dst, starts_dev, (int)R, plan->edge_lo, plan->edge_hi, kpad,
                                                              kpos_dev, key, val);
         GN_LAUNCH_CHECK();
-        size_t bytes = 0;
-        GN_HIP(rocprim::radix_sort_pairs(nullptr, bytes, key, key_sorted, val, val_sorted, (size_t)E, 0, bits_for(N * kpad), st));
-        char* scratch = nullptr;
-        GN_HIP(tmp.get(&scratch, bytes));
-        GN_HIP(rocprim::radix_sort_pairs(scratch, bytes, key, key_sorted, val, val_sorted, (size_t)E, 0, bits_for(N * kpad), st));
-        k_pair_rowptr<<<(int)gn::ceil_div(N * kpad + 1, 256), 256, 0, st>>>(key_sorted, (int)E, N * kpad, rowptr_dev);
-        GN_LAUNCH_CHECK();
+        GN_OK_OR_RETURN(gn::sort_pairs(tmp, key, key_sorted, val, val_sorted, (size_t)E, gn::bits_for(N * kpad), st));
+        GN_OK_OR_RETURN(gn::first_at_least(key_sorted, E, N * kpad, rowptr_dev, st));
         GN_HIP(hipMemcpyAsync(rp.data(), rowptr_dev, ((size_t)N * kpad + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
         GN_HIP(hipMemcpyAsync(rels.data(), val_sorted, (size_t)E * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         GN_HIP(hipStreamSynchronize(st));

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 161 /* 0.1.55 */
+#define GN_VERSION 162 /* 0.1.56 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -76,6 +76,9 @@ typedef struct gn_rgcn_plan gn_rgcn_plan;   /* multi-relational graph of one sup
 GN_API int gn_version(void);
 /* Message of the last failing call made by this thread ("" if none). */
 GN_API const char* gn_last_error(void);
+/* Device allocations the library holds right now: the buffers of every live plan, sampler and known-pair set plus the
+ * scratch blocks of a builder that is running.  Back to its earlier value once a handle is destroyed or a create fails. */
+GN_API int64_t gn_device_blocks_live(void);
 
 /* ---------------------------------------------------------------------------------------
  * GCN-style normalised graph.  Replaces myGCN.norm + its cache (gripnet/layers.py:52-69,

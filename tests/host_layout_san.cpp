@@ -294,6 +294,153 @@ gn_layout::PairLayout pair_case(int64_t N, int64_t R, int64_t E, unsigned seed, 
     return L;
 }
 
+// ---- relational layer: LDS-accumulator work items ----------------------------------------------------------------------------
+#if __has_include("layout_rgcn_fast.hpp")
+using gn_layout::FastItems;
+using gn_layout::FastWork;
+using gn_layout::build_fast_items;
+using gn_layout::build_fast_work;
+using gn_layout::kFastItemEdges;
+using gn_layout::kFastItemOverhead;
+#else
+// (a tree from before layout_rgcn_fast.hpp: the same loops as they stood in gn_rgcn_build_fast_segments, for the digest comparison)
+constexpr int kFastItemEdges = 4096 - 3 * 128, kFastItemOverhead = 2048;
+struct FastItems {
+    std::vector<int32_t> item_rel, item_tile, item_begin, piece_first, piece_group;
+    int groups = 0;
+    int n_items() const { return (int)item_rel.size(); }
+    int n_pieces() const { return (int)piece_group.size(); }
+    int64_t piece_cost(int pc) const { return (int64_t)kFastItemOverhead + (item_begin[piece_first[pc + 1]] - item_begin[piece_first[pc]]); }
+};
+struct FastWork { std::vector<int32_t> wg_begin, desc; };
+FastItems build_fast_items(const std::vector<int32_t>& seg, int tiles, int64_t E) {
+    const int kGroups = 256, kItemEdges = kFastItemEdges, kItemOverhead = kFastItemOverhead;
+    const int n_seg = (int)seg.size() - 1;
+    FastItems L;
+    std::vector<int32_t>&item_rel = L.item_rel, &item_tile = L.item_tile, &item_begin = L.item_begin;
+    for (int sg = 0; sg < n_seg; ++sg) {
+        for (int32_t b = seg[sg]; b < seg[sg + 1]; b += kItemEdges) {
+            item_rel.push_back(sg / tiles);
+            item_tile.push_back(sg % tiles);
+            item_begin.push_back(b);
+        }
+    }
+    const int n_items = (int)item_rel.size();
+    item_begin.push_back((int32_t)E);
+    int64_t total_cost = 0;
+    for (int sg = 0; sg < n_seg; ++sg)
+        if (seg[sg + 1] > seg[sg]) total_cost += kItemOverhead + (seg[sg + 1] - seg[sg]);
+    const int groups0 = std::min(kGroups, std::max(n_items, 1));
+    const int64_t piece_cap = std::max<int64_t>(kItemOverhead + kItemEdges, total_cost / groups0 / 4);
+    const int piece_chunks = (int)std::max<int64_t>(1, (piece_cap - kItemOverhead) / kItemEdges);
+    std::vector<int32_t> piece_first, piece_count;
+    std::vector<int64_t> piece_cost;
+    for (int i = 0; i < n_items;) {
+        int jn = i + 1;
+        while (jn < n_items && jn - i < piece_chunks && item_rel[jn] == item_rel[i] && item_tile[jn] == item_tile[i]) ++jn;
+        piece_first.push_back(i);
+        piece_count.push_back(jn - i);
+        piece_cost.push_back((int64_t)kItemOverhead + (item_begin[jn] - item_begin[i]));
+        i = jn;
+    }
+    const int n_pieces = (int)piece_first.size();
+    const int groups = std::min(groups0, std::max(n_pieces, 1));
+    const std::vector<int> order = gn_layout::descending_order<int>(n_pieces, [&](int x) { return piece_cost[x]; });
+    L.piece_group.assign((size_t)n_pieces, 0);
+    {
+        std::vector<std::pair<int64_t, int>> heap;   // min-heap over (load, group)
+        for (int gidx = 0; gidx < groups; ++gidx) heap.emplace_back(0, gidx);
+        auto cmp = [](const std::pair<int64_t, int>& x, const std::pair<int64_t, int>& y) { return x > y; };
+        std::make_heap(heap.begin(), heap.end(), cmp);
+        for (int pc : order) {
+            std::pop_heap(heap.begin(), heap.end(), cmp);
+            auto& top = heap.back();
+            L.piece_group[pc] = top.second;
+            top.first += piece_cost[pc];
+            std::push_heap(heap.begin(), heap.end(), cmp);
+        }
+    }
+    L.piece_first = piece_first;
+    L.piece_first.push_back(n_items);
+    L.groups = groups;
+    return L;
+}
+FastWork build_fast_work(const FastItems& L, const std::vector<int32_t>& item_pad) {
+    const int groups = L.groups;
+    std::vector<std::vector<int32_t>> bins(groups);
+    for (int pc = 0; pc < L.n_pieces(); ++pc)
+        for (int32_t it = L.piece_first[pc]; it < L.piece_first[pc + 1]; ++it) bins[L.piece_group[pc]].push_back(it);
+    FastWork W;
+    W.wg_begin.assign((size_t)groups + 1, 0);
+    for (int gidx = 0; gidx < groups; ++gidx) {
+        std::sort(bins[gidx].begin(), bins[gidx].end(), [&](int32_t x, int32_t y) {
+            return L.item_tile[x] != L.item_tile[y] ? L.item_tile[x] < L.item_tile[y] : x < y;
+        });
+        for (int32_t it : bins[gidx]) {
+            const int32_t w[8] = {L.item_rel[it], L.item_tile[it], item_pad[it], item_pad[it + 1] - item_pad[it], it, 0, 0, 0};
+            W.desc.insert(W.desc.end(), w, w + 8);
+        }
+        W.wg_begin[gidx + 1] = (int32_t)(W.desc.size() / 8);
+    }
+    return W;
+}
+#endif
+
+// R x tiles segments over E sorted edges (a hub relation, empty segments), the items' padded offsets as the device scan would
+// give them.  Every item sits in exactly one workgroup; the workgroups' loads differ by at most the largest piece (each piece
+// went to the least loaded one); a workgroup's descriptors are sorted by tile, then item, and name their item's words.
+std::pair<FastItems, FastWork> fast_case(int64_t R, int tiles, int64_t E, unsigned seed) {
+    std::mt19937_64 rng(seed);
+    const int n_seg = (int)(R * tiles);
+    std::vector<int32_t> seg((size_t)n_seg + 1, 0);
+    for (int64_t e = 0; e < E; ++e) {
+        const int64_t sg = e < E / 3 ? (int64_t)(rng() % (uint64_t)tiles) : (int64_t)(rng() % (uint64_t)n_seg);   // relation 0 is a hub
+        if (sg % 7 != 3 || n_seg < 8) seg[(size_t)sg + 1]++; else seg[1]++;                                     // (empty segments)
+    }
+    for (int sg = 0; sg < n_seg; ++sg) seg[(size_t)sg + 1] += seg[(size_t)sg];
+    CHECK(seg[(size_t)n_seg] == E);
+    const FastItems L = build_fast_items(seg, tiles, E);
+    const int n_items = L.n_items(), n_pieces = L.n_pieces();
+    CHECK((int)L.item_begin.size() == n_items + 1 && L.item_begin[(size_t)n_items] == E && (int)L.piece_first.size() == n_pieces + 1);
+    CHECK(L.groups >= 1 && L.groups <= 256 && L.groups <= std::max(n_pieces, 1));
+    for (int i = 0; i < n_items; ++i) {
+        const int sg = L.item_rel[i] * tiles + L.item_tile[i];
+        const int32_t len = L.item_begin[(size_t)i + 1] - L.item_begin[i];
+        CHECK(L.item_tile[i] >= 0 && L.item_tile[i] < tiles && L.item_rel[i] >= 0 && L.item_rel[i] < R);
+        CHECK(len >= 1 && len <= kFastItemEdges && L.item_begin[i] >= seg[sg] && L.item_begin[(size_t)i + 1] <= seg[(size_t)sg + 1]);
+    }
+    // pieces: consecutive items of one segment; loads: the least loaded workgroup took every piece in turn
+    std::vector<int64_t> load((size_t)L.groups, 0);
+    int64_t largest = 0;
+    CHECK(L.piece_first[0] == 0 && L.piece_first[(size_t)n_pieces] == n_items);
+    for (int pc = 0; pc < n_pieces; ++pc) {
+        CHECK(L.piece_first[(size_t)pc + 1] > L.piece_first[pc] && L.piece_group[pc] >= 0 && L.piece_group[pc] < L.groups);
+        for (int32_t it = L.piece_first[pc]; it < L.piece_first[(size_t)pc + 1]; ++it)
+            CHECK(L.item_rel[it] == L.item_rel[L.piece_first[pc]] && L.item_tile[it] == L.item_tile[L.piece_first[pc]]);
+        load[(size_t)L.piece_group[pc]] += L.piece_cost(pc);
+        largest = std::max(largest, L.piece_cost(pc));
+    }
+    if (n_pieces > 0) CHECK(*std::max_element(load.begin(), load.end()) - *std::min_element(load.begin(), load.end()) <= largest);
+    std::vector<int32_t> item_pad((size_t)n_items + 1, 0);
+    for (int i = 0; i < n_items; ++i)
+        item_pad[(size_t)i + 1] = item_pad[i] + ((L.item_begin[(size_t)i + 1] - L.item_begin[i] + 3 * (int32_t)(rng() % 128) + 3) & ~3);
+    const FastWork W = build_fast_work(L, item_pad);
+    CHECK((int)W.wg_begin.size() == L.groups + 1 && W.wg_begin[0] == 0 && W.wg_begin[(size_t)L.groups] == n_items && W.desc.size() == (size_t)n_items * 8);
+    std::vector<int> seen((size_t)n_items, 0);
+    for (int g = 0; g < L.groups; ++g)
+        for (int32_t k = W.wg_begin[g]; k < W.wg_begin[(size_t)g + 1]; ++k) {
+            const int32_t* d = W.desc.data() + (size_t)k * 8;
+            const int32_t it = d[4];
+            CHECK(it >= 0 && it < n_items);
+            seen[it]++;
+            CHECK(d[0] == L.item_rel[it] && d[1] == L.item_tile[it] && d[2] == item_pad[it] && d[3] == item_pad[(size_t)it + 1] - item_pad[it]);
+            CHECK(d[5] == 0 && d[6] == 0 && d[7] == 0);
+            if (k > W.wg_begin[g]) CHECK(d[-7] < d[1] || (d[-7] == d[1] && d[-4] < d[4]));      // by tile, then item
+        }
+    for (int i = 0; i < n_items; ++i) CHECK(seen[i] == 1);
+    return {L, W};
+}
+
 // ---- gene layers: LDS-staged gather ----------------------------------------------------------------------------------------
 gn_layout::BlockedLayout blocked_case(int64_t N, int deg, int R, unsigned seed, bool check) {
     std::mt19937_64 rng(seed);
@@ -496,6 +643,7 @@ const int64_t kWindowCases[] = {(int64_t)8 << 10, (int64_t)40 << 10};     // an 
 const struct { int64_t n; int R; int64_t e; } kPhaseCases[] = {{645, 40, 20000}, {645, 7, 3000}, {30, 2, 5}};   // (the last: fewer than 64 scored edges)
 const struct { int64_t N, R, E; } kPairCases[] = {{645, 30, 60000}, {200, 5, 9000}, {1, 1, 300}, {300, 964, 20000}};
 const struct { int64_t N; int deg, R; } kBlockedCases[] = {{5000, 16, 32}, {700, 3, 11}, {19081, 38, 32}};
+const struct { int64_t R; int tiles; int64_t E; } kFastCases[] = {{30, 2, 2000000}, {964, 1, 400000}, {3, 1, 300}, {5, 4, 9000}, {1, 1, 1}};
 const struct { int64_t n, R, E; int groups; } kRelGradCases[] = {{645, 40, 200000, 256}, {100, 7, 5000, 256}, {37, 3, 10, 8}, {300, 964, 60000, 64}};
 
 void general_cases() {
@@ -533,6 +681,12 @@ void digest_all(int threads) {
         const gn_layout::PairLayout L = pair_case(c.N, c.R, c.E, 11, true);
         std::snprintf(name, sizeof name, "pair %lld/%lld/%lld", (long long)c.N, (long long)c.R, (long long)c.E);
         emit(name, {fnv(L.stream), fnv(L.wave_first), fnv(L.desc), fnv(L.wave_units), fnv(L.wave_desc), fnv(L.wg_dst), (uint64_t)L.blocks});
+    }
+    for (auto& c : kFastCases) {
+        const std::pair<FastItems, FastWork> L = fast_case(c.R, c.tiles, c.E, 19);
+        std::snprintf(name, sizeof name, "rgcn_fast %lld/%d/%lld", (long long)c.R, c.tiles, (long long)c.E);
+        emit(name, {fnv(L.first.item_rel), fnv(L.first.item_tile), fnv(L.first.item_begin), fnv(L.first.piece_first), fnv(L.first.piece_group),
+                    (uint64_t)L.first.groups, fnv(L.second.wg_begin), fnv(L.second.desc)});
     }
     for (auto& c : kBlockedCases) {
         const gn_layout::BlockedLayout L = blocked_case(c.N, c.deg, c.R, 13, true);
@@ -612,6 +766,21 @@ int main(int argc, char** argv) {
         gn_layout::PairLayout b = pair_case(c.N, c.R, c.E, 11, true);
         CHECK(same(a.stream, b.stream) && same(a.desc, b.desc) && same(a.wave_first, b.wave_first) && same(a.wave_units, b.wave_units) &&
               same(a.wave_desc, b.wave_desc) && same(a.wg_dst, b.wg_dst));
+    }
+#if __has_include("layout_rgcn_fast.hpp")
+    {   // more items than the caller's 32-bit indices hold: nothing behind the items is built
+        const FastItems refused = build_fast_items({0, 3 * kFastItemEdges}, 1, 3 * kFastItemEdges, 2);
+        CHECK(refused.n_items() == 3 && refused.groups == 0 && refused.piece_first.empty());
+        CHECK(build_fast_items({0, 3 * kFastItemEdges}, 1, 3 * kFastItemEdges, 3).groups >= 1);
+    }
+#endif
+    for (auto& c : kFastCases) {
+        set_threads(1);
+        const std::pair<FastItems, FastWork> a = fast_case(c.R, c.tiles, c.E, 19);
+        set_threads(16);
+        const std::pair<FastItems, FastWork> b = fast_case(c.R, c.tiles, c.E, 19);
+        CHECK(same(a.first.item_begin, b.first.item_begin) && same(a.first.piece_group, b.first.piece_group) && a.first.groups == b.first.groups &&
+              same(a.second.wg_begin, b.second.wg_begin) && same(a.second.desc, b.second.desc));
     }
     for (auto& c : kBlockedCases) {
         set_threads(1);
