@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 162                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 163                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -54,6 +54,8 @@ SIGNATURES = {
     "gn_graph_transform_fusable": (_int, [_p, _i64, _i64]),
     "gn_graph_plan_build_blocked": (_int, [_p, _i64, _p]),
     "gn_graph_plan_blocked_cols": (_i64, [_p]),
+    "gn_graph_plan_blocked_gather_kernel": (_int, [_p]),
+    "gn_graph_plan_blocked_waves": (_i64, [_p, _p, _i64]),
     "gn_graph_blocked_applicable": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _i64]),
     "gn_graph_chain_applicable": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _p, _i64, _p]),
     "gn_graph_aggregate_chain_f32": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _p, _p]),
@@ -376,7 +378,7 @@ def replay(calls):
 # Test hooks the library reads from the environment at call time (common.h, aggregate.cuh, gcn_blocked.hip): part of every
 # memo key, so that a shortcut recorded under one setting is not replayed under another.
 _ENV_HOOKS = ("GN_DISABLE_FAST", "GN_DISABLE_QUAD", "GN_DISABLE_BLOCKED", "GN_BLOCKED_ANY", "GN_DISABLE_LDS_TABLE",
-              "GN_ENABLE_CHAIN")
+              "GN_ENABLE_CHAIN", "GN_BLOCKED_DIRECT")
 # hooks the C side reads that can NOT change what a memoised inference forward launches: the host threads of the plan builders
 # (plans do not depend on them), the sampler's kernel choice (same draws; no module forward calls the sampler) and the slab size of the
 # general relational path (read inside the entry point at every call: a slab is a range of rows, the bits do not depend on it).
@@ -760,6 +762,25 @@ class GraphPlan(Handle):
     @property
     def blocked_cols(self) -> int:
         return int(load().gn_graph_plan_blocked_cols(self._h))
+
+    @property
+    def blocked_gather_kernel(self) -> str:
+        """The gather kernel the LDS-staged path launches for this plan: "staged", "direct" or "" (no such encoding)."""
+        return ("", "staged", "direct")[int(load().gn_graph_plan_blocked_gather_kernel(self._h))]
+
+    def blocked_waves(self) -> torch.Tensor:
+        """[ranges, 16, 2] int64 on the CPU: (tiles, id-stream iterations) of every wave of every range's workgroup.
+        (16 waves of 12 ints: the record gn_graph_plan_blocked_waves documents in include/gripnet_hip.h, kColWaves and
+        kWaveInts of gcn_blocked.hip; a count that is no multiple of them raises here.)"""
+        lib = load()
+        n = int(lib.gn_graph_plan_blocked_waves(self._h, None, 0))
+        cell = torch.zeros((n,), dtype=torch.int32)
+        if n and lib.gn_graph_plan_blocked_waves(self._h, cell.data_ptr(), n) != n:
+            raise GripNetHipError(GN_ERR_HIP, "gn_graph_plan_blocked_waves failed")
+        if n % (16 * 12):
+            raise GripNetHipError(GN_ERR_HIP, "gn_graph_plan_blocked_waves: {} ints are no whole number of 16 x 12 records".format(n))
+        cell = cell.view(-1, 16, 12).long()
+        return torch.stack([cell[:, :, 1] - cell[:, :, 0], cell[:, :, 3] - cell[:, :, 2]], dim=2)
 
     def blocked_ok(self, x: torch.Tensor, weight: torch.Tensor, bias, out: torch.Tensor) -> bool:
         """True when gn_graph_aggregate_f32(x, weight=W, bias, out) runs on the source-blocked kernels (the library's own

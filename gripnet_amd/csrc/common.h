@@ -253,6 +253,7 @@ struct gn_graph_plan {
     int blk_rows = 0;                    // rows of one column group of the table (nodes + the zero row, padded to 1 KB pieces)
     int blk_cells = 0;                   // ranges of destination rows (workgroups per column group)
     int64_t blk_iters = 0;               // 512-byte iterations of the id stream
+    int blk_range_tiles = 0;             // tiles of the largest range (the staged gather parks a range's tile sums in LDS)
     gn::DevBuf<float> blk_dis;           // [blk_rows + 16] dis, zero padded
     gn::DevBuf<int32_t> blk_tile_off;    // [tiles + 4] first iteration of every tile
     gn::DevBuf<int32_t> blk_tile_rows;   // [tiles + 4][16] destination row of every quad of a tile (-1: none)

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "common.h"
+#include "dpp.cuh"
 
 namespace gn_dm {
 
@@ -18,13 +19,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 
-// quad_perm controls write every lane, so no "old" value has to be set up in front of the DPP move
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int x) { return __builtin_amdgcn_mov_dpp(x, CTRL, 0xf, 0xf, true); }
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x) {
-    return x + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
+using gn::dpp_i;
+using gn::dpp_add;
 // sum over the 16 lanes of a DPP row, result in every lane
 __device__ __forceinline__ float row_sum16(float x) {
     x = dpp_add<0xB1>(x);    // quad_perm [1,0,3,2]

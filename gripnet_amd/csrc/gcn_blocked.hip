@@ -29,6 +29,7 @@
 // launch took 3.8 + 11.2 + 5.5 us per layer - the 10 MB of partial sums are flushed at one kernel boundary and read back
 // behind the next - against 19.2 / 14.7 us for the wave-per-row kernels.)
 #include "aggregate.cuh"
+#include "dpp.cuh"
 #include "layout_blocked.hpp"
 
 #include <algorithm>
@@ -162,7 +163,29 @@ __device__ unsigned long long g_blk_stamps[2][512][4];
 // into ITS cells of next_table: the table T' = dis * h of a following layer over the same graph whose transform is applied
 // behind that layer's sum instead of in front of it, (A h) W = A (h W) (gn_graph_aggregate_chain_f32).  Column-local: no
 // workgroup waits for another, the kernel boundary that follows hands the table over.
-template <int CW, bool NEXT>
+// STAGED: a finished tile's folded sums are parked in LDS behind the table (slot (tile - first tile of the range) * 16 +
+// quad, CW floats) and the wave writes all its rows behind its loop.  Loads and stores share the in-order vmcnt: with a
+// store inside the loop every wait for a later load (the ids, the next tile's row and scale) also waited for that store's
+// acknowledgement from L2.  The staged loop has no vector-memory instruction but the id stream's own loads.  Plans whose
+// ranges hold more tiles than fit behind the table run the direct-store loop (blocked_gather decides per launch).
+// acc * d + bias with the rounding spelled out, so that the staged write-out and the direct loop cannot drift apart with the
+// compiler's contraction choices: one FMA per column for two columns (what the layer has always computed there: v_pk_fma_f32),
+// a product rounded on its own and a sum for one column (likewise: v_mul_f32, v_add_f32)
+template <int CW, typename V>
+__device__ __forceinline__ V scale_bias(V acc, float d, V bias) {
+    V r;
+    if constexpr (CW == 2) {
+#pragma unroll
+        for (int c = 0; c < CW; ++c) r[c] = __builtin_fmaf(acc[c], d, bias[c]);
+    } else {
+#pragma clang fp contract(off)
+        const float p = acc[0] * d;
+        r[0] = p + bias[0];
+    }
+    return r;
+}
+
+template <int CW, bool NEXT, bool STAGED>
 __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
     typedef float vec_t __attribute__((ext_vector_type(CW)));
     extern __shared__ f32x4 lds4[];
@@ -185,6 +208,7 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
     int it = cell[2];
     const int it_last = cell[3];
     const int e0 = cell[4], e1 = cell[5], e2 = cell[6], e3 = cell[7], e4 = cell[8];   // last iteration of the wave's first five tiles
+    const int range_c0 = a.cell[(size_t)(live ? range : 0) * kColWaves * kWaveInts];  // first tile of the range: wave 0's c0
     // ---- this column group of every node -> LDS, 1 KB per wave instruction (rows_pad * CW * 4 is a multiple of 1 KB;
     //      row n of the table is zero: padded id slots name it) ----
     if (live) {
@@ -207,16 +231,19 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) wb[k] = sp[512 + 64 * k];
     sp += 1024;
-    // destination row and scale of this quad in the wave's first four tiles (more tiles: read when they come up)
-    const int32_t* __restrict__ trp = a.tile_rows + (size_t)c0 * 16 + q;   // the arrays end with four spare tiles
-    const float* __restrict__ tdp = a.tile_dis + (size_t)c0 * 16 + q;
-    int row = trp[0];
-    const int row1 = trp[16], row2 = trp[32], row3 = trp[48];
-    float d = tdp[0];
-    const float d1 = tdp[16], d2 = tdp[32], d3 = tdp[48];
-    int t = c0;
+    // direct stores: destination row and scale of this quad in the wave's first four tiles (more tiles: read when they
+    // come up).  The staged loop needs neither: its write-out reads them for all the wave's tiles at once.
+    int row = -1, row1 = -1, row2 = -1, row3 = -1;
+    float d = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
     vec_t bias = (vec_t)(0.f);
-    if (a.bias) bias = *reinterpret_cast<const vec_t*>(a.bias + CW * cg);
+    if constexpr (!STAGED) {
+        const int32_t* __restrict__ trp = a.tile_rows + (size_t)c0 * 16 + q;   // the arrays end with four spare tiles
+        const float* __restrict__ tdp = a.tile_dis + (size_t)c0 * 16 + q;
+        row = trp[0]; row1 = trp[16]; row2 = trp[32]; row3 = trp[48];
+        d = tdp[0]; d1 = tdp[16]; d2 = tdp[32]; d3 = tdp[48];
+        if (a.bias) bias = *reinterpret_cast<const vec_t*>(a.bias + CW * cg);
+    }
+    int t = c0;
     // Everything requested so far has to be here: the LDS-DMA loads, and with them the id / row / scale loads issued
     // behind them.  (Loads return in issue order, so a count that lets exactly those later loads stay in flight would
     // release the barrier a little earlier - measured: the same total, the gather needs the first ids at once - but such
@@ -227,19 +254,19 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
     const unsigned long long st1 = __builtin_amdgcn_s_memrealtime();
 #endif
     const vec_t* __restrict__ tab = reinterpret_cast<const vec_t*>(lds4);
+    vec_t* stage = reinterpret_cast<vec_t*>(lds4) + a.rows_pad;          // behind the table: slot (tile - range_c0) * 16 + quad
     vec_t acc = (vec_t)(0.f);
     // (macros, not lambdas: with the closures hipcc 7.2 kept the kernel arguments and every captured local in scratch)
-    // GN_COL_FLUSH: tile t is complete - fold the quad, scale, bias, ReLU, write; step to the next tile
+    // GN_COL_FLUSH: tile t is complete - fold the quad (DPP: no LDS round trip), then either park the sums (staged) or
+    // scale, bias, ReLU, write (direct); step to the next tile
 #define GN_COL_FLUSH()                                                                                         \
     do {                                                                                                       \
-        _Pragma("unroll") for (int c = 0; c < CW; ++c) {                                                       \
-            float v = acc[c];                                                                                  \
-            v += __shfl_xor(v, 1);                                                                             \
-            v += __shfl_xor(v, 2);                                                                             \
-            acc[c] = v;                                                                                        \
-        }                                                                                                      \
-        if (j == 0 && row >= 0) {                                                                              \
-            vec_t r = acc * d + bias;                                                                          \
+        _Pragma("unroll") for (int c = 0; c < CW; ++c)                                                         \
+            acc[c] = gn::dpp_add<0x4E>(gn::dpp_add<0xB1>(acc[c]));     /* + lane ^ 1, then + lane ^ 2 */       \
+        if constexpr (STAGED) {                                                                                \
+            if (j == 0) stage[(t - range_c0) * 16 + q] = acc;                                                  \
+        } else if (j == 0 && row >= 0) {                                                                       \
+            vec_t r = scale_bias<CW>(acc, d, bias);                                                            \
             if (a.relu) {                                                                                      \
                 _Pragma("unroll") for (int c = 0; c < CW; ++c) r[c] = fmaxf(r[c], 0.f);                        \
             }                                                                                                  \
@@ -251,12 +278,14 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
         ++t;                                                                                                   \
         const int kk = t - c0;                                                                                 \
         tile_end = kk == 1 ? e1 : (kk == 2 ? e2 : (kk == 3 ? e3 : (kk == 4 ? e4 : a.tile_off[t + 1])));       \
-        if (kk < 4) {                                                                                          \
-            row = kk == 1 ? row1 : (kk == 2 ? row2 : row3);                                                    \
-            d = kk == 1 ? d1 : (kk == 2 ? d2 : d3);                                                            \
-        } else {                                                                                               \
-            row = a.tile_rows[(size_t)t * 16 + q];                                                             \
-            d = a.tile_dis[(size_t)t * 16 + q];                                                                \
+        if constexpr (!STAGED) {                                                                               \
+            if (kk < 4) {                                                                                      \
+                row = kk == 1 ? row1 : (kk == 2 ? row2 : row3);                                                \
+                d = kk == 1 ? d1 : (kk == 2 ? d2 : d3);                                                        \
+            } else {                                                                                           \
+                row = a.tile_rows[(size_t)t * 16 + q];                                                         \
+                d = a.tile_dis[(size_t)t * 16 + q];                                                            \
+            }                                                                                                  \
         }                                                                                                      \
     } while (0)
     // GN_COL_CONSUME: eight iterations out of registers; tile ends are wave-uniform (the inner while also passes empty tiles)
@@ -269,23 +298,61 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
             ++it;                                                                                              \
         }                                                                                                      \
     }
+    // A buffer is requested again only when iterations beyond the eight the OTHER buffer holds remain: a wave of up to
+    // sixteen iterations (every wave on PoSE) asks for its ids once, in the prologue.
     while (it < it_last) {
         GN_COL_CONSUME(wa)
         if (it >= it_last) break;
+        if (it + 8 < it_last) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) wa[k] = sp[64 * k];                    // the stream has slack behind its end
+            for (int k = 0; k < 8; ++k) wa[k] = sp[64 * k];                // the stream has slack behind its end
+        }
         GN_COL_CONSUME(wb)
+        if (it + 8 < it_last) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) wb[k] = sp[512 + 64 * k];
+            for (int k = 0; k < 8; ++k) wb[k] = sp[512 + 64 * k];
+        }
         sp += 1024;
     }
     while (t < c1) GN_COL_FLUSH();
 #undef GN_COL_CONSUME
 #undef GN_COL_FLUSH
 #ifdef GN_STAMPS
+    const unsigned long long st2 = __builtin_amdgcn_s_memrealtime();
+#endif
+    if constexpr (STAGED) {
+        // ---- write-out: a lane per (tile, quad) of the wave's tiles, 128 slots per trip.  The wave itself wrote the
+        //      slots (LDS operations of a wave complete in order): no barrier.  Rows, scales and slots of a trip are all
+        //      requested before the first store; the expressions are the direct loop's ----
+        vec_t wbias = (vec_t)(0.f);
+        if (a.bias) wbias = *reinterpret_cast<const vec_t*>(a.bias + CW * cg);
+        const int s_end = c1 * 16;
+        for (int s0 = c0 * 16 + lane; s0 < s_end; s0 += 128) {
+            const bool two = s0 + 64 < s_end;
+            const int s1 = two ? s0 + 64 : s0;
+            int rowa = a.tile_rows[s0], rowb = a.tile_rows[s1];
+            float da = a.tile_dis[s0], db = a.tile_dis[s1];
+            const vec_t va = stage[s0 - range_c0 * 16], vb = stage[s1 - range_c0 * 16];
+            asm volatile("" : "+v"(rowa), "+v"(rowb), "+v"(da), "+v"(db));    // one wait behind all four requests, not one per use
+            vec_t ra = scale_bias<CW>(va, da, wbias), rb = scale_bias<CW>(vb, db, wbias);
+            if (a.relu) {
+#pragma unroll
+                for (int c = 0; c < CW; ++c) { ra[c] = fmaxf(ra[c], 0.f); rb[c] = fmaxf(rb[c], 0.f); }
+            }
+            if (rowa >= 0) {
+                *reinterpret_cast<vec_t*>(a.out + (int64_t)rowa * a.ld_out + CW * cg) = ra;
+                if constexpr (NEXT) *reinterpret_cast<vec_t*>(a.next_table + ((size_t)cg * a.rows_pad + rowa) * CW) = ra * da;
+            }
+            if (two && rowb >= 0) {
+                *reinterpret_cast<vec_t*>(a.out + (int64_t)rowb * a.ld_out + CW * cg) = rb;
+                if constexpr (NEXT) *reinterpret_cast<vec_t*>(a.next_table + ((size_t)cg * a.rows_pad + rowb) * CW) = rb * db;
+            }
+        }
+    }
+#ifdef GN_STAMPS
     if (tid == 0 && blockIdx.x < 512) {
         unsigned long long* o = g_blk_stamps[stamp_set & 1][blockIdx.x];
-        o[0] = st0; o[1] = st1; o[2] = __builtin_amdgcn_s_memrealtime(); o[3] = 0;
+        o[0] = st0; o[1] = st1; o[2] = __builtin_amdgcn_s_memrealtime(); o[3] = st2;
     }
 #endif
     } while (0);
@@ -293,10 +360,15 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
     gn::side_copy_stream(a.side, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
 
+// k_col_gather / k_col_gather_next: the staged kernels; *_direct: stores from inside the loop, for plans without room for the slots
 template <int CW>
-__global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp_set) { col_gather<CW, false>(a, stamp_set); }
+__global__ __launch_bounds__(kColThreads) void k_col_gather(ColArgs a, int stamp_set) { col_gather<CW, false, true>(a, stamp_set); }
 template <int CW>
-__global__ __launch_bounds__(kColThreads) void k_col_gather_next(ColArgs a, int stamp_set) { col_gather<CW, true>(a, stamp_set); }
+__global__ __launch_bounds__(kColThreads) void k_col_gather_next(ColArgs a, int stamp_set) { col_gather<CW, true, true>(a, stamp_set); }
+template <int CW>
+__global__ __launch_bounds__(kColThreads) void k_col_gather_direct(ColArgs a, int stamp_set) { col_gather<CW, false, false>(a, stamp_set); }
+template <int CW>
+__global__ __launch_bounds__(kColThreads) void k_col_gather_next_direct(ColArgs a, int stamp_set) { col_gather<CW, true, false>(a, stamp_set); }
 
 template <int FIN, int NT>
 void launch_transform(const TransArgs& t, int cw, hipStream_t st) {
@@ -347,6 +419,16 @@ gn_status blocked_transform(const gn_graph_plan* plan, const float* x, int64_t l
     return GN_OK;
 }
 
+// The staging slots of the largest range: 16 quads x blk_cw floats per tile
+size_t stage_bytes(const gn_graph_plan* plan) { return (size_t)plan->blk_range_tiles * 16 * plan->blk_cw * sizeof(float); }
+
+// The staged kernels run when the slots fit behind the table (GN_BLOCKED_DIRECT=1, tests: never)
+bool blocked_staged(const gn_graph_plan* plan) {
+    const char* e = getenv("GN_BLOCKED_DIRECT");
+    if (e && e[0] == '1') return false;
+    return (size_t)plan->blk_rows * plan->blk_cw * sizeof(float) + stage_bytes(plan) <= kColLdsBytes;
+}
+
 // The gather from LDS over the plan's table as it stands, one workgroup per (column group, range of destination rows);
 // next_table != null: the launch also fills that table of a following layer (k_col_gather_next)
 gn_status blocked_gather(const gn_graph_plan* plan, int64_t fout, const float* bias, int relu, float* out, int64_t ld_out,
@@ -363,15 +445,21 @@ gn_status blocked_gather(const gn_graph_plan* plan, int64_t fout, const float* b
     a.groups = (int)(fout / cw); a.ranges = plan->blk_cells; a.relu = relu; a.side = side; a.next_table = next_table;
     const int per_x = (a.ranges + 7) / 8;
     const int grid = 8 * per_x * a.groups;
-    const size_t lds = (size_t)plan->blk_rows * cw * sizeof(float);
+    const bool staged = blocked_staged(plan);
+    const size_t lds = (size_t)plan->blk_rows * cw * sizeof(float) + (staged ? stage_bytes(plan) : 0);
     auto launch = [&](auto kernel) {
         gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(kernel), (int)kColLdsBytes);
         if (s == GN_OK) kernel<<<grid, kColThreads, lds, st>>>(a, stamp_set);
         return s;
     };
     gn_status s;
-    if (next_table) s = cw == 2 ? launch(k_col_gather_next<2>) : launch(k_col_gather_next<1>);
-    else s = cw == 2 ? launch(k_col_gather<2>) : launch(k_col_gather<1>);
+    if (staged) {
+        if (next_table) s = cw == 2 ? launch(k_col_gather_next<2>) : launch(k_col_gather_next<1>);
+        else s = cw == 2 ? launch(k_col_gather<2>) : launch(k_col_gather<1>);
+    } else {
+        if (next_table) s = cw == 2 ? launch(k_col_gather_next_direct<2>) : launch(k_col_gather_next_direct<1>);
+        else s = cw == 2 ? launch(k_col_gather_direct<2>) : launch(k_col_gather_direct<1>);
+    }
     if (s != GN_OK) return s;
     GN_LAUNCH_CHECK();
     return GN_OK;
@@ -495,6 +583,11 @@ extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t co
     GN_LAP("blocked: upload");
     plan->blk_cols = (int)cols; plan->blk_cw = cw; plan->blk_rows = (int)rows_pad; plan->blk_cells = R;
     plan->blk_iters = bl.iters_total;
+    plan->blk_range_tiles = 0;                                          // the largest range: last wave's end tile - first wave's first tile
+    for (int r = 0; r < R; ++r) {
+        const int32_t* c = bl.cell.data() + (size_t)r * kColWaves * kWaveInts;
+        plan->blk_range_tiles = std::max<int>(plan->blk_range_tiles, c[(kColWaves - 1) * kWaveInts + 1] - c[0]);
+    }
     plan->blk_ok = 1;
     return GN_OK;
 }
@@ -504,6 +597,22 @@ extern "C" __attribute__((visibility("default"))) int gn_debug_read_blk_stamps(u
     return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_blk_stamps), sizeof(unsigned long long) * 2 * 512 * 4);
 }
 #endif
+
+extern "C" int gn_graph_plan_blocked_gather_kernel(const gn_graph_plan* plan) {
+    if (!plan || !plan->blk_ok || blocked_disabled()) return 0;
+    return blocked_staged(plan) ? 1 : 2;
+}
+
+// tests: the schedule the gather walks, [ranges][16 waves][12] (first tile, end tile, first iteration, end iteration, ...)
+extern "C" int64_t gn_graph_plan_blocked_waves(const gn_graph_plan* plan, int32_t* host_out, int64_t capacity) {
+    if (!plan || !plan->blk_ok) return 0;
+    const int64_t count = (int64_t)plan->blk_cell.n;
+    if (host_out) {
+        if (capacity < count) return -1;
+        if (hipMemcpy(host_out, plan->blk_cell.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    }
+    return count;
+}
 
 extern "C" int64_t gn_graph_plan_blocked_cols(const gn_graph_plan* plan) {
     return (plan && plan->blk_ok && !blocked_disabled()) ? plan->blk_cols : 0;

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 162 /* 0.1.56 */
+#define GN_VERSION 163 /* 0.1.57 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -157,6 +157,15 @@ GN_API int gn_graph_transform_fusable(const gn_graph_plan* plan, int64_t in_feat
  * and synchronises `stream`: meant for graphs that are kept (the Python layer builds it only for `cached=True`). */
 GN_API gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t cols, void* stream);
 GN_API int64_t gn_graph_plan_blocked_cols(const gn_graph_plan* plan);
+/* Which gather kernel the LDS-staged path launches for this plan right now: 0 = the plan has no such encoding, 1 = the
+ * staged kernel (a range's tile sums parked in LDS behind the table, all rows written behind the loop), 2 = the
+ * direct-store kernel (no room for the slots behind the table, or GN_BLOCKED_DIRECT=1).  Same bits either way. */
+GN_API int gn_graph_plan_blocked_gather_kernel(const gn_graph_plan* plan);
+/* The schedule the gather walks, copied to `host_out` (null: only counted): per range and per wave of its workgroup (16)
+ * twelve ints - first tile, end tile, first iteration, end iteration of the id stream, the ends of its first five tiles,
+ * three unused.  Returns the number of ints, 0 without the encoding, -1 when `capacity` is too small or the copy failed.
+ * Synchronises the device.  For tests and tools that must know which waves a graph produces. */
+GN_API int64_t gn_graph_plan_blocked_waves(const gn_graph_plan* plan, int32_t* host_out, int64_t capacity);
 /* Whether gn_graph_aggregate_f32 with these operands takes the LDS-staged path (it also needs `out`, `ld_out` and `bias`
  * aligned to the gather's column groups; other operands keep the wave-per-row kernels).  Launches nothing. */
 GN_API int gn_graph_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,

@@ -5,7 +5,8 @@
         python tools/blk_stamps.py
 
 Reads the stamps the diagnostic build leaves behind per workgroup: 100 MHz real-time clock at kernel entry,
-after the table fill (barrier) and at exit.  Set 0 = the 32 -> 16 layer, set 1 = the 16 -> 16 layer.
+after the table fill (barrier), at the end of wave 0's loop (staged kernels: in front of its write-out) and at exit.
+Set 0 = the 32 -> 16 layer, set 1 = the 16 -> 16 layer.
 """
 import ctypes as C
 import os
@@ -45,6 +46,9 @@ def main():
                   s, len(b), us(b[:, 0].max() - t0), us(b[:, 1].mean() - t0), us(b[:, 1].max() - t0), us(b[:, 2].mean() - t0),
                   us(b[:, 2].max() - t0), us((b[:, 1] - b[:, 0]).mean()), us((b[:, 1] - b[:, 0]).max()),
                   us((b[:, 2] - b[:, 1]).mean()), us((b[:, 2] - b[:, 1]).max())))
+        if (b[:, 3] > 0).all():                 # staged kernels: wave 0's loop and its write-out apart
+            print("             loop per wg mean {:.2f} max {:.2f}; write-out per wg mean {:.2f} max {:.2f}".format(
+                us((b[:, 3] - b[:, 1]).mean()), us((b[:, 3] - b[:, 1]).max()), us((b[:, 2] - b[:, 3]).mean()), us((b[:, 2] - b[:, 3]).max())))
 
 
 if __name__ == "__main__":
