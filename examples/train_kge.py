@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Counterpart of the reference's KGE link-prediction baselines (baselines/LP_baselines/TransE_DistMult_ComplEx_RotatE.py)
+on the MI355X path.
+
+The reference script executes at import and loads `datasets_baselines/pose-*-combl.pt` (:28), which is not available
+offline; this driver runs the same model, loss, optimiser and epoch structure (:238-305) on the synthetic homogenised
+graph of gripnet_amd.synth.make_rgcn_pose (all drug and gene nodes are entities; the gene-gene and gene-drug edges are the
+last two relations):
+
+    python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3
+    python examples/train_kge.py --model RotatE --workload pose0-syn --time
+
+The reference defines KGEModel in the driver itself; here it comes from the package.  `--time` prints the milliseconds of
+one training step (forward of both lists, backward, optimiser; fixed negatives) and, next to it, the same step with the
+scoring done by the torch formulation of the reference (tests/kge_cases.py) on the same GPU.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from gripnet_amd import KGEModel                                      # reference: class KGEModel, :58-235
+from gripnet_amd import _hip
+from gripnet_amd.synth import make_rgcn_pose
+from gripnet_amd.utils import EPS, device_negative_sampler, relation_metrics, typed_negative_sampling
+
+
+class Negatives:
+    """Per-relation negatives of a static positive list: drawn on the device; where the device sampler refuses the list
+    (its pair keys do not hold this many entities) by the host loop of utils.typed_negative_sampling."""
+
+    def __init__(self, pos_index, num_nodes, range_list):
+        self.pos, self.n, self.ranges = pos_index, num_nodes, range_list
+        try:
+            self.sampler = device_negative_sampler(pos_index, num_nodes, range_list)
+        except (_hip.GripNetHipError, ValueError):
+            self.sampler, self.host_pos = None, pos_index.cpu()
+
+    def sample(self, seed):
+        if self.sampler is not None:
+            return self.sampler.sample(seed=seed)
+        return typed_negative_sampling(self.host_pos, self.n, self.ranges.cpu(), np.random.RandomState(seed)).to(self.pos.device)
+
+
+class TorchKGE(torch.nn.Module):
+    """The same parameters scored by the torch formulation of the reference (for --time only)."""
+
+    def __init__(self, model):
+        super().__init__()
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import kge_cases
+        self.formulation = kge_cases.log_sigmoid_score
+        self.name, self.gamma = model.model_name, model.gamma.item()
+        self.entity_embedding = torch.nn.Parameter(model.entity_embedding.detach().clone())
+        self.relation_embedding = torch.nn.Parameter(model.relation_embedding.detach().clone())
+
+    def forward(self, sample, et):
+        return self.formulation(self.name, self.entity_embedding, self.relation_embedding, sample, et, self.gamma)
+
+
+def step_ms(model, optimizer, pos_index, neg_index, et, warmup=3, steps=10):
+    def step():
+        optimizer.zero_grad()
+        neg_score = model(neg_index, et)
+        pos_score = model(pos_index, et)
+        loss = -(pos_score + EPS).mean() + -(1 - neg_score + EPS).mean()
+        loss.backward()
+        optimizer.step()
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        step()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="RotatE", choices=["TransE", "DistMult", "ComplEx", "RotatE"])
+    ap.add_argument("--workload", default="small")
+    ap.add_argument("--epochs", type=int, default=3)
+    ap.add_argument("--time", action="store_true")
+    args = ap.parse_args()
+    torch.manual_seed(1111)
+    np.random.seed(1111)
+    device = torch.device("cuda")
+    data = make_rgcn_pose(args.workload).to(device)
+    embed_dim, learning_rate = 32, 0.01                                # :54-55
+    model = KGEModel(args.model, data.n_node, data.n_edge_type, hidden_dim=embed_dim, gamma=12).to(device)   # :238-244
+    optimizer = torch.optim.Adam(model.parameters(), lr=learning_rate)                                       # :247
+    negatives = Negatives(data.train_idx, data.n_node, data.train_range)
+    drug_edges = int(data.train_range[-2][0])
+    drug_ranges = data.train_range[:-2]
+    drug_negatives = Negatives(data.train_idx[:, :drug_edges].contiguous(), data.n_drug, drug_ranges)
+
+    if args.time:
+        neg_index = negatives.sample(0)
+        other = TorchKGE(model).to(device)
+        other_optimizer = torch.optim.Adam(other.parameters(), lr=learning_rate)
+        for run in range(3):
+            ours = step_ms(model, optimizer, data.train_idx, neg_index, data.train_et)
+            torch_ms = step_ms(other, other_optimizer, data.train_idx, neg_index, data.train_et)
+            print("{} {} run {}: E = {}, n = {}, R = {}: HIP step {:.3f} ms, torch formulation {:.3f} ms ({:.2f}x)".format(
+                args.model, data.name, run + 1, data.train_idx.shape[1], data.n_node, data.n_edge_type, ours, torch_ms,
+                torch_ms / ours))
+        _hip.raise_if_index_errors(device)
+        return
+
+    def train(epoch):                                                 # :254-305
+        model.train()
+        optimizer.zero_grad()
+        pos_index = data.train_idx
+        neg_index = negatives.sample(2 * epoch)
+        neg_score = model(neg_index, data.train_et)
+        pos_score = model(pos_index, data.train_et)
+        pos_loss = -(pos_score + EPS).mean()
+        neg_loss = -(1 - neg_score + EPS).mean()
+        loss = pos_loss + neg_loss
+        loss.backward()
+        optimizer.step()
+        model.eval()
+        with torch.no_grad():
+            neg_score = model(drug_negatives.sample(2 * epoch + 1), data.train_et[:drug_edges])
+        # the reference loops over the drug relations with one scikit-learn call each (:282-293); here one pass on the GPU
+        auprc, auroc, ap = relation_metrics(pos_score.detach()[:drug_edges].contiguous(), neg_score, drug_ranges)
+        return float(loss.detach()), float(auprc.nanmean()), float(auroc.nanmean()), float(ap.nanmean())
+
+    for epoch in range(args.epochs):
+        t0 = time.time()
+        loss, auprc, auroc, ap = train(epoch)
+        torch.cuda.synchronize()
+        print("{:3d}   loss:{:0.4f}   auprc:{:0.4f}   auroc:{:0.4f}   ap@50:{:0.4f}    time:{:0.2f}s".format(
+            epoch, loss, auprc, auroc, ap, time.time() - t0))
+
+
+if __name__ == "__main__":
+    main()

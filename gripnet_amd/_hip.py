@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 163                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 164                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -104,6 +104,10 @@ SIGNATURES = {
     "gn_distmult_backward_planned_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _sz, _p]),
     "gn_distmult_backward_loss_packed_f32": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _p, _i64, _int, _p, _p, _i64, _p, _i64, _p, _sz, _p]),
     "gn_distmult_backward_loss_planned_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _p, _p, _i64, _p, _i64, _p, _sz, _p]),
+    "gn_kge_forward_workspace_bytes": (_sz, [_int, _i64, _i64]),
+    "gn_kge_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
+    "gn_kge_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),
+    "gn_kge_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
     "gn_negative_sampler_create": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, C.POINTER(_p)]),
     "gn_negative_sampler_destroy": (None, [_p]),
     "gn_negative_sampler_sample": (_int, [_p, C.c_uint64, _p, _p, _p, _p]),
@@ -1008,7 +1012,7 @@ def raise_if_index_errors(device=None):
                 raise RuntimeError("negative sampler: a relation's positive pairs leave no pair to draw")
             found = []
             if bits & 1:
-                found.append("DistMult decoder saw an edge endpoint or relation id outside its table")
+                found.append("DistMult decoder saw an edge endpoint or relation id outside its table (or a KGE scorer a head, tail or relation id)")
             if bits & 8:
                 found.append("class metrics saw a class id outside [0, num_class) (true or predicted)")
             raise IndexError("; ".join(found))
@@ -1309,6 +1313,61 @@ def distmult_backward_planned(plan, z, u_v, edge_type, weight, grad_logit, dz, d
         return False
     distmult_backward(z, u_v, edge_type, weight, grad_logit, dz, dd, probs=probs)
     return True
+
+
+KGE_MODELS = {"TransE": 0, "DistMult": 1, "ComplEx": 2, "RotatE": 3}          # GN_KGE_* of include/gripnet_hip.h
+
+
+def _kge_operands(model, ent, rel, sample, et):
+    """(hidden size, kept-alive index tensor, head pointer, tail pointer, E, edge_type) of a KGE call, shapes checked."""
+    m = KGE_MODELS[model]
+    h = rel.shape[1] // 2 if model == "ComplEx" else rel.shape[1]
+    de = 2 * h if model in ("ComplEx", "RotatE") else h
+    if ent.shape[1] != de or (model == "ComplEx" and rel.shape[1] != 2 * h):
+        raise ValueError("{}: entity rows of {} and relation rows of {} columns do not belong together".format(
+            model, ent.shape[1], rel.shape[1]))
+    idx, head, tail, e = edge_rows(sample)
+    types = i64_vec(et)
+    if types.numel() != e:
+        raise ValueError("edge_type has {} entries for {} triples".format(types.numel(), e))
+    return m, h, idx, head, tail, e, types
+
+
+_sorted_types = VersionedCache(4)          # edge_type tensor -> whether it is non-decreasing
+
+
+def _non_decreasing(et):
+    """One device reduction and host read per tensor (and version): the reference scores its static `train_et` every step."""
+    known = _sorted_types.get(et)
+    if known is MISS:
+        known = _sorted_types.put(et, bool((et[1:] >= et[:-1]).all()))
+    return known
+
+
+def kge_forward(model, ent, rel, sample, et, gamma, divisor, log_sigmoid, out, raw=None):
+    """gn_kge_forward_f32: the scores of `sample` [2, E] under `model` into `out` (with `log_sigmoid`: their log-sigmoid,
+    the raw scores into `raw`).  Ids outside the tables: NaN and the device's error flag (raise_if_index_errors)."""
+    m, h, idx, head, tail, e, types = _kge_operands(model, ent, rel, sample, et)
+    need = int(load().gn_kge_forward_workspace_bytes(m, rel.shape[0], h))
+    ws = torch.empty((need,), dtype=torch.uint8, device=ent.device) if need else None
+    _call("gn_kge_forward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, head, tail, ptr(types), e,
+          float(gamma), float(divisor), int(bool(log_sigmoid)), ptr(out), ptr(raw), ptr(error_flag(ent.device)), ptr(ws), need,
+          stream_ptr(ent.device))
+    return out
+
+
+def kge_backward(model, ent, rel, sample, et, divisor, grad_out, raw, d_ent, d_rel, types_sorted=None):
+    """gn_kge_backward_f32: d_ent / d_rel (overwritten) from the gradient of the forward's output; `raw`: the raw scores
+    when that output was the log-sigmoid.  `types_sorted` None: looked up (once per edge_type tensor and version)."""
+    m, h, idx, head, tail, e, types = _kge_operands(model, ent, rel, sample, et)
+    if types_sorted is None:
+        types_sorted = e < 2 or _non_decreasing(et)
+    need = int(load().gn_kge_backward_workspace_bytes(m, ent.shape[0], rel.shape[0], h, e))
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=ent.device)
+    _call("gn_kge_backward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, head, tail, ptr(types), e,
+          float(divisor), ptr(grad_out), ptr(raw), ptr(d_ent), ld(d_ent), ptr(d_rel), ld(d_rel),
+          GN_DM_TYPES_SORTED if types_sorted else 0, ptr(ws), need, stream_ptr(ent.device))
+    return d_ent, d_rel
 
 
 def link_loss_forward(pos, neg, eps):

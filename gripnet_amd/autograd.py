@@ -301,6 +301,30 @@ class DistMultFn(torch.autograd.Function):
         return (dz if ctx.needs_input_grad[0] else None), (dd if ctx.needs_input_grad[1] else None), None, None, None, None
 
 
+class KgeScoreFn(torch.autograd.Function):
+    """The score of a triple list under one of the KGE baselines, or its log-sigmoid (KGEModel.forward,
+    baselines/LP_baselines/TransE_DistMult_ComplEx_RotatE.py:127-235), with the scatter gradients in HIP."""
+
+    @staticmethod
+    def forward(ctx, entity, relation, sample, et, model, gamma, divisor, log_sigmoid):
+        ent, rel = _hip.f32_rows(entity.detach()), _hip.f32_rows(relation.detach())
+        e = sample.shape[1]
+        out = torch.empty((e,), dtype=torch.float32, device=ent.device)
+        raw = torch.empty((e,), dtype=torch.float32, device=ent.device) if log_sigmoid else None
+        _hip.kge_forward(model, ent, rel, sample, et, gamma, divisor, log_sigmoid, out, raw)
+        ctx.model, ctx.divisor = model, divisor
+        ctx.save_for_backward(ent, rel, sample, et, raw)       # (sigma(-s) of the log-sigmoid is applied where the records are built)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ent, rel, sample, et, raw = ctx.saved_tensors
+        g = g.contiguous().to(torch.float32)
+        d_ent, d_rel = torch.empty_like(ent), torch.empty_like(rel)
+        _hip.kge_backward(ctx.model, ent, rel, sample, et, ctx.divisor, g, raw, d_ent, d_rel)
+        return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None
+
+
 class LinkLossFn(torch.autograd.Function):
     """``-mean(log(pos + eps)) - mean(log(1 - neg + eps))`` (the loss of GripNet-pose.py:140-142) in one launch forward and
     one backward, instead of the ~20 element-wise and reduction launches of the torch expression."""

@@ -29,6 +29,7 @@
 #include "common.h"
 #include "layout_decoder_bwd.hpp"
 #include "plan_device.cuh"
+#include "seg_sort.cuh"
 
 #include <unordered_map>
 #include <vector>
@@ -92,7 +93,7 @@ struct EdgeSrc {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
+size_t align_up(size_t v) { return gn::seg_align_up(v); }
 
 using gn::bits_for;
 
@@ -116,16 +117,7 @@ __global__ void k_make_recs(int mode, const int64_t* __restrict__ u, const int64
     }
 }
 
-__global__ void k_key_offsets(const uint32_t* __restrict__ sorted, int64_t n, int rows, int32_t* __restrict__ rowptr) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > rows) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid] < (uint32_t)i) lo = mid + 1; else hi = mid;
-    }
-    rowptr[i] = (int32_t)lo;
-}
+using gn::k_key_offsets;                      // rowptr[i] = first position whose sorted key is >= i (seg_sort.cuh)
 
 // Chunked segmented reduction.  The sorted record array is cut into chunks of kChunkRecs records, one
 // workgroup each (hub rows of 10^5 records and rows of a few records cost the same per record).  A
@@ -134,7 +126,7 @@ __global__ void k_key_offsets(const uint32_t* __restrict__ sorted, int64_t n, in
 // in a fixed order.  A row that lies wholly inside the chunk is final and goes to `out`; the chunk's
 // first / last row may continue in a neighbour chunk and goes to partial slot 2b / 2b+1 (columns
 // [c0, c0+64)), which k_seg_combine adds up in chunk order: bitwise reproducible.
-constexpr int kChunkRecs = 2048;
+constexpr int kChunkRecs = gn::kSegChunkRecs;
 
 template <int LPE>
 __global__ __launch_bounds__(256) void k_seg_reduce(const int32_t* __restrict__ rowptr, const uint32_t* __restrict__ keys,
@@ -258,18 +250,6 @@ __global__ void k_pair_recs(const int64_t* __restrict__ u, const int64_t* __rest
         recs[e] = ok ? pack_rec((uint32_t)uu, (uint32_t)vv, gs.at(e)) : 0ull;
         if (keys) keys[e] = ok ? (uint32_t)rr : (uint32_t)R;
     }
-}
-
-// rowptr[i] = first position whose (sorted, int64) key is >= i
-__global__ void k_key_offsets64(const int64_t* __restrict__ sorted, int64_t n, int rows, int32_t* __restrict__ rowptr) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i > rows) return;
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (sorted[mid] < (int64_t)i) lo = mid + 1; else hi = mid;
-    }
-    rowptr[i] = (int32_t)lo;
 }
 
 // taskptr[k] = number of tasks of the keys before k (a task = up to kTaskRecs records of one key), and the tasks
@@ -978,12 +958,12 @@ gn_status dd_lds(const Call& c, const LdsWs& w, const Route& rt, const int32_t* 
     if (rt.types_sorted && type_offsets) {
         rowptr = type_offsets;                             // the caller keeps them with its static edge_type
     } else if (rt.types_sorted) {
-        k_key_offsets64<<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(c.edges.et, e, (int)r, w.rowptr);
+        k_key_offsets<int64_t><<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(c.edges.et, e, (int)r, w.rowptr);
         GN_LAUNCH_CHECK();
     } else {
         size_t sort_bytes = w.sort_tmp_bytes;
         GN_HIP(rocprim::radix_sort_pairs(w.sort_tmp, sort_bytes, w.keys, w.keys_sorted, w.recs, w.recs_sorted, (size_t)e, 0, bits_for(r + 1), st));
-        k_key_offsets<<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(w.keys_sorted, e, (int)r, w.rowptr);
+        k_key_offsets<uint32_t><<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(w.keys_sorted, e, (int)r, w.rowptr);
         GN_LAUNCH_CHECK();
         recs = w.recs_sorted;
     }
@@ -1020,7 +1000,7 @@ gn_status general_pass(int mode, const Call& c, bool vec, char* ws, const WsLayo
     k_make_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(mode, c.edges.u, c.edges.v, c.edges.et, c.grad, e, c.n, c.r, (uint32_t)rows, keys, recs);
     GN_LAUNCH_CHECK();
     GN_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, sort_bytes, keys, keys_sorted, recs, recs_sorted, (size_t)e, 0, bits_for(rows + 1), st));
-    k_key_offsets<<<(int)gn::ceil_div(rows + 1, 256), 256, 0, st>>>(keys_sorted, e, (int)rows, rowptr);
+    k_key_offsets<uint32_t><<<(int)gn::ceil_div(rows + 1, 256), 256, 0, st>>>(keys_sorted, e, (int)rows, rowptr);
     GN_LAUNCH_CHECK();
     if (!vec) {
         k_seg_reduce_scalar<<<(unsigned)rows, 256, 0, st>>>(rowptr, recs_sorted, A, ld_a, B, ld_b, out, ld_out, (int)f, accumulate);
@@ -1289,7 +1269,7 @@ gn_status build_bwd_plan(gn_distmult_bwd_plan* p, hipStream_t st) {
     gn_status rc = count_half_edges(EdgeSrc{p->eu.p, p->ev.p, p->er.p, nullptr, nullptr}, none, E, n, R, p->offsets.p, totals, p->he_taskptr.p,
                                     reinterpret_cast<int4*>(p->he_tasks.p), st);
     if (rc != GN_OK) return rc;
-    k_key_offsets64<<<(int)gn::ceil_div(R + 1, 256), 256, 0, st>>>(p->er.p, E, (int)R, rp);
+    k_key_offsets<int64_t><<<(int)gn::ceil_div(R + 1, 256), 256, 0, st>>>(p->er.p, E, (int)R, rp);
     GN_LAUNCH_CHECK();
     k_task_ptr<<<1, 1024, 0, st>>>(rp, 1, (int)R, p->pr_taskptr.p, reinterpret_cast<int4*>(p->pr_tasks.p));
     GN_LAUNCH_CHECK();

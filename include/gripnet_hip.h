@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 163 /* 0.1.57 */
+#define GN_VERSION 164 /* 0.1.58 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -563,6 +563,53 @@ GN_API gn_status gn_distmult_backward_loss_planned_f32(const gn_distmult_bwd_pla
                                                 const gn_link_loss_grad* loss, const float* sigmoid_scores,
                                                 float* dz, int64_t ld_dz, float* dd, int64_t ld_dd, void* workspace,
                                                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Knowledge-graph-embedding scorers of the link-prediction baselines (KGEModel.forward,
+ * baselines/LP_baselines/TransE_DistMult_ComplEx_RotatE.py:127-235).  With h = ent[head_e], t = ent[tail_e],
+ * r = rel[edge_type_e] and H = hidden_dim:
+ *   GN_KGE_TRANSE    ent [n, H],  rel [R, H]    s_e = gamma - sum_k |h_k + r_k - t_k|                          (:189-193)
+ *   GN_KGE_DISTMULT  ent [n, H],  rel [R, H]    s_e = sum_k h_k r_k t_k                                        (:195-199)
+ *   GN_KGE_COMPLEX   ent [n, 2H], rel [R, 2H]   s_e = sum_k (hr rr - hi ri) tr + (hr ri + hi rr) ti            (:201-211)
+ *   GN_KGE_ROTATE    ent [n, 2H], rel [R, H]    s_e = gamma - sum_k sqrt(a_k^2 + b_k^2),  theta = r / phase_divisor,
+ *                                               a = hr cos - hi sin - tr,  b = hr sin + hi cos - ti            (:213-235)
+ * (real part: columns [0, H), imaginary part: columns [H, 2H)).  phase_divisor is the fp32 value of embedding_range / pi
+ * (:221): the phases are divided by it, not multiplied by a reciprocal.  out[e] = s_e, or with log_sigmoid
+ * min(s, 0) - log1p(exp(-|s|)) (:187); raw_out (nullable) receives s_e as well.  cos / sin are evaluated once per call
+ * for the relation table, into `workspace` (gn_kge_forward_workspace_bytes bytes, 16-byte aligned; 0 for the other
+ * models).  A head, tail or relation outside its table yields NaN for that triple and sets bit 0 of *error_flag (device
+ * int32, may be NULL).  GN_ERR_INVALID_ARG: an unknown model, a null operand, a leading dimension below the row length,
+ * a zero phase_divisor, a workspace that is too small; GN_ERR_UNSUPPORTED: 2^31 - 512 or more rows in a table, 2^31 - 2048
+ * or more triples, a hidden_dim of 2^29 or more. */
+#define GN_KGE_TRANSE 0
+#define GN_KGE_DISTMULT 1
+#define GN_KGE_COMPLEX 2
+#define GN_KGE_ROTATE 3
+GN_API size_t gn_kge_forward_workspace_bytes(int model, int64_t num_relations, int64_t hidden_dim);
+GN_API gn_status gn_kge_forward_f32(int model, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                             int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* head,
+                             const int64_t* tail, const int64_t* edge_type, int64_t num_edges, float gamma,
+                             float phase_divisor, int log_sigmoid, float* out, float* raw_out /* nullable */,
+                             int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of the scorers (autograd of :127-235 under the loss of :266-268).  grad_out[e] is the gradient with respect
+ * to what the forward returned: with raw_scores (the s_e of raw_out) that is the log-sigmoid, and the factor sigma(-s_e)
+ * is applied where the records are built; with raw_scores = NULL it is s_e itself.  d_ent [n, De] and d_rel [R, Dr] are
+ * overwritten with the sums of g_e * ds_e/d(row) over the triples of every row; rows without a triple get exact zeros;
+ * triples with an id outside its table contribute nothing.  torch's subgradients: sign(0) = 0 (TransE), a term with
+ * a = b = 0 contributes nothing (RotatE).  Three passes (key = head, + key = tail, key = relation) of a sort-based
+ * segmented reduction: no float atomics, chunk partials added in chunk order, two calls give the same bits.
+ * flags: GN_DM_TYPES_SORTED promises a non-decreasing edge_type - the relation pass then skips its sort and takes the row
+ * offsets by binary search.  Scratch is caller-provided: gn_kge_backward_workspace_bytes bytes, 256-byte aligned.
+ * Refusals as for the forward. */
+GN_API size_t gn_kge_backward_workspace_bytes(int model, int64_t num_entities, int64_t num_relations, int64_t hidden_dim,
+                                       int64_t num_edges);
+GN_API gn_status gn_kge_backward_f32(int model, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                              int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* head,
+                              const int64_t* tail, const int64_t* edge_type, int64_t num_edges, float phase_divisor,
+                              const float* grad_out, const float* raw_scores /* nullable */, float* d_ent, int64_t ld_dent,
+                              float* d_rel, int64_t ld_drel, int flags, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Typed negative sampling on the device (replaces gripnet/utils.py:98-119 and its per-epoch host round
