@@ -9,10 +9,14 @@ last two relations):
 
     python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3
     python examples/train_kge.py --model RotatE --workload pose0-syn --time
+    python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3 --rank
 
 The reference defines KGEModel in the driver itself; here it comes from the package.  `--time` prints the milliseconds of
 one training step (forward of both lists, backward, optimiser; fixed negatives) and, next to it, the same step with the
-scoring done by the torch formulation of the reference (tests/kge_cases.py) on the same GPU.
+scoring done by the torch formulation of the reference (tests/kge_cases.py) on the same GPU.  `--rank` prints, after the
+last epoch, filtered MRR and Hits@1/3/10 of a fixed sample of the list's triples against every entity, tail side and head
+side (KGEModel.rank; the synthetic graph has no held-out split, so the triples ranked are training triples and the
+filter is the training list: as given for the tail side, flipped for the head side).
 """
 import argparse
 import os
@@ -28,7 +32,8 @@ sys.path.insert(0, ROOT)
 from gripnet_amd import KGEModel                                      # reference: class KGEModel, :58-235
 from gripnet_amd import _hip
 from gripnet_amd.synth import make_rgcn_pose
-from gripnet_amd.utils import EPS, device_negative_sampler, relation_metrics, typed_negative_sampling
+from gripnet_amd.decoder import KnownPairs
+from gripnet_amd.utils import EPS, device_negative_sampler, ranking_metrics, relation_metrics, typed_negative_sampling
 
 
 class Negatives:
@@ -88,6 +93,8 @@ def main():
     ap.add_argument("--workload", default="small")
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--time", action="store_true")
+    ap.add_argument("--rank", action="store_true", help="filtered MRR / Hits@k of both sides after the last epoch")
+    ap.add_argument("--rank-sample", type=int, default=20000, help="triples ranked by --rank")
     args = ap.parse_args()
     torch.manual_seed(1111)
     np.random.seed(1111)
@@ -139,6 +146,20 @@ def main():
         torch.cuda.synchronize()
         print("{:3d}   loss:{:0.4f}   auprc:{:0.4f}   auroc:{:0.4f}   ap@50:{:0.4f}    time:{:0.2f}s".format(
             epoch, loss, auprc, auroc, ap, time.time() - t0))
+
+    if args.rank:
+        lists = [(data.train_idx, data.train_et)]
+        known = {"tail": KnownPairs(lists, data.n_node, data.n_edge_type),                      # rows keyed (relation, head)
+                 "head": KnownPairs([(ei.flip(0), et) for ei, et in lists], data.n_node, data.n_edge_type)}   # (relation, tail)
+        e = data.train_idx.shape[1]
+        pick = torch.randperm(e, generator=torch.Generator().manual_seed(7))[:args.rank_sample].to(device)
+        sample, et = data.train_idx[:, pick].contiguous(), data.train_et[pick].contiguous()
+        for side in ("tail", "head"):
+            greater, ties = model.rank(sample, et, side=side, known=known[side])
+            m = ranking_metrics(greater, ties, et, data.n_edge_type)
+            print("filtered ranking, {} side ({} triples against {} entities):   mrr:{:0.4f}   hits@1:{:0.4f}   hits@3:{:0.4f}   "
+                  "hits@10:{:0.4f}".format(side, sample.shape[1], data.n_node, m["mrr_all"].item(), m["hits@1_all"].item(),
+                                           m["hits@3_all"].item(), m["hits@10_all"].item()))
 
 
 if __name__ == "__main__":

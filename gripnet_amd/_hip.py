@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 164                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 165                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -108,6 +108,9 @@ SIGNATURES = {
     "gn_kge_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),
     "gn_kge_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
+    "gn_kge_rank_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
+    "gn_kge_rank_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
+    "gn_kge_topk_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
     "gn_negative_sampler_create": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, C.POINTER(_p)]),
     "gn_negative_sampler_destroy": (None, [_p]),
     "gn_negative_sampler_sample": (_int, [_p, C.c_uint64, _p, _p, _p, _p]),
@@ -1515,6 +1518,61 @@ def distmult_topk(z, nodes, edge_type, weight, k, known=None):
     _call("gn_distmult_topk_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], ptr(nodes),
           ptr(et), q, int(k), _known_handle(known, z, weight), ptr(scores), ptr(ids), ptr(error_flag(z.device)),
           stream_ptr(z.device))
+    return scores, ids
+
+
+KGE_SIDES = {"tail": 0, "head": 1}                                             # GN_KGE_SIDE_* of include/gripnet_hip.h
+KGE_RANK_MAX_ROW = 128                                                         # floats of an entity row the ranking kernels take
+
+
+def _kge_rank_operands(model, ent, rel, side, known, queries):
+    """(model id, side id, hidden size, known handle, workspace, its size) of a KGE ranking call, shapes checked."""
+    if side not in KGE_SIDES:
+        raise ValueError("side must be 'tail' or 'head', got {!r}".format(side))
+    m = KGE_MODELS[model]
+    h = rel.shape[1] // 2 if model == "ComplEx" else rel.shape[1]
+    de = 2 * h if model in ("ComplEx", "RotatE") else h
+    if ent.shape[1] != de or (model == "ComplEx" and rel.shape[1] != 2 * h):
+        raise ValueError("{}: entity rows of {} and relation rows of {} columns do not belong together".format(
+            model, ent.shape[1], rel.shape[1]))
+    if de > KGE_RANK_MAX_ROW:
+        raise ValueError("{}: the ranking kernels take entity rows of at most {} floats (hidden_dim <= {}), got {}".format(
+            model, KGE_RANK_MAX_ROW, KGE_RANK_MAX_ROW * h // de, de))
+    need = int(load().gn_kge_rank_workspace_bytes(m, rel.shape[0], h, queries))
+    ws = torch.empty((need,), dtype=torch.uint8, device=ent.device) if need else None
+    return m, KGE_SIDES[side], h, _known_handle(known, ent, rel), ws, need
+
+
+def kge_rank(model, ent, rel, sample, et, gamma, divisor, side="tail", known=None):
+    """(greater, ties) int32 [E] of the triples (sample[0, e], et[e], sample[1, e]) against every candidate tail (`side`
+    "tail") or head ("head") that is not in `known` (gn_kge_rank_f32).  `ent`, `rel`: rows contiguous fp32."""
+    idx, head, tail, e = edge_rows(sample)
+    types = i64_vec(et)
+    if types.numel() != e:
+        raise ValueError("edge_type has {} entries for {} triples".format(types.numel(), e))
+    m, sd, h, kh, ws, need = _kge_rank_operands(model, ent, rel, side, known, e)
+    fixed, truth = (head, tail) if sd == 0 else (tail, head)
+    greater = torch.empty((e,), dtype=torch.int32, device=ent.device)
+    ties = torch.empty((e,), dtype=torch.int32, device=ent.device)
+    _call("gn_kge_rank_f32", m, sd, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, fixed, truth, ptr(types), e,
+          float(gamma), float(divisor), kh, ptr(greater), ptr(ties), ptr(error_flag(ent.device)), ptr(ws), need,
+          stream_ptr(ent.device))
+    return greater, ties
+
+
+def kge_topk(model, ent, rel, entities, et, k, gamma, divisor, side="tail", known=None):
+    """(scores fp32 [Q, k], ids int64 [Q, k]) of the queries (entities[q], et[q]) (gn_kge_topk_f32)."""
+    entities, types = i64_vec(entities), i64_vec(et)
+    if entities.dim() != 1 or types.dim() != 1 or entities.numel() != types.numel():
+        raise ValueError("entities and edge_type must be 1-D of one length, got {} and {}".format(
+            tuple(entities.shape), tuple(types.shape)))
+    q = int(entities.numel())
+    m, sd, h, kh, ws, need = _kge_rank_operands(model, ent, rel, side, known, q)
+    scores = torch.empty((q, k), dtype=torch.float32, device=ent.device)
+    ids = torch.empty((q, k), dtype=torch.int64, device=ent.device)
+    _call("gn_kge_topk_f32", m, sd, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(entities), ptr(types), q,
+          int(k), float(gamma), float(divisor), kh, ptr(scores), ptr(ids), ptr(error_flag(ent.device)), ptr(ws), need,
+          stream_ptr(ent.device))
     return scores, ids
 
 

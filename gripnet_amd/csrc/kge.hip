@@ -19,49 +19,13 @@
 // leaves a partial that k_kge_combine adds in chunk order.  g = grad_out * sigma(-s) when the forward returned the
 // log-sigmoid.  The contribution of a record is g * ds/d(row), a function of the three rows per model and role.
 #include "common.h"
+#include "kge_term.cuh"
 #include "plan_device.cuh"
 #include "seg_sort.cuh"
 
 namespace {
 
-enum { kTransE = GN_KGE_TRANSE, kDistMult = GN_KGE_DISTMULT, kComplEx = GN_KGE_COMPLEX, kRotatE = GN_KGE_ROTATE };
 enum { kHead = 0, kTail = 1, kRelation = 2 };
-
-template <int M> struct Traits;
-template <> struct Traits<kTransE>   { static constexpr int ent_parts = 1; };
-template <> struct Traits<kDistMult> { static constexpr int ent_parts = 1; };
-template <> struct Traits<kComplEx>  { static constexpr int ent_parts = 2; };
-template <> struct Traits<kRotatE>   { static constexpr int ent_parts = 2; };   // (its relation operand has two parts as well: cos, sin)
-
-// One column of a triple: (hr, hi), (rr, ri), (tr, ti); the imaginary members are unused by the real models.  For RotatE
-// (rr, ri) = (cos theta, sin theta).
-struct Col { float hr, hi, rr, ri, tr, ti; };
-
-// the column's term of the sum (TransE and RotatE: of the distance that gamma is reduced by).  No contraction into fused
-// multiply-adds here or in dscore: every product is rounded as the reference's element-wise kernels round it, so a term that
-// cancels inside (ComplEx's four products, a short (a, b) of RotatE) carries the reference's own error, not another one.
-template <int M>
-__device__ __forceinline__ float term(const Col& c) {
-#pragma clang fp contract(off)
-    if constexpr (M == kTransE) {
-        return fabsf((c.hr + c.rr) - c.tr);
-    } else if constexpr (M == kDistMult) {
-        return (c.hr * c.rr) * c.tr;
-    } else if constexpr (M == kComplEx) {
-        const float re = c.hr * c.rr - c.hi * c.ri;
-        const float im = c.hr * c.ri + c.hi * c.rr;
-        return re * c.tr + im * c.ti;
-    } else {
-        const float a = (c.hr * c.rr - c.hi * c.ri) - c.tr;
-        const float b = (c.hr * c.ri + c.hi * c.rr) - c.ti;
-        return sqrtf(a * a + b * b);
-    }
-}
-
-template <int M>
-__device__ __forceinline__ float finish(float sum, float gamma) {
-    return (M == kTransE || M == kRotatE) ? gamma - sum : sum;
-}
 
 // ds / d(row of ROLE) for one column: (d0, d1) = derivative with respect to the real and the imaginary member (d1 unused
 // by the real models).  RotatE's relation derivative is with respect to the phase's source r = theta * divisor: d0 only.
@@ -139,17 +103,6 @@ __device__ __forceinline__ void load_cols(const Tables& t, int hh, int tt, int r
         c[3] = {a.w, ai.w, w.w, wi.w, b.w, bi.w};
     } else {
         c[0] = {ph[0], two ? ph[t.h] : 0.f, pr[0], two ? pri[0] : 0.f, pt[0], two ? pt[t.h] : 0.f};
-    }
-}
-
-// cos / sin of the relation table's phases, once per call: [R, H] each, rows H apart
-__global__ void k_kge_trig(const float* __restrict__ rel, int64_t ld_rel, int64_t r, int h, float divisor,
-                           float* __restrict__ cos_out, float* __restrict__ sin_out) {
-    const int64_t total = r * h;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const float theta = rel[(i / h) * ld_rel + (i % h)] / divisor;
-        cos_out[i] = cosf(theta);
-        sin_out[i] = sinf(theta);
     }
 }
 

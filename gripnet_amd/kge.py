@@ -5,6 +5,7 @@ itself: the same constructor signature, attributes, state-dict keys, initialisat
 one HIP launch (csrc/kge.hip) instead of three ``index_select``s of [E, D] and a dozen element-wise kernels, and its
 gradients come from a sort-based segmented reduction instead of autograd's scatter-adds.
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -73,3 +74,39 @@ class KGEModel(nn.Module):
     def score(self, sample, et):
         """The raw scores [E] (before the log-sigmoid): for metrics and tests."""
         return self._score(sample, et, False)
+
+    def _eval_operands(self, *index):
+        ent, rel = self.entity_embedding, self.relation_embedding
+        _hip.require_gpu(ent, rel, *index)
+        return _hip.f32_rows(ent.detach()), _hip.f32_rows(rel.detach())
+
+    def rank(self, sample, et, side="tail", known=None):
+        """Filtered ranking of the triples (h, r, t) = (sample[0], et, sample[1]) against every candidate entity:
+        ``(greater, ties)``, int32 [E] each.  ``side="tail"``: the candidates t' != t whose (r, h, t') is not in `known`
+        (a KnownPairs, None: no filter) with score s(h, r, t') > s(h, r, t) and == s(h, r, t).  ``side="head"``: the
+        candidates h' != h of (., r, t), filtered by a KnownPairs whose rows are keyed (r, t) - one built from the FLIPPED
+        lists, ``KnownPairs([(ei.flip(0), et), ...], nentity, nrelation)``; the filter given for the tail side does not
+        serve the head side (TransE, ComplEx and RotatE are not symmetric; neither are their known pairs).  Raw scores
+        (``score``), not their log-sigmoid; the true triple's score is the scan's own value for that candidate.  No
+        autograd, no host synchronisation: an id out of range gives -1 / -1 and the IndexError at the next check
+        (``utils.ranking_metrics`` / ``_hip.raise_if_index_errors``); ``utils.ranking_metrics`` turns the counts into MRR
+        and Hits@k.  Entity rows of at most 128 floats (hidden_dim <= 128 for TransE and DistMult, <= 64 for ComplEx and
+        RotatE): ValueError beyond, there is no torch fallback."""
+        ent, rel = self._eval_operands(sample, et)
+        gamma, divisor = self._constants()
+        with torch.no_grad():
+            return _hip.kge_rank(self.model_name, ent, rel, sample, et, gamma, divisor, side, known)
+
+    def top_k(self, entities, et, k, side="tail", known=None):
+        """The `k` (1..64) best partners of every query (entities[q], et[q]) that are not in `known`: the tails of
+        (entities[q], r, .) for ``side="tail"``, the heads of (., r, entities[q]) for ``side="head"`` (`known` keyed as for
+        ``rank``: built from the flipped lists for the head side).  ``(scores, ids)``: fp32 raw scores [Q, k] and int64
+        ids [Q, k], by score descending then id ascending, padded with -inf / -1 when fewer than k candidates remain.  No
+        autograd, no host synchronisation (ids out of range: NaN / -1 and the IndexError at the next check).  Width limit
+        as for ``rank``."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
+            raise ValueError("k must be an integer in [1, 64], got {!r}".format(k))
+        ent, rel = self._eval_operands(entities, et)
+        gamma, divisor = self._constants()
+        with torch.no_grad():
+            return _hip.kge_topk(self.model_name, ent, rel, entities, et, int(k), gamma, divisor, side, known)

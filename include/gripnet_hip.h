@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 164 /* 0.1.58 */
+#define GN_VERSION 165 /* 0.1.59 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -668,6 +668,38 @@ GN_API gn_status gn_distmult_topk_f32(const float* z, int64_t ld_z, int64_t num_
                                int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* edge_type, int64_t num_queries,
                                int64_t k, const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids,
                                int32_t* error_flag, void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Filtered ranking and top-k retrieval for the knowledge-graph-embedding scorers (GN_KGE_*; tables, gamma and
+ * phase_divisor as for gn_kge_forward_f32, scores are the raw s, not their log-sigmoid).  A query is (fixed[e],
+ * edge_type[e]) and a side: GN_KGE_SIDE_TAIL - fixed is the head, the candidates are the tails t' of (fixed, r, t');
+ * GN_KGE_SIDE_HEAD - fixed is the tail, the candidates are the heads h' of (h', r, fixed).  `known` (nullable) filters the
+ * candidates whose (relation, fixed, candidate) is a known pair: its rows are keyed (relation, fixed entity), so for the
+ * head side it is built from the FLIPPED lists (u = tail, v = head).
+ *   rank:  greater[e] / ties[e] = the non-known candidates c != truth[e] with s(c) > s(truth[e]) / s(c) == s(truth[e]);
+ *   top-k: the k (1..64) best non-known candidates, score descending then id ascending: scores[e * k + j], ids[e * k + j],
+ *          padded with -inf / -1.
+ * A candidate's score depends on the query's and the candidate row's bits and a fixed column order only (equal rows tie),
+ * and the true score is the scan's own value for that candidate.  DistMult and ComplEx run on the fp32 matrix cores (the
+ * engine of gn_distmult_rank_f32, fed with query rows that a small launch prepares), TransE and RotatE on the vector ALU
+ * with the arithmetic of the forward's terms.  No [Q, n] or [Q, n, D] buffer, no float atomics, no host synchronisation.
+ * A query with an id out of range gets -1 / -1 (rank) or NaN / -1 (top-k) and sets bit 0 of *error_flag.  Entity rows of
+ * at most 128 floats: hidden_dim <= 128 (TransE, DistMult), <= 64 (ComplEx, RotatE); GN_ERR_UNSUPPORTED beyond.  Scratch:
+ * gn_kge_rank_workspace_bytes bytes, 16-byte aligned (RotatE: cos / sin of the relation table; DistMult, ComplEx: the
+ * query rows [Q, De]; TransE: 0).  `known` must have been built for the same num_entities and num_relations. */
+#define GN_KGE_SIDE_TAIL 0
+#define GN_KGE_SIDE_HEAD 1
+GN_API size_t gn_kge_rank_workspace_bytes(int model, int64_t num_relations, int64_t hidden_dim, int64_t num_queries);
+GN_API gn_status gn_kge_rank_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                          int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                          const int64_t* truth, const int64_t* edge_type, int64_t num_queries, float gamma,
+                          float phase_divisor, const gn_known_pairs* known /* nullable */, int32_t* greater, int32_t* ties,
+                          int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream);
+GN_API gn_status gn_kge_topk_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                          int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                          const int64_t* edge_type, int64_t num_queries, int64_t k, float gamma, float phase_divisor,
+                          const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids, int32_t* error_flag,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* Independent small products in ONE launch.  Between gn_dense_batch_begin() and gn_dense_batch_end(stream) (per host thread,
  * not nested) the calls that carry GN_GEMM_JOIN_BATCH / GN_XTG_JOIN_BATCH - those of gn_gemm_f32 that take the deep-and-narrow kernel (a single product with at most 64 rows or 32 columns
