@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 165                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 166                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -61,6 +61,8 @@ SIGNATURES = {
     "gn_graph_aggregate_chain_f32": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _p, _p]),
     "gn_graph_gather_chained_f32": (_int, [_p, _p, _i64, _p]),
     "gn_graph_aggregate_tail_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _p, _p, _p, _p, _int, _p]),
+    "gn_graph_split_applicable": (_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _i64]),
+    "gn_graph_aggregate_split_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _int, _p, _i64, _p, _p, _p]),
     "gn_graph_plan_build_transpose": (_int, [_p, _p]),
     "gn_graph_aggregate_t_f32": (_int, [_p, _p, _i64, _i64, _p, _i64, _p]),
     "gn_xtg_wide_supported": (_int, [_i64, _i64, _i64]),
@@ -839,6 +841,26 @@ class GraphPlan(Handle):
         _call("gn_graph_aggregate_f32", self._h, ptr(xw), ld(xw), xw.shape[1], ptr(weight),
               0 if weight is None else weight.shape[1], ptr(bias), int(bool(relu)),
               ptr(out), ld(out), _ref(sc), _ref(pd), stream_ptr(xw.device), tag="gn_graph_aggregate_f32[{}]".format(self.kind))
+        return out
+
+    def split_ok(self, head: torch.Tensor, tail: torch.Tensor, fout: int) -> bool:
+        """True when `aggregate_split(head, tail, ...)` takes these operands (the library's own answer: widths, alignment,
+        leading dimensions, environment switches).  Launches nothing."""
+        return bool(load().gn_graph_split_applicable(self._h, head.data_ptr(), ld(head), head.shape[1], tail.data_ptr(), ld(tail),
+                                                     head.shape[1] + tail.shape[1], int(fout)))
+
+    def aggregate_split(self, head: torch.Tensor, tail: torch.Tensor, bias, relu: bool, out: torch.Tensor, weight: torch.Tensor,
+                        side=None, planes=None):
+        """`aggregate(cat([head, tail], 1), ..., weight=weight)` without the concatenation: a gathered row is read from the
+        two tables where they lie (gn_graph_aggregate_split_f32; same bits; raises Unsupported for what it does not cover)."""
+        sc = side_copy(side)
+        pd = None
+        if planes is not None:
+            pd = planes[0].desc(planes[1], planes[2])
+            planes[0].generation += 1
+        _call("gn_graph_aggregate_split_f32", self._h, ptr(head), ld(head), head.shape[1], ptr(tail), ld(tail),
+              head.shape[1] + tail.shape[1], ptr(weight), weight.shape[1], ptr(bias), int(bool(relu)), ptr(out), ld(out), _ref(sc),
+              _ref(pd), stream_ptr(head.device), tag="gn_graph_aggregate_split_f32[{}]".format(self.kind))
         return out
 
     def chain_ok(self, nxt: "GraphPlan", x: torch.Tensor, weight: torch.Tensor, bias, out: torch.Tensor, out_next: torch.Tensor) -> bool:

@@ -70,6 +70,14 @@ struct AggTail {
     int relu;
 };
 
+// A gathered row kept in two tables (k_aggregate_transform_split): its first head_cols columns are row `col` of AggArgs::table
+// (leading dimension ld_table), the rest row `col` of `tail` - a concat that is read where its parts lie, not built
+struct AggSplit {
+    const float* tail;     // [table rows, features - head_cols], 16-byte aligned
+    uint32_t ld_tail;      // % 4 == 0
+    int head_cols;         // 16, 32 or 48 of the 64
+};
+
 // The fused row copy of a launch (a concat slot), streamed by the whole grid; where in the kernel is the caller's choice
 // (the gather family streams it before its own rows, k_col_gather behind them: nothing depends on the order).  The kernel
 // hands in its global thread index and the grid's thread count: blockDim read inside a __device__ function compiles to
@@ -143,6 +151,11 @@ gn_status launch_aggregate_bf16(const AggArgs& a, int lpe, bool by_group, hipStr
 gn_status launch_aggregate_transform(const AggArgs& a, const float* w, int fout, hipStream_t st);
 // the 64 -> 16 shuffle form with the deferred tail transform of the table's columns 48..63
 gn_status launch_aggregate_transform_tail(const AggArgs& a, const float* w, int fout, const AggTail& tail, hipStream_t st);
+// the 64 -> 16 shuffle form over a row kept in two tables; split_source_refusal: why it does not take these operands (null:
+// it does), asked without launching
+const char* split_source_refusal(const float* head, int64_t ld_head, int64_t head_cols, const float* tail, int64_t ld_tail,
+                                 int64_t features, int64_t fout);
+gn_status launch_aggregate_transform_split(const AggArgs& a, const float* w, int fout, const AggSplit& split, hipStream_t st);
 gn_status launch_aggregate_mfma(const AggArgs& a, const float* w, int fout, hipStream_t st);
 // the three bf16 terms of src[rows, cols] into columns col0 .. of the planes
 gn_status launch_split_planes(const float* src, int64_t ld_src, int64_t rows, int cols, int col0, const gn_split_planes& sp, hipStream_t st);

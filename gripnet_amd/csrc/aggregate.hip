@@ -283,11 +283,16 @@ __device__ __forceinline__ float tail_bcast(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 
-template <int LPE, int FOUT, bool TAIL>
-__device__ __forceinline__ void aggregate_transform(const AggArgs& a, const float* __restrict__ w, const AggTail& tail) {
+// SPLIT (64 input features): the gathered row is kept in two tables (AggSplit) - lane j of a neighbour's group takes its 16
+// bytes from the head table where 4 j < head_cols, from the tail table otherwise: the same loads, lines, sums and bits as over
+// the materialised concatenation, which then has no reader.
+template <int LPE, int FOUT, bool TAIL, bool SPLIT = false>
+__device__ __forceinline__ void aggregate_transform(const AggArgs& a, const float* __restrict__ w, const AggTail& tail,
+                                                    const AggSplit& split = AggSplit{nullptr, 0, 0}) {
     constexpr int FIN = 4 * LPE, S = kWave / LPE, G = kWave / FOUT, KPL = FIN / G;
     static_assert(KPL % 4 == 0, "K slice per lane must cover whole float4 groups");
     static_assert(!TAIL || LPE == 16, "the deferred tail transform is the last quad of a 16-lane group");
+    static_assert(!SPLIT || !TAIL, "a split source has no deferred tail transform");
     const int lane = threadIdx.x & 63;
     const int slot = lane / LPE, j = lane % LPE;
     const int c = lane % FOUT, kq = lane / FOUT;
@@ -314,6 +319,14 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
     if (side_t0 < side_total) {
         const int64_t i = side_t0 / a.side.cols, cc = side_t0 - i * a.side.cols;
         side_first = a.side.src[i * a.side.ld_src + cc];
+    }
+    // SPLIT: this lane's table at its first feature, and that table's row stride (both fit 32 bits: the launcher checked)
+    const float* __restrict__ src = nullptr;
+    uint32_t src_ld = 0;
+    if constexpr (SPLIT) {
+        const bool in_head = 4 * j < split.head_cols;
+        src = in_head ? a.table + 4 * j : split.tail + (4 * j - split.head_cols);
+        src_ld = in_head ? (uint32_t)a.ld_table : split.ld_tail;
     }
     for (int row = wave; row < a.rows; row += n_waves) {
         // padded rows: this lane's (column, coefficient) pair sits at row * 64 + lane - no row pointers in front of it
@@ -349,7 +362,11 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
                     const uint32_t cc = (uint32_t)__shfl((int)cl, idx);
                     vv[it] = __shfl(v, idx);
                     t[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (idx < cnt) t[it] = *reinterpret_cast<const float4*>(a.table + (int64_t)cc * a.ld_table + 4 * j);
+                    if constexpr (SPLIT) {
+                        if (idx < cnt) t[it] = *reinterpret_cast<const float4*>(src + (uint64_t)cc * src_ld);
+                    } else {
+                        if (idx < cnt) t[it] = *reinterpret_cast<const float4*>(a.table + (int64_t)cc * a.ld_table + 4 * j);
+                    }
                 }
                 if constexpr (TAIL) {
 #pragma unroll
@@ -411,6 +428,10 @@ __global__ __launch_bounds__(256) void k_aggregate_transform(AggArgs a, const fl
 }
 __global__ __launch_bounds__(256) void k_aggregate_transform_tail(AggArgs a, const float* __restrict__ w, AggTail tail) {
     aggregate_transform<16, 16, true>(a, w, tail);
+}
+template <int FOUT>
+__global__ __launch_bounds__(256) void k_aggregate_transform_split(AggArgs a, const float* __restrict__ w, AggSplit split) {
+    aggregate_transform<16, FOUT, false, true>(a, w, AggTail{nullptr, nullptr, 0}, split);
 }
 
 
@@ -767,6 +788,28 @@ gn_status launch_aggregate_transform_tail(const AggArgs& a, const float* w, int 
     if (a.rows == 0) return GN_OK;
     const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
     k_aggregate_transform_tail<<<grid, 256, 0, st>>>(a, w, tail);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
+const char* split_source_refusal(const float* head, int64_t ld_head, int64_t head_cols, const float* tail, int64_t ld_tail,
+                                 int64_t features, int64_t fout) {
+    if (fast_paths_disabled()) return "the wave-per-row transform kernel is switched off (GN_DISABLE_FAST)";
+    if (features != 64 || fout != 16) return "the split source exists for 64 -> 16 features";
+    if (head_cols != 16 && head_cols != 32 && head_cols != 48) return "head_cols must be 16, 32 or 48";
+    if (!head || !tail || !aligned16(head) || !aligned16(tail)) return "both tables must be 16-byte aligned";
+    if (ld_head % 4 != 0 || ld_tail % 4 != 0) return "both leading dimensions must be multiples of 4";
+    if (ld_head < head_cols || ld_tail < features - head_cols) return "a leading dimension is smaller than its table's row";
+    if (ld_head >= (1ll << 31) || ld_tail >= (1ll << 31)) return "a leading dimension does not fit 31 bits";
+    return nullptr;
+}
+
+gn_status launch_aggregate_transform_split(const AggArgs& a, const float* w, int fout, const AggSplit& split, hipStream_t st) {
+    const char* why = split_source_refusal(a.table, a.ld_table, split.head_cols, split.tail, split.ld_tail, a.features, fout);
+    if (why) return fail(GN_ERR_UNSUPPORTED, "split source, %d -> %d features, head %d: %s", a.features, fout, split.head_cols, why);
+    if (a.rows == 0) return GN_OK;
+    const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
+    k_aggregate_transform_split<16><<<grid, 256, 0, st>>>(a, w, split);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

@@ -109,6 +109,35 @@ extern "C" gn_status gn_graph_aggregate_tail_f32(const gn_graph_plan* plan, cons
                                                gn::as_stream(stream));
 }
 
+// act( (A_norm [head | tail]) weight + bias ) without the concatenation: row `col` of the gathered table is row `col` of `head`
+// (head_cols columns) followed by row `col` of `tail` - the external layer reading the gene embedding where it lies
+extern "C" int gn_graph_split_applicable(const gn_graph_plan* plan, const float* head, int64_t ld_head, int64_t head_cols,
+                                         const float* tail, int64_t ld_tail, int64_t num_features, int64_t out_features) {
+    return plan && !gn::split_source_refusal(head, ld_head, head_cols, tail, ld_tail, num_features, out_features) ? 1 : 0;
+}
+
+extern "C" gn_status gn_graph_aggregate_split_f32(const gn_graph_plan* plan, const float* head, int64_t ld_head, int64_t head_cols,
+                                                  const float* tail, int64_t ld_tail, int64_t num_features, const float* weight,
+                                                  int64_t out_features, const float* bias, int relu, float* out, int64_t ld_out,
+                                                  const gn_side_copy* side, const gn_split_planes* planes, void* stream) {
+    GN_REQUIRE(plan != nullptr, "plan is null");
+    GN_REQUIRE(weight && out, "a weight or output pointer is null");
+    const char* why = gn::split_source_refusal(head, ld_head, head_cols, tail, ld_tail, num_features, out_features);
+    if (why)
+        return gn::fail(GN_ERR_UNSUPPORTED, "split source, %lld -> %lld features, head %lld: %s", (long long)num_features,
+                        (long long)out_features, (long long)head_cols, why);
+    GN_REQUIRE(ld_out >= out_features, "leading dimension smaller than the row length");
+    if (plan->rows == 0) return GN_OK;
+    gn::AggArgs a = forward_args(plan, head, ld_head, num_features, bias, relu, out, ld_out);
+    gn_status ss = gn::check_side(side, plan->rows, &a.side);
+    if (ss != GN_OK) return ss;
+    ss = check_planes(planes, plan, out_features, a.side);
+    if (ss != GN_OK) return ss;
+    if (planes && planes->planes) a.split = *planes;                                 // written by the kernel's own epilogue
+    return gn::launch_aggregate_transform_split(a, weight, (int)out_features, gn::AggSplit{tail, (uint32_t)ld_tail, (int)head_cols},
+                                                gn::as_stream(stream));
+}
+
 extern "C" size_t gn_split_planes_bytes(int64_t rows, int nt) {
     if (rows < 0 || nt < 1) return 0;
     return (size_t)(rows + 1) * 64 * (size_t)((3 * nt + 1) / 2);

@@ -431,11 +431,18 @@ def gene_stack_to_external(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if
     last layer is 16 -> 16, both layers hold LDS-staged plans, storage and arithmetic are the defaults, `gd` is the
     one-external `cat` form over 64 gene columns and the library takes the operands (gn_graph_chain_applicable: opt-in with
     GN_ENABLE_CHAIN=1 until the step has been measured with it); otherwise the two module calls, as before.  `gene_stack_path(gg)` tells which.  One re-associated fp32 sum apart, the chained
-    result is the separate one."""
+    result is the separate one.
+
+    The separate path does not build the gene concat where nobody else reads it (`_gene_split`): the gene layers write
+    [h1 | h2] into a buffer of their own and the external layer's launch reads slot 0 from the embedding parameter itself
+    (gn_graph_aggregate_split_f32) - no copy of the embedding, the same launches otherwise and the same bits."""
     chained = _gene_chain(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu)
     gg.__dict__["_gene_stack_path"] = "separate" if chained is None else "chained"
     if chained is not None:
         return chained
+    split = _gene_split(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu)
+    if split is not None:
+        return split
     z = gg(None, gg_edge_index, edge_weight=edge_weight, if_catout=True)
     return gd(z, gd_edge_index, mod="cat", if_relu=if_relu)
 
@@ -487,12 +494,59 @@ def _gene_chain(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu):
 
 
 class _NotChained(Exception):
-    """The library does not take the chained launches for these operands."""
+    """The library does not take the chained (or the split-source) launches for these operands."""
 
 
-def _gene_chain_memo(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu, x, out, convs, plans, run):
+def _gene_split(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu):
+    """The separate path of `gene_stack_to_external` without the concat's slot 0, or None where it does not apply: inference
+    (grad mode off) on a `start_graph`, non-relational two-layer stack over a contiguous fp32 embedding of 16, 32 or 48
+    columns (64 gene columns in all), default storage and arithmetic, `gd` the one-external `cat` form, and operands the
+    library takes (gn_graph_split_applicable).  The launches of the two module calls, minus the first layer's side copy;
+    the concat `homoGraph.forward` returns is not built, so nothing of it leaves this function."""
+    if torch.is_grad_enabled() or not isinstance(gg, homoGraph) or not isinstance(gd, interGraph):
+        return None
+    if gg.multi_relational or not gg.start_graph or len(gg.conv_list) != 2 or not gd.if_one_external:
+        return None
+    c1, c2, cd = gg.conv_list[0], gg.conv_list[1], gd.conv
+    emb = gg.embedding.detach()
+    w0, w1, w2 = emb.shape[1], c1.out_channels, c2.out_channels
+    if w0 not in (16, 32, 48) or w1 % 4 or w2 % 4 or w0 + w1 + w2 != 64 or (cd.in_channels, cd.out_channels) != (64, 16):
+        return None
+    if any(c.table_storage != "fp32" or c.arithmetic != "fp32" or not c.weight.is_contiguous() for c in (c1, c2, cd)):
+        return None
+    if emb.dtype != torch.float32 or not emb.is_contiguous() or emb.data_ptr() % 16 or not gd.target_feat.is_contiguous():
+        return None
+    _hip.require_gpu(emb, gg_edge_index, edge_weight, gd_edge_index)
+    n, dev = emb.shape[0], emb.device
+    p1, p2 = c1._gcn_plan(gg_edge_index, n, edge_weight), c2._gcn_plan(gg_edge_index, n, edge_weight)
+    pd = cd._plan(gd_edge_index, lambda: _hip.GraphPlan.bipartite(gd_edge_index, n, gd.n_target, None))
+    out = torch.empty((gd.n_target, gd.target_dim + gd.target_feat_dim), dtype=torch.float32, device=dev)
+
+    def run():
+        layers = torch.empty((n, w1 + w2), dtype=torch.float32, device=dev)      # [h1 | h2], internal
+        if not pd.split_ok(emb, layers, cd.out_channels):
+            raise _NotChained()                  # (before the first launch: nothing is recorded, nothing memoised)
+        h1 = c1._run(p1, emb, n, layers[:, :w1], True, None)                     # no side copy: slot 0 stays where it is
+        c2._run(p2, h1, n, layers[:, w1:], True, None)
+        planes = gd._cat_planes(dev)
+        pd.aggregate_split(emb, layers, cd.bias, if_relu, out[:, :gd.target_dim], cd.weight,
+                           side=(gd.target_feat, out[:, gd.target_dim:], 1),     # |target_feat| slot, same launch
+                           planes=None if planes is None else (planes, 0, gd.target_dim))
+        if planes is not None:
+            planes.tag(out)
+        return out
+
+    try:
+        return _gene_chain_memo(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu, emb, out, (c1, c2, cd), (p1, p2, pd), run,
+                                slot="_split_memo")
+    except _NotChained:
+        return None
+
+
+def _gene_chain_memo(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu, x, out, convs, plans, run, slot="_chain_memo"):
     """`run()`, or in the steady state its recorded calls (_hip.CallMemo; see homoGraph.forward): one entry under both
-    modules' guards."""
+    modules' guards, in the memo `gg` keeps under `slot`.  The guard names pointers, not values: a parameter (the
+    embedding `x` included) updated in place is read anew by the replayed launches."""
     if _hip._recorder is not None:
         return run()
     n, dev = x.shape[0], x.device
@@ -502,9 +556,9 @@ def _gene_chain_memo(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu,
              tuple([(id(c.cached_result),) + tuple([0 if p is None else p.data_ptr() for p in c._parameters.values()])
                     for c in convs]),
              _hip.launch_context(dev), _hip.env_stamp())
-    memo = gg.__dict__.get("_chain_memo")
+    memo = gg.__dict__.get(slot)
     if memo is None:
-        memo = gg.__dict__["_chain_memo"] = _hip.CallMemo()
+        memo = gg.__dict__[slot] = _hip.CallMemo()
 
     def retag():                        # the launch leaves the output's split planes: on a hit they describe THAT output
         planes = _hip.SplitPlanes.of(out, out.shape[1] // 16) if out.shape[1] % 16 == 0 else None

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 165 /* 0.1.59 */
+#define GN_VERSION 166 /* 0.1.60 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -140,6 +140,26 @@ GN_API int gn_transform_fusable(int64_t in_features, int64_t out_features);
  * the plan's rows average fewer than 48 neighbours and there are at least 4,096 of them (the second layer of the
  * node-classification stacks: no x W launch, no [N, out] round trip). */
 GN_API int gn_graph_transform_fusable(const gn_graph_plan* plan, int64_t in_features, int64_t out_features);
+
+/* gn_graph_aggregate_f32 with `weight` on the wave-per-row transform kernel over a gathered row that is kept in TWO tables:
+ * row `col` of the table is row `col` of `head` ([table rows, head_cols], leading dimension ld_head) followed by row `col`
+ * of `tail` ([table rows, num_features - head_cols], leading dimension ld_tail) - the concat of layers.py:309 read where
+ * its parts lie instead of built (the external layer of PoSE reads the gene embedding parameter itself: no copy of it
+ * into a concat slot).  Per lane the same 16-byte loads, the same sums in the same order, the same contraction: the
+ * bits of gn_graph_aggregate_f32 over the materialised [head | tail].  Plan, bias, relu, `side` and `planes` as there.
+ * Supported: num_features 64 -> out_features 16, head_cols 16, 32 or 48, both tables 16-byte aligned with leading
+ * dimensions that are multiples of 4 and below 2^31, not under GN_DISABLE_FAST; GN_ERR_UNSUPPORTED otherwise, with
+ * nothing launched.  gn_graph_split_applicable tells without launching.  Nothing is kept between calls.
+ * Measured on pose0-syn (round 19, profiles/r19_split_source.md): without the copy the first gene layer's gather launch
+ * takes 8.7-9.0 us instead of 10.8, the external launch 7.5-7.7 us over either source (7.5 over the concat), the step
+ * 1.6-2.5 us less of ~75; z and score bit for bit the parent's. */
+GN_API int gn_graph_split_applicable(const gn_graph_plan* plan, const float* head, int64_t ld_head, int64_t head_cols,
+                                     const float* tail, int64_t ld_tail, int64_t num_features, int64_t out_features);
+GN_API gn_status gn_graph_aggregate_split_f32(const gn_graph_plan* plan, const float* head, int64_t ld_head, int64_t head_cols,
+                                       const float* tail, int64_t ld_tail, int64_t num_features, const float* weight,
+                                       int64_t out_features, const float* bias, int relu, float* out, int64_t ld_out,
+                                       const gn_side_copy* side /* nullable */, const gn_split_planes* planes /* nullable */,
+                                       void* stream);
 
 /* Column-group encoding of a GCN plan for LDS-staged gathers (the gene supervertex of PoSE: 19,081 nodes, 1.45 M
  * stored edges; gcn_blocked.hip).  Applies to plans whose stored weights are all exactly 1, self loops included

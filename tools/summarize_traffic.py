@@ -28,6 +28,8 @@ WEIGHTED = {
     # one call per gene layer: its transform (two instantiations, one per layer) and its gather (same kernel, both layers)
     "gn_graph_aggregate_f32[gcn]": (("k_col_transform<32", 0.5), ("k_col_transform<16", 0.5), ("k_col_gather", 1.0)),
     "gn_graph_aggregate_f32[bipartite]": (("gn::k_aggregate_transform<16, 16>", 1.0), ("k_aggregate_transform<16, 16>", 1.0)),
+    # the external layer over the embedding and the gene layers' own buffer (layers.gene_stack_to_external, separate path)
+    "gn_graph_aggregate_split_f32[bipartite]": (("gn::k_aggregate_transform_split<16>", 1.0), ("k_aggregate_transform_split<16>", 1.0)),
     # the chained gene stack (layers.gene_stack_to_external): layer 1 with the gather that also fills layer 2's table, layer 2's
     # gather alone, the external layer with the deferred 16 -> 16 transform
     "gn_graph_aggregate_chain_f32": (("k_col_transform<32", 1.0), ("k_col_gather_next", 1.0)),
