@@ -823,25 +823,28 @@ class GraphPlan(Handle):
     def __iter__(self):          # lets `edge_index, norm = conv.cached_result` keep working
         return iter(self.export())
 
-    def aggregate(self, xw: torch.Tensor, bias, relu: bool, out: torch.Tensor, side=None, weight=None, planes=None, tail=None):
-        """out = act(A_norm xw + b), or with `weight` act((A_norm xw) weight + b) (xw is then the layer input).
-        `planes` = (SplitPlanes, col_main, col_side): the launch also leaves the bf16 split planes of its output and of
-        its side copy.  `tail` = (W2 [16, 16], b2): every gathered row's last 16 columns enter the sum as
-        relu(row[-16:] W2 + b2) (gn_graph_aggregate_tail_f32: 64 -> 16 features only, raises Unsupported otherwise)."""
+    def _forward(self, entry, source, weight, bias, relu, out, side, planes, extra=()):
+        """The forward launch `entry` over `source` (the gathered table's arguments: one table, or head and tail): the side
+        copy's and the planes' descriptors, the planes' generation bumped once, the call under its tag."""
         sc = side_copy(side)
         pd = None
         if planes is not None:
             pd = planes[0].desc(planes[1], planes[2])
             planes[0].generation += 1
-        if tail is not None:
-            _call("gn_graph_aggregate_tail_f32", self._h, ptr(xw), ld(xw), xw.shape[1], ptr(weight), weight.shape[1], ptr(bias),
-                  int(bool(relu)), ptr(out), ld(out), _ref(sc), _ref(pd), ptr(tail[0]), ptr(tail[1]), 1, stream_ptr(xw.device),
-                  tag="gn_graph_aggregate_tail_f32[{}]".format(self.kind))
-            return out
-        _call("gn_graph_aggregate_f32", self._h, ptr(xw), ld(xw), xw.shape[1], ptr(weight),
-              0 if weight is None else weight.shape[1], ptr(bias), int(bool(relu)),
-              ptr(out), ld(out), _ref(sc), _ref(pd), stream_ptr(xw.device), tag="gn_graph_aggregate_f32[{}]".format(self.kind))
+        _call(entry, self._h, *source, ptr(weight), 0 if weight is None else weight.shape[1], ptr(bias), int(bool(relu)),
+              ptr(out), ld(out), _ref(sc), _ref(pd), *extra, stream_ptr(out.device), tag="{}[{}]".format(entry, self.kind))
         return out
+
+    def aggregate(self, xw: torch.Tensor, bias, relu: bool, out: torch.Tensor, side=None, weight=None, planes=None, tail=None):
+        """out = act(A_norm xw + b), or with `weight` act((A_norm xw) weight + b) (xw is then the layer input).
+        `planes` = (SplitPlanes, col_main, col_side): the launch also leaves the bf16 split planes of its output and of
+        its side copy.  `tail` = (W2 [16, 16], b2): every gathered row's last 16 columns enter the sum as
+        relu(row[-16:] W2 + b2) (gn_graph_aggregate_tail_f32: 64 -> 16 features only, raises Unsupported otherwise)."""
+        source = (ptr(xw), ld(xw), xw.shape[1])
+        if tail is not None:
+            return self._forward("gn_graph_aggregate_tail_f32", source, weight, bias, relu, out, side, planes,
+                                 extra=(ptr(tail[0]), ptr(tail[1]), 1))
+        return self._forward("gn_graph_aggregate_f32", source, weight, bias, relu, out, side, planes)
 
     def split_ok(self, head: torch.Tensor, tail: torch.Tensor, fout: int) -> bool:
         """True when `aggregate_split(head, tail, ...)` takes these operands (the library's own answer: widths, alignment,
@@ -853,15 +856,8 @@ class GraphPlan(Handle):
                         side=None, planes=None):
         """`aggregate(cat([head, tail], 1), ..., weight=weight)` without the concatenation: a gathered row is read from the
         two tables where they lie (gn_graph_aggregate_split_f32; same bits; raises Unsupported for what it does not cover)."""
-        sc = side_copy(side)
-        pd = None
-        if planes is not None:
-            pd = planes[0].desc(planes[1], planes[2])
-            planes[0].generation += 1
-        _call("gn_graph_aggregate_split_f32", self._h, ptr(head), ld(head), head.shape[1], ptr(tail), ld(tail),
-              head.shape[1] + tail.shape[1], ptr(weight), weight.shape[1], ptr(bias), int(bool(relu)), ptr(out), ld(out), _ref(sc),
-              _ref(pd), stream_ptr(head.device), tag="gn_graph_aggregate_split_f32[{}]".format(self.kind))
-        return out
+        source = (ptr(head), ld(head), head.shape[1], ptr(tail), ld(tail), head.shape[1] + tail.shape[1])
+        return self._forward("gn_graph_aggregate_split_f32", source, weight, bias, relu, out, side, planes)
 
     def chain_ok(self, nxt: "GraphPlan", x: torch.Tensor, weight: torch.Tensor, bias, out: torch.Tensor, out_next: torch.Tensor) -> bool:
         """True when `aggregate_chain` / `nxt.gather_chained` can run this layer and the 16 -> 16 layer behind it (the

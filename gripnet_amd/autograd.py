@@ -81,6 +81,39 @@ class AbsSlotFn(torch.autograd.Function):
         return out, None
 
 
+def gcn_layer_forward(plan, x, w, b, relu, out, side, planes, storage, *, fuse_on_plan, fast):
+    """``act(A_norm (x W) + b)`` into `out`: the launches of one GCN-style layer, on the inference path (myGCN._run) and in
+    the training forward (GcnConvFn.forward) alike.  True when the launch left the offered `planes`.
+
+    bf16 storage: x W in fp32 arithmetic (layers.py:73), rounded to bf16 where the product stores it (no gn_cast_bf16 pass;
+    shapes outside the tall-skinny kernel leave a fp32 product that aggregate_bf16 rounds), gathered at half the bytes; no
+    planes.  Else fused - A_norm (x W) = (A_norm x) W, the contraction runs on the aggregated row in the gather's launch -
+    where the library has the form, else the product and then the gather (layers.py:92-100)."""
+    # fuse_on_plan: the parent's inference fused on blocked_ok or transform_ok, its training on transform_fusable; one rule changes training's bits and time: not here
+    # fast: the parent passed the layer's `arithmetic` to the product on the inference path only; one rule changes training's bits and time: not here
+    shape = (x.shape[0], w.shape[1])
+    if storage == "bf16" and w.shape[1] % 8 == 0 and _hip.ld(out) % 4 == 0 and out.data_ptr() % 16 == 0:
+        xw = torch.empty(shape, dtype=torch.bfloat16, device=x.device)
+        try:
+            _hip.gemm(x, w, xw, out_bf16=True, fast=fast)
+        except _hip.Unsupported:
+            xw = torch.empty(shape, dtype=torch.float32, device=x.device)
+            _hip.gemm(x, w, xw, fast=fast)
+        plan.aggregate_bf16(xw, b, relu, out, side)
+        return False
+    if fuse_on_plan:
+        fused = w.is_contiguous() and (plan.blocked_ok(x, w, b, out) or plan.transform_ok(w.shape[0], w.shape[1], x))
+    else:
+        fused = w.is_contiguous() and _hip.transform_fusable(w.shape[0], w.shape[1], x)
+    if fused:
+        plan.aggregate(x, b, relu, out, side, weight=w, planes=planes)
+    else:
+        xw = torch.empty(shape, dtype=torch.float32, device=x.device)
+        _hip.gemm(x, w, xw, fast=fast)
+        plan.aggregate(xw, b, relu, out, side, planes=planes)
+    return planes is not None
+
+
 class GcnConvFn(torch.autograd.Function):
     """``act(A_norm (x W) + b)`` over a cached plan (myGCN.forward, gripnet/layers.py:71-100, with the ReLU
     that follows it at layers.py:279,305,370).  ``n_out`` rows: N for a square graph, n_target for the
@@ -102,24 +135,12 @@ class GcnConvFn(torch.autograd.Function):
         if side is not None:
             side = (side[0].detach(), side[1].view(), side[2])
         b = None if bias is None else bias.detach()
-        if (storage == "bf16" and planes is None and w.shape[1] % 8 == 0 and _hip.ld(out) % 4 == 0 and out.data_ptr() % 16 == 0):
-            # bf16 storage of the gathered table under training (round 6; BASELINE config 5): the forward is the inference path's
-            # (x W rounded to bf16 where the product stores it, fp32 sums); the backward below is the fp32 layer's - rounding
-            # the table has the identity as its (straight-through) derivative, and neither dx = A^T g W^T nor dW = x^T A^T g
-            # reads the table.  What differs from fp32 training is the forward's values (and the ReLU mask they give).
-            xw = torch.empty((x.shape[0], w.shape[1]), dtype=torch.bfloat16, device=x.device)
-            try:
-                _hip.gemm(x, w, xw, out_bf16=True)
-            except _hip.Unsupported:
-                xw = torch.empty((x.shape[0], w.shape[1]), dtype=torch.float32, device=x.device)
-                _hip.gemm(x, w, xw)
-            plan.aggregate_bf16(xw, b, relu, out, side)
-        elif _hip.transform_fusable(w.shape[0], w.shape[1], x) and w.is_contiguous():
-            plan.aggregate(x, b, relu, out, side, weight=w, planes=planes)    # (A_norm x) W in one launch, as the inference path
-        else:
-            xw = torch.empty((x.shape[0], w.shape[1]), dtype=torch.float32, device=x.device)
-            _hip.gemm(x, w, xw)
-            plan.aggregate(xw, b, relu, out, side, planes=planes)
+        # bf16 storage of the gathered table under training (round 6; BASELINE config 5): the forward is the inference path's
+        # (x W rounded to bf16 where the product stores it, fp32 sums); the backward below is the fp32 layer's - rounding
+        # the table has the identity as its (straight-through) derivative, and neither dx = A^T g W^T nor dW = x^T A^T g
+        # reads the table.  What differs from fp32 training is the forward's values (and the ReLU mask they give).  (A launch
+        # that is to leave planes keeps the fp32 table: the bf16 gather writes none.)
+        gcn_layer_forward(plan, x, w, b, relu, out, side, planes, storage if planes is None else "fp32", fuse_on_plan=False, fast=False)
         ctx.plan, ctx.relu, ctx.has_bias = plan, bool(relu), bias is not None
         ctx.save_for_backward(x, w, out if relu else None)
         return (out, x_in) if passthrough else out

@@ -2,11 +2,14 @@
 //
 //   out[i, :] = act( (sum_{p in row i} coef[p] * T[col[p], :]) / max(1, rowdiv[i]) + addend[i, :] + bias )
 //
-// The kernels and their launchers live in aggregate.hip, compiled once; this header is what their callers need: the
-// argument block, the thresholds of the selection rules, the host predicates and the launchers' declarations.
+// The kernels and their launch functions live in aggregate.hip, compiled once; which of them serves a call is gather_route.hpp's
+// to say.  This header is what their callers need: the argument block, the call's facts as the route asks them, and
+// launch_gather's declaration.
 #pragma once
 
 #include "common.h"
+
+#include "gather_route.hpp"
 
 // Groups of S neighbour rows a wave requests before it consumes the first one.
 #ifndef GN_AGG_U
@@ -15,19 +18,7 @@
 #ifndef GN_AGG_U_WIDE
 #define GN_AGG_U_WIDE 8
 #endif
-// Upper bound of the launch grid (blocks of four waves); rows beyond it are taken grid-stride.
-#ifndef GN_AGG_GRID
-#define GN_AGG_GRID (256 * 8)
-#endif
-
-// Average row length below which LPE lanes own a row (k_aggregate_short: two gathers in flight per lane; k_aggregate_group:
-// GN_AGG_GROUP_U of them) instead of a wave
-#ifndef GN_AGG_SHORT_MAX_DEG
-#define GN_AGG_SHORT_MAX_DEG 8
-#endif
-#ifndef GN_AGG_GROUP_MAX_DEG
-#define GN_AGG_GROUP_MAX_DEG 48
-#endif
+// Row gathers in flight per lane of k_aggregate_group
 #ifndef GN_AGG_GROUP_U
 #define GN_AGG_GROUP_U 8
 #endif
@@ -42,7 +33,7 @@ struct AggArgs {
     const int32_t* rowptr;
     const uint32_t* col;
     const float* coef;     // nullable (all ones)
-    const float* table;    // the gathered table in fp32 (launch_aggregate_bf16 reads table_bf16 instead)
+    const float* table;    // the gathered table in fp32 (the bf16 kernels read table_bf16 instead)
     int64_t ld_table;
     int features;
     const float* rowdiv;   // nullable
@@ -94,13 +85,6 @@ __device__ __forceinline__ void side_copy_stream(gn_side_copy s, int64_t thread,
     }
 }
 
-// lanes a feature row of `units` 16-byte (or scalar) loads takes: the next power of two, one wave at the most
-inline int lanes_per_row(int64_t units) {
-    int lpe = 1;
-    while (lpe < units && lpe < kWave) lpe <<= 1;
-    return lpe;
-}
-
 inline gn_status check_side(const gn_side_copy* side, int64_t rows, gn_side_copy* out) {
     *out = gn_side_copy{nullptr, 0, nullptr, 0, 0, 0, 0};
     if (!side || side->rows == 0 || side->cols == 0) return GN_OK;
@@ -112,51 +96,82 @@ inline gn_status check_side(const gn_side_copy* side, int64_t rows, gn_side_copy
     return GN_OK;
 }
 
-// FIN in {16, 32, 64}, FOUT in {16, 32} with at least 4 input features per lane slice
-inline bool transform_fusable(int64_t fin, int64_t fout) {
-    if (fast_paths_disabled()) return false;
-    // exactly the specialisations launch_aggregate_transform has (16 -> 32 has none: its K slice per lane would be two floats)
-    return (fout == 16 && (fin == 16 || fin == 32 || fin == 64)) || (fout == 32 && (fin == 32 || fin == 64));
+// The gather's arguments of a forward call on `plan`
+inline AggArgs forward_args(const gn_graph_plan* plan, const float* xw, int64_t ld_xw, int64_t num_features, const float* bias,
+                            int relu, float* out, int64_t ld_out) {
+    AggArgs a;
+    a.rowptr = plan->rowptr.p;
+    a.col = reinterpret_cast<const uint32_t*>(plan->col.p);
+    a.coef = plan->plain_ones ? nullptr : plan->coef.p;       // (null = all ones)
+    a.table = xw;
+    a.ld_table = ld_xw;
+    a.features = (int)num_features;
+    a.rowdiv = nullptr;
+    a.addend = nullptr;
+    a.ld_addend = 0;
+    a.bias = bias;
+    a.relu = relu;
+    a.out = out;
+    a.ld_out = ld_out;
+    a.rows = (int)plan->rows;
+    a.nnz = plan->nnz;
+    a.table_rows = plan->table_rows;
+    if (plan->ell_ok) { a.ell_col = plan->ell_col.p; a.ell_coef = plan->ell_coef.p; }
+    return a;
 }
 
-// in -> out widths the matrix-core form takes (gn_graph_aggregate_f32 with weight != NULL); rows of up to
-// GN_AGG_GROUP_MAX_DEG neighbours on average (longer rows belong to a wave each: the product first, then k_aggregate)
-inline bool mfma_fusable(int64_t fin, int64_t fout, int64_t rows, int64_t nnz) {
-    if (fast_paths_disabled()) return false;
-    if (!(fin == 64 || fin == 128) || fout % 16 != 0 || fout < fin || fout > 128) return false;
-    return nnz >= 0 && nnz < GN_AGG_GROUP_MAX_DEG * rows && rows >= 4096;
+// ---- what gather_route.hpp is asked: the facts of a call, with the environment's switches read here ----
+// A getenv or a device query costs a recorded step more than the route's arithmetic (0.3-0.4 us per gather call, measured on the
+// flagship step), so a switch is read only where the call can reach the rule that asks it, and stays false elsewhere.
+inline bool switched_on(const char* value) { return value && value[0] == '1'; }
+inline bool blocked_switched_off() { return switched_on(getenv("GN_DISABLE_BLOCKED")); }     // (gcn_blocked.hip asks as well)
+
+inline unsigned past16(const void* p) { return (unsigned)(reinterpret_cast<uintptr_t>(p) & 15); }
+
+// a bare gather-reduce: no plan behind it, no weight (rgcn.hip's sum, gn_graph_aggregate_t_f32, and what forward_call starts from)
+inline route::GatherCall gather_call(const AggArgs& a) {
+    route::GatherCall c{};
+    c.kind = a.table_bf16 ? route::Source::bf16 : route::Source::f32;
+    c.rows = a.rows; c.nnz = a.nnz; c.table_rows = a.table_rows;
+    c.features = a.features; c.fout = a.features;
+    c.ld_table = a.ld_table; c.ld_out = a.ld_out;
+    c.table_at = past16(a.table_bf16 ? static_cast<const void*>(a.table_bf16) : a.table);
+    c.out_at = past16(a.out); c.bias_at = past16(a.bias);
+    c.coef = a.coef != nullptr; c.rowdiv = a.rowdiv != nullptr; c.addend = a.addend != nullptr; c.bias = a.bias != nullptr;
+    c.relu = a.relu != 0; c.side = a.side.dst != nullptr;
+    c.fast_disabled = fast_paths_disabled();
+    c.lds_table_disabled = a.rows >= route::kLdsTableRows && switched_on(getenv("GN_DISABLE_LDS_TABLE"));   // (asked from there on)
+    return c;
 }
 
-// GN_DISABLE_QUAD=1: the shuffle-based kernel for 16- and 32-wide rows as well (parity tests cover both)
-inline bool quad_gather_disabled() {
-    const char* e = getenv("GN_DISABLE_QUAD");
-    return e && e[0] == '1';
-}
-
-// (the quad kernel does not write split planes: its caller follows it with the stand-alone split)
-inline bool transform_takes_quad_kernel(int64_t fin, int64_t fout) { return fin == 16 && fout == 16 && !quad_gather_disabled(); }
-
-inline bool lds_table_disabled() {
-    const char* e = getenv("GN_DISABLE_LDS_TABLE");
-    return e && e[0] == '1';
+// a forward call on `plan` that writes rows of `width` floats (weight == null: the gathered row's own)
+inline route::GatherCall forward_call(const gn_graph_plan* plan, const AggArgs& a, const float* weight, int64_t width) {
+    route::GatherCall c = gather_call(a);
+    c.weight = weight != nullptr; c.weight_at = past16(weight); c.fout = width;
+    if (plan->blk_ok) {
+        c.blk_ok = true; c.blk_cw = plan->blk_cw; c.blk_cols = plan->blk_cols;
+        c.blocked_disabled = blocked_switched_off();
+        if (route::blocked_applicable(c)) return c;          // (the first rule of the ladder, and it reads nothing of what follows)
+    }
+    if (weight) {
+        // GN_DISABLE_QUAD=1: the shuffle-based kernel for 16-wide rows as well (parity tests cover both)
+        c.quad_disabled = switched_on(getenv("GN_DISABLE_QUAD"));
+        if (route::mfma_fusable(c.features, c.fout, c.rows, c.nnz, c.fast_disabled)) c.compute_units = compute_units();
+    }
+    return c;
 }
 
 // ---- launchers (aggregate.hip) ----
-// the fp32 gather-reduce: picks the LDS-table, short-row, lane-group or wave-per-row kernel from the shapes
-gn_status launch_aggregate(const AggArgs& a, hipStream_t st);
-// the same over a.table_bf16 with lpe = lanes_per_row(features / 8); the caller says which of the two mappings (lane groups
-// own rows, or a wave per row)
-gn_status launch_aggregate_bf16(const AggArgs& a, int lpe, bool by_group, hipStream_t st);
-// out = act( (A table) w + bias ): shuffle or quad epilogue (transform_fusable), or the matrix cores (mfma_fusable)
-gn_status launch_aggregate_transform(const AggArgs& a, const float* w, int fout, hipStream_t st);
-// the 64 -> 16 shuffle form with the deferred tail transform of the table's columns 48..63
-gn_status launch_aggregate_transform_tail(const AggArgs& a, const float* w, int fout, const AggTail& tail, hipStream_t st);
-// the 64 -> 16 shuffle form over a row kept in two tables; split_source_refusal: why it does not take these operands (null:
-// it does), asked without launching
-const char* split_source_refusal(const float* head, int64_t ld_head, int64_t head_cols, const float* tail, int64_t ld_tail,
-                                 int64_t features, int64_t fout);
-gn_status launch_aggregate_transform_split(const AggArgs& a, const float* w, int fout, const AggSplit& split, hipStream_t st);
-gn_status launch_aggregate_mfma(const AggArgs& a, const float* w, int fout, hipStream_t st);
+// The kernel `r` names over `a`: one launch function per kernel behind it.  `w` [features, fout]: the weight of the mfma and
+// transform kernels; `tail` / `split`: the extra operand of transform_tail / transform_split.  (blocked is not launched from
+// here: gcn_blocked.hip)
+gn_status launch_gather(const route::GatherRoute& r, const AggArgs& a, hipStream_t st, const float* w = nullptr, int fout = 0,
+                        const AggTail* tail = nullptr, const AggSplit* split = nullptr);
+// the route of a bare gather-reduce, launched
+inline gn_status launch_aggregate(const AggArgs& a, hipStream_t st) {
+    if (a.rows == 0 || a.features == 0) return GN_OK;
+    return launch_gather(route::gather_route(gather_call(a)), a, st);
+}
 // the three bf16 terms of src[rows, cols] into columns col0 .. of the planes
 gn_status launch_split_planes(const float* src, int64_t ld_src, int64_t rows, int cols, int col0, const gn_split_planes& sp, hipStream_t st);
 

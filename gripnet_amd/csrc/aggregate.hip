@@ -1,5 +1,5 @@
 // Destination-major gather-reduce shared by the GCN-style layers and the general RGCN path: every kernel of the family
-// and its launchers, compiled here once (aggregate.cuh: arguments, thresholds, predicates, declarations).
+// and its launch function, compiled here once (aggregate.cuh: arguments and declarations; gather_route.hpp: the selection).
 //
 //   out[i, :] = act( (sum_{p in row i} coef[p] * T[col[p], :]) / max(1, rowdiv[i]) + addend[i, :] + bias )
 //
@@ -722,16 +722,64 @@ void dispatch_lpe(int lpe, F&& f) {
     f(std::integral_constant<int, MIN>{});
 }
 
+// ---- one launch function per kernel: the geometry is the route's (gather_route.hpp), nothing is decided here ----
+using route::Gather;
+using route::GatherRoute;
+
 template <typename Row>
-void launch_wave_per_row(const AggArgs& a, int lpe, hipStream_t st) {
-    const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
-    dispatch_lpe<64>(lpe, [&](auto l) { k_aggregate<Row, decltype(l)::value><<<grid, 256, 0, st>>>(a); });
+void launch_wave(const AggArgs& a, const GatherRoute& r, hipStream_t st) {
+    dispatch_lpe<64>(r.lpe, [&](auto l) { k_aggregate<Row, decltype(l)::value><<<r.grid, r.block, 0, st>>>(a); });
 }
 
 template <typename Row>
-void launch_group_per_row(const AggArgs& a, int lpe, hipStream_t st) {
-    const int grid = (int)ceil_div((int64_t)a.rows * lpe, 256);              // one row per lane group, no grid-stride loop
-    dispatch_lpe<32>(lpe, [&](auto l) { k_aggregate_group<Row, decltype(l)::value, GN_AGG_GROUP_U><<<grid, 256, 0, st>>>(a); });
+void launch_group(const AggArgs& a, const GatherRoute& r, hipStream_t st) {
+    dispatch_lpe<32>(r.lpe, [&](auto l) { k_aggregate_group<Row, decltype(l)::value, GN_AGG_GROUP_U><<<r.grid, r.block, 0, st>>>(a); });
+}
+
+void launch_short(const AggArgs& a, const GatherRoute& r, hipStream_t st) {
+    dispatch_lpe<16>(r.lpe, [&](auto l) { k_aggregate_short<decltype(l)::value><<<r.grid, r.block, 0, st>>>(a); });
+}
+
+gn_status launch_lds_table(const AggArgs& a, const GatherRoute& r, hipStream_t st) {
+    gn_status ls = GN_OK;
+    dispatch_lpe<16, 4>(r.lpe, [&](auto l) {
+        ls = allow_large_lds(reinterpret_cast<const void*>(k_aggregate_lds_table<decltype(l)::value>), 160 * 1024);
+        if (ls == GN_OK) k_aggregate_lds_table<decltype(l)::value><<<r.grid, r.block, r.lds, st>>>(a);
+    });
+    return ls;
+}
+
+gn_status launch_mfma(const AggArgs& a, const GatherRoute& r, const float* w, int fout, hipStream_t st) {
+    gn_status ls = GN_OK;
+    dispatch_lpe<32, 16>(r.lpe, [&](auto l) {
+        ls = allow_large_lds(reinterpret_cast<const void*>(k_aggregate_mfma<decltype(l)::value>), 160 * 1024);
+        if (ls == GN_OK) k_aggregate_mfma<decltype(l)::value><<<r.grid, r.block, r.lds, st>>>(a, w, fout, r.row_blocks);
+    });
+    return ls;
+}
+
+gn_status launch_transform(const AggArgs& a, const GatherRoute& r, const float* w, int fout, hipStream_t st) {
+    switch (a.features * 100 + fout) {
+        case 1616: k_aggregate_transform<4, 16><<<r.grid, r.block, 0, st>>>(a, w); break;
+        case 3216: k_aggregate_transform<8, 16><<<r.grid, r.block, 0, st>>>(a, w); break;
+        case 6416: k_aggregate_transform<16, 16><<<r.grid, r.block, 0, st>>>(a, w); break;
+        case 3232: k_aggregate_transform<8, 32><<<r.grid, r.block, 0, st>>>(a, w); break;
+        case 6432: k_aggregate_transform<16, 32><<<r.grid, r.block, 0, st>>>(a, w); break;
+        default: return fail(GN_ERR_UNSUPPORTED, "no fused transform for %d -> %d features", a.features, fout);
+    }
+    return GN_OK;
+}
+
+void launch_transform_quad(const AggArgs& a, const GatherRoute& r, const float* w, hipStream_t st) {
+    k_aggregate_transform_q<1><<<r.grid, r.block, 0, st>>>(a, w);
+}
+
+void launch_transform_tail(const AggArgs& a, const GatherRoute& r, const float* w, const AggTail& tail, hipStream_t st) {
+    k_aggregate_transform_tail<<<r.grid, r.block, 0, st>>>(a, w, tail);
+}
+
+void launch_transform_split(const AggArgs& a, const GatherRoute& r, const float* w, const AggSplit& split, hipStream_t st) {
+    k_aggregate_transform_split<16><<<r.grid, r.block, 0, st>>>(a, w, split);
 }
 
 }  // namespace
@@ -743,110 +791,26 @@ gn_status launch_split_planes(const float* src, int64_t ld_src, int64_t rows, in
     return GN_OK;
 }
 
-gn_status launch_aggregate_mfma(const AggArgs& a, const float* w, int fout, hipStream_t st) {
-    if (a.rows == 0) return GN_OK;
-    const int lpe = a.features / 4, rpi = 16 * (kWave / lpe);
-    const int row_blocks = (int)ceil_div(a.rows, rpi);
-    const size_t lds = (size_t)a.features * fout * 6 + 2 * (size_t)rpi * (a.features + 4) * sizeof(float);
-    const int grid = lpe == 16 ? row_blocks : std::min(row_blocks, compute_units());     // (see k_aggregate_mfma)
-    gn_status ls = GN_OK;
-    dispatch_lpe<32, 16>(lpe, [&](auto l) {
-        ls = allow_large_lds(reinterpret_cast<const void*>(k_aggregate_mfma<decltype(l)::value>), 160 * 1024);
-        if (ls == GN_OK) k_aggregate_mfma<decltype(l)::value><<<grid, 1024, lds, st>>>(a, w, fout, row_blocks);
-    });
-    if (ls != GN_OK) return ls;
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-gn_status launch_aggregate_transform(const AggArgs& a, const float* w, int fout, hipStream_t st) {
-    if (a.rows == 0) return GN_OK;
-    const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
-    const int key = a.features * 100 + fout;
-    // 16-wide rows: quad gathers (14.8 vs 16.4 us on the second gene layer of pose0-syn); 32-wide rows are faster
-    // with one 16-byte load per lane and neighbour (k_aggregate_transform<8, 16> 19.2 us, the quad form 21.5)
-    if (key == 1616 && a.ld_table % 4 == 0 && aligned16(a.table) && !quad_gather_disabled()) {
-        k_aggregate_transform_q<1><<<grid, 256, 0, st>>>(a, w);
-        GN_LAUNCH_CHECK();
-        return GN_OK;
+gn_status launch_gather(const GatherRoute& r, const AggArgs& a, hipStream_t st, const float* w, int fout, const AggTail* tail,
+                        const AggSplit* split) {
+    gn_status s = GN_OK;
+    switch (r.kernel) {
+        case Gather::mfma: s = launch_mfma(a, r, w, fout, st); break;
+        case Gather::transform: s = launch_transform(a, r, w, fout, st); break;
+        case Gather::transform_quad: launch_transform_quad(a, r, w, st); break;
+        case Gather::transform_tail: launch_transform_tail(a, r, w, *tail, st); break;
+        case Gather::transform_split: launch_transform_split(a, r, w, *split, st); break;
+        case Gather::lds_table: s = launch_lds_table(a, r, st); break;
+        case Gather::short_rows: launch_short(a, r, st); break;
+        case Gather::group: launch_group<RowF32>(a, r, st); break;
+        case Gather::wave: launch_wave<RowF32>(a, r, st); break;
+        case Gather::wave_scalar: launch_wave<RowScalar>(a, r, st); break;
+        case Gather::bf16_group: launch_group<RowBf16>(a, r, st); break;
+        case Gather::bf16_wave: launch_wave<RowBf16>(a, r, st); break;
+        case Gather::blocked:
+        case Gather::refused: return fail(GN_ERR_UNSUPPORTED, "internal: this route has no kernel in aggregate.hip");
     }
-    switch (key) {
-        case 1616: k_aggregate_transform<4, 16><<<grid, 256, 0, st>>>(a, w); break;
-        case 3216: k_aggregate_transform<8, 16><<<grid, 256, 0, st>>>(a, w); break;
-        case 6416: k_aggregate_transform<16, 16><<<grid, 256, 0, st>>>(a, w); break;
-        case 3232: k_aggregate_transform<8, 32><<<grid, 256, 0, st>>>(a, w); break;
-        case 6432: k_aggregate_transform<16, 32><<<grid, 256, 0, st>>>(a, w); break;
-        default: return fail(GN_ERR_UNSUPPORTED, "no fused transform for %d -> %d features", a.features, fout);
-    }
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-gn_status launch_aggregate_transform_tail(const AggArgs& a, const float* w, int fout, const AggTail& tail, hipStream_t st) {
-    if (a.features != 64 || fout != 16)
-        return fail(GN_ERR_UNSUPPORTED, "the deferred tail transform exists for 64 -> 16 features, got %d -> %d", a.features, fout);
-    if (a.rows == 0) return GN_OK;
-    const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
-    k_aggregate_transform_tail<<<grid, 256, 0, st>>>(a, w, tail);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-const char* split_source_refusal(const float* head, int64_t ld_head, int64_t head_cols, const float* tail, int64_t ld_tail,
-                                 int64_t features, int64_t fout) {
-    if (fast_paths_disabled()) return "the wave-per-row transform kernel is switched off (GN_DISABLE_FAST)";
-    if (features != 64 || fout != 16) return "the split source exists for 64 -> 16 features";
-    if (head_cols != 16 && head_cols != 32 && head_cols != 48) return "head_cols must be 16, 32 or 48";
-    if (!head || !tail || !aligned16(head) || !aligned16(tail)) return "both tables must be 16-byte aligned";
-    if (ld_head % 4 != 0 || ld_tail % 4 != 0) return "both leading dimensions must be multiples of 4";
-    if (ld_head < head_cols || ld_tail < features - head_cols) return "a leading dimension is smaller than its table's row";
-    if (ld_head >= (1ll << 31) || ld_tail >= (1ll << 31)) return "a leading dimension does not fit 31 bits";
-    return nullptr;
-}
-
-gn_status launch_aggregate_transform_split(const AggArgs& a, const float* w, int fout, const AggSplit& split, hipStream_t st) {
-    const char* why = split_source_refusal(a.table, a.ld_table, split.head_cols, split.tail, split.ld_tail, a.features, fout);
-    if (why) return fail(GN_ERR_UNSUPPORTED, "split source, %d -> %d features, head %d: %s", a.features, fout, split.head_cols, why);
-    if (a.rows == 0) return GN_OK;
-    const int grid = (int)std::min<int64_t>(ceil_div(a.rows, 4), GN_AGG_GRID);
-    k_aggregate_transform_split<16><<<grid, 256, 0, st>>>(a, w, split);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-gn_status launch_aggregate(const AggArgs& a, hipStream_t st) {
-    if (a.rows == 0 || a.features == 0) return GN_OK;
-    const bool vec = (a.features % 4 == 0) && (a.ld_table % 4 == 0) && (a.ld_out % 4 == 0) && aligned16(a.table) &&
-                     aligned16(a.out);
-    const int lpe = lanes_per_row(vec ? a.features / 4 : a.features);
-    // many short rows over a table that fits the LDS, nothing but a plain sum: the table is gathered from there
-    if (vec && lpe >= 4 && lpe <= 16 && a.nnz > 0 && a.nnz < 8 * (int64_t)a.rows && a.rows >= 65536 && !a.coef && !a.rowdiv &&
-        !a.addend && !a.bias && !a.relu && !a.side.dst && a.table_rows > 0 &&
-        (size_t)a.table_rows * a.features * sizeof(float) <= 128 * 1024 && !fast_paths_disabled() && !lds_table_disabled()) {
-        const size_t lds = (size_t)(a.table_rows + 1) * a.features * sizeof(float);
-        const int wgs = (int)std::min<int64_t>(256, ceil_div((int64_t)a.rows * lpe, 2 * 1024));
-        gn_status ls = GN_OK;
-        dispatch_lpe<16, 4>(lpe, [&](auto l) {
-            ls = allow_large_lds(reinterpret_cast<const void*>(k_aggregate_lds_table<decltype(l)::value>), 160 * 1024);
-            if (ls == GN_OK) k_aggregate_lds_table<decltype(l)::value><<<wgs, 1024, lds, st>>>(a);
-        });
-        if (ls != GN_OK) return ls;
-    } else if (vec && lpe <= 16 && a.nnz >= 0 && a.nnz < GN_AGG_SHORT_MAX_DEG * (int64_t)a.rows && !fast_paths_disabled()) {
-        const int sgrid = (int)std::min<int64_t>(ceil_div((int64_t)a.rows * lpe, 256), GN_AGG_GRID);
-        dispatch_lpe<16>(lpe, [&](auto l) { k_aggregate_short<decltype(l)::value><<<sgrid, 256, 0, st>>>(a); });
-    } else if (vec && lpe <= 32 && a.nnz >= 0 && a.nnz < GN_AGG_GROUP_MAX_DEG * (int64_t)a.rows && !fast_paths_disabled()) {
-        launch_group_per_row<RowF32>(a, lpe, st);
-    } else if (vec) {
-        launch_wave_per_row<RowF32>(a, lpe, st);
-    } else {
-        launch_wave_per_row<RowScalar>(a, lpe, st);
-    }
-    GN_LAUNCH_CHECK();
-    return GN_OK;
-}
-
-gn_status launch_aggregate_bf16(const AggArgs& a, int lpe, bool by_group, hipStream_t st) {
-    if (by_group) launch_group_per_row<RowBf16>(a, lpe, st); else launch_wave_per_row<RowBf16>(a, lpe, st);
+    if (s != GN_OK) return s;
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

@@ -52,11 +52,7 @@ constexpr size_t kColLdsBytes = 160 * 1024;
 constexpr int kColSlack = gn_layout::kColLayoutSlack;            // spare iterations behind the id stream: look-ahead loads never leave it
 constexpr int kWaveInts = 12;            // per wave of a range: first tile, end tile, first iteration, end iteration, the ends of its first five tiles, 3 unused
 
-bool blocked_disabled() {
-    if (gn::fast_paths_disabled()) return true;
-    const char* e = getenv("GN_DISABLE_BLOCKED");
-    return e && e[0] == '1';
-}
+bool blocked_disabled() { return gn::fast_paths_disabled() || gn::blocked_switched_off(); }
 
 // ---- T = dis * (x W), column-group-major ---------------------------------------------------------------------------
 // A quad of lanes per row: lane j holds the features 16 p + 4 j + c of its row (one contiguous 64-byte read per quad and
@@ -378,23 +374,12 @@ void launch_transform(const TransArgs& t, int cw, hipStream_t st) {
 
 }  // namespace
 
-// True when gn_graph_aggregate_f32 takes the LDS-staged path for these shapes and operands: the gather writes out (and
-// reads bias) in column groups of blk_cw floats, so an output slice at an odd column or with an odd stride keeps the
-// wave-per-row kernels.
-bool gn_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout,
-                           const float* bias, const float* out, int64_t ld_out) {
-    if (!plan->blk_ok || blocked_disabled()) return false;
-    const int cw = plan->blk_cw;
-    if ((ld_out % cw) != 0 || (reinterpret_cast<uintptr_t>(out) % (4 * cw)) != 0 ||
-        (bias && (reinterpret_cast<uintptr_t>(bias) % (4 * cw)) != 0)) return false;
-    if (!(fout == 16 || fout == 32) || fout > plan->blk_cols) return false;
-    if (w) {
-        if (!(fin == 16 || fin == 32 || fin == 64)) return false;
-        if (!gn::aligned16(w)) return false;
-    } else if (fin != fout) {
-        return false;
-    }
-    return (ld_x % 4) == 0 && gn::aligned16(x);
+// True when gn_graph_aggregate_f32 takes the LDS-staged path for these shapes and operands: the route's own answer
+// (gather_route.hpp, blocked_applicable)
+static bool blocked_route(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* w, int64_t fout,
+                          const float* bias, const float* out, int64_t ld_out) {
+    const gn::AggArgs a = gn::forward_args(plan, x, ld_x, fin, bias, 0, const_cast<float*>(out), ld_out);
+    return gn::route::gather_route(gn::forward_call(plan, a, w, fout)).kernel == gn::route::Gather::blocked;
 }
 
 namespace {
@@ -494,7 +479,7 @@ extern "C" int gn_graph_chain_applicable(const gn_graph_plan* plan, const gn_gra
                                          int64_t num_features, const float* weight, int64_t out_features, const float* bias,
                                          const float* out, int64_t ld_out, const float* out_next) {
     if (chain_disabled() || !chain_plans_match(plan, next) || !weight || out_features != 16) return 0;
-    if (!gn_blocked_applicable(plan, x, ld_x, num_features, weight, out_features, bias, out, ld_out)) return 0;
+    if (!blocked_route(plan, x, ld_x, num_features, weight, out_features, bias, out, ld_out)) return 0;
     return (reinterpret_cast<uintptr_t>(out_next) % (4 * next->blk_cw)) == 0 ? 1 : 0;
 }
 
@@ -530,7 +515,7 @@ extern "C" gn_status gn_graph_gather_chained_f32(const gn_graph_plan* plan, floa
 extern "C" int gn_graph_blocked_applicable(const gn_graph_plan* plan, const float* x, int64_t ld_x, int64_t num_features,
                                            const float* weight, int64_t out_features, const float* bias, const float* out,
                                            int64_t ld_out) {
-    return plan && gn_blocked_applicable(plan, x, ld_x, num_features, weight, out_features, bias, out, ld_out) ? 1 : 0;
+    return plan && blocked_route(plan, x, ld_x, num_features, weight, out_features, bias, out, ld_out) ? 1 : 0;
 }
 
 extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t cols, void* stream) {

@@ -60,11 +60,11 @@ gn_status gn_graph_aggregate_bf16(const gn_graph_plan* plan, const uint16_t* tab
     a.out = out; a.ld_out = ld_out; a.rows = (int)plan->rows;
     gn_status ss = gn::check_side(side, plan->rows, &a.side);
     if (ss != GN_OK) return ss;
-    // many short rows (the node-classification graphs): lane groups own rows, eight row gathers in flight per lane; else one
-    // wave per destination row (aggregate.hip: k_aggregate_group / k_aggregate on 16 bytes = 8 bf16 features per lane)
-    const int lpe = gn::lanes_per_row(num_features / 8);
-    const bool by_group = lpe <= 32 && plan->nnz < GN_AGG_GROUP_MAX_DEG * plan->rows && plan->rows >= 4096 && !gn::fast_paths_disabled();
-    return gn::launch_aggregate_bf16(a, lpe, by_group, gn::as_stream(stream));
+    // lane groups own rows or a wave per destination row (gather_route.hpp; aggregate.hip: k_aggregate_group / k_aggregate on
+    // 16 bytes = 8 bf16 features per lane)
+    gn::route::GatherCall c = gn::gather_call(a);
+    c.nnz = plan->nnz;
+    return gn::launch_gather(gn::route::gather_route(c), a, gn::as_stream(stream));
 }
 
 }  // extern "C"

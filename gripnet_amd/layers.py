@@ -21,7 +21,8 @@ import torch
 from torch.nn import Module, Parameter
 
 from . import _hip
-from .autograd import AbsSlotFn, GcnConvFn, HalfSumAbsFn, HalfSumDownFn, RgcnConvFn, Slot, SlotsCatFn, cat_slots, recording
+from .autograd import (AbsSlotFn, GcnConvFn, HalfSumAbsFn, HalfSumDownFn, RgcnConvFn, Slot, SlotsCatFn, cat_slots, gcn_layer_forward,
+                       recording)
 
 
 def _unslot(out, side):
@@ -92,26 +93,9 @@ class myGCN(Module):
         x = _hip.f32_rows(x.detach())
         if out is None:
             out = torch.empty((n_out, self.out_channels), dtype=torch.float32, device=x.device)
-        if self.table_storage == "bf16" and self.out_channels % 8 == 0 and _hip.ld(out) % 4 == 0 and out.data_ptr() % 16 == 0:
-            # layers.py:73 in fp32 arithmetic; the product's own store rounds the table to bf16 (round 6: no gn_cast_bf16 pass),
-            # shapes outside the tall-skinny kernel leave a fp32 product that aggregate_bf16 rounds
-            xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.bfloat16, device=x.device)
-            try:
-                _hip.gemm(x, self.weight, xw, out_bf16=True, fast=self.arithmetic == "fast")
-            except _hip.Unsupported:
-                xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.float32, device=x.device)
-                _hip.gemm(x, self.weight, xw, fast=self.arithmetic == "fast")
-            return plan.aggregate_bf16(xw, self.bias, relu, out, side)
-        if self.weight.is_contiguous() and (plan.blocked_ok(x, self.weight, self.bias, out) or
-                                            plan.transform_ok(self.in_channels, self.out_channels, x)):
-            # A_norm (x W) = (A_norm x) W: the contraction of layers.py:73 runs on the aggregated row
-            y = plan.aggregate(x, self.bias, relu, out, side, weight=self.weight, planes=planes)
-            self._planes_written = planes is not None
-            return y
-        xw = torch.empty((x.shape[0], self.out_channels), dtype=torch.float32, device=x.device)
-        _hip.gemm(x, self.weight, xw, fast=self.arithmetic == "fast")               # layers.py:73
-        self._planes_written = planes is not None
-        return plan.aggregate(xw, self.bias, relu, out, side, planes=planes)     # layers.py:92-100
+        self._planes_written = gcn_layer_forward(plan, x, self.weight, self.bias, relu, out, side, planes, self.table_storage,
+                                                 fuse_on_plan=True, fast=self.arithmetic == "fast")
+        return out
 
     def forward(self, x, edge_index, edge_weight=None, *, _out=None, _relu=False, _side=None, _pass=False):
         # (_pass: also return x, for the concat that holds it - homoGraph's training path; GcnConvFn)
@@ -452,30 +436,46 @@ def gene_stack_path(gg):
     return gg.__dict__.get("_gene_stack_path")
 
 
-def _gene_chain(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu):
-    """The chained launches of `gene_stack_to_external`, or None where they do not apply."""
+def _gene_operands(gg, gd, gg_edge_index, edge_weight, gd_edge_index, own):
+    """What `_gene_chain` and `_gene_split` share, or None where neither applies: inference (grad mode off) on a
+    `start_graph`, non-relational two-layer stack in front of the one-external 64 -> 16 `cat` form, default storage and
+    arithmetic, contiguous weights and target features.  `own(c1, c2, cd)`: the path's own tests, its input table or None.
+    Returns (table, the three convs, their plans, the output tensor)."""
     if torch.is_grad_enabled() or not isinstance(gg, homoGraph) or not isinstance(gd, interGraph):
         return None
     if gg.multi_relational or not gg.start_graph or len(gg.conv_list) != 2 or not gd.if_one_external:
         return None
-    c1, c2, cd = gg.conv_list[0], gg.conv_list[1], gd.conv
-    widths = [gg.embedding.shape[1], c1.out_channels, c2.out_channels]
-    if (c2.in_channels, c2.out_channels) != (16, 16) or sum(widths) != 64 or (cd.in_channels, cd.out_channels) != (64, 16):
+    convs = c1, c2, cd = gg.conv_list[0], gg.conv_list[1], gd.conv
+    if gg.embedding.shape[1] + c1.out_channels + c2.out_channels != 64 or (cd.in_channels, cd.out_channels) != (64, 16):
         return None
-    if any(c.table_storage != "fp32" or c.arithmetic != "fp32" or not c.weight.is_contiguous() for c in (c1, c2, cd)):
+    if any(c.table_storage != "fp32" or c.arithmetic != "fp32" or not c.weight.is_contiguous() for c in convs):
         return None
-    if not c1.cached or not c2.cached or c2.bias is None or not gd.target_feat.is_contiguous():
+    x = own(c1, c2, cd) if gd.target_feat.is_contiguous() else None
+    if x is None:
         return None
-    _hip.require_gpu(gg.embedding, gg_edge_index, edge_weight, gd_edge_index)
-    x = _hip.f32_rows(gg.embedding.detach())
-    n, dev = x.shape[0], x.device
-    p1, p2 = c1._gcn_plan(gg_edge_index, n, edge_weight), c2._gcn_plan(gg_edge_index, n, edge_weight)
-    pd = cd._plan(gd_edge_index, lambda: _hip.GraphPlan.bipartite(gd_edge_index, n, gd.n_target, None))
-    out = torch.empty((gd.n_target, gd.target_dim + gd.target_feat_dim), dtype=torch.float32, device=dev)
+    _hip.require_gpu(x, gg_edge_index, edge_weight, gd_edge_index)
+    n = x.shape[0]
+    plans = (c1._gcn_plan(gg_edge_index, n, edge_weight), c2._gcn_plan(gg_edge_index, n, edge_weight),
+             cd._plan(gd_edge_index, lambda: _hip.GraphPlan.bipartite(gd_edge_index, n, gd.n_target, None)))
+    out = torch.empty((gd.n_target, gd.target_dim + gd.target_feat_dim), dtype=torch.float32, device=x.device)
+    return x, convs, plans, out
+
+
+def _gene_chain(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu):
+    """The chained launches of `gene_stack_to_external`, or None where they do not apply."""
+    def own(c1, c2, cd):                         # a 16 -> 16 last layer with a bias, both gene layers on kept plans
+        if (c2.in_channels, c2.out_channels) != (16, 16) or not c1.cached or not c2.cached or c2.bias is None:
+            return None
+        return _hip.f32_rows(gg.embedding.detach())
+    found = _gene_operands(gg, gd, gg_edge_index, edge_weight, gd_edge_index, own)
+    if found is None:
+        return None
+    x, (c1, c2, cd), (p1, p2, pd), out = found
+    n, dev, w0 = x.shape[0], x.device, x.shape[1]
 
     def run():
         genes = torch.empty((n, 64), dtype=torch.float32, device=dev)     # [embedding | h1 | A h1], internal
-        s0, s1, s2 = genes[:, :widths[0]], genes[:, widths[0]:widths[0] + 16], genes[:, 48:]
+        s0, s1, s2 = genes[:, :w0], genes[:, w0:w0 + 16], genes[:, 48:]
         if not (p1.chain_ok(p2, x, c1.weight, c1.bias, s1, s2) and pd.transform_ok(64, 16, genes)):
             raise _NotChained()                  # (before the first launch: nothing is recorded, nothing memoised)
         p1.aggregate_chain(p2, x, c1.weight, c1.bias, True, s1, side=(x, s0, 0))
@@ -503,24 +503,18 @@ def _gene_split(gg, gd, gg_edge_index, edge_weight, gd_edge_index, if_relu):
     columns (64 gene columns in all), default storage and arithmetic, `gd` the one-external `cat` form, and operands the
     library takes (gn_graph_split_applicable).  The launches of the two module calls, minus the first layer's side copy;
     the concat `homoGraph.forward` returns is not built, so nothing of it leaves this function."""
-    if torch.is_grad_enabled() or not isinstance(gg, homoGraph) or not isinstance(gd, interGraph):
+    def own(c1, c2, cd):                         # an fp32 embedding of 16, 32 or 48 columns where it lies, 16-byte rows throughout
+        emb = gg.embedding.detach()
+        if emb.shape[1] not in (16, 32, 48) or c1.out_channels % 4 or c2.out_channels % 4:
+            return None
+        if emb.dtype != torch.float32 or not emb.is_contiguous() or emb.data_ptr() % 16:
+            return None
+        return emb
+    found = _gene_operands(gg, gd, gg_edge_index, edge_weight, gd_edge_index, own)
+    if found is None:
         return None
-    if gg.multi_relational or not gg.start_graph or len(gg.conv_list) != 2 or not gd.if_one_external:
-        return None
-    c1, c2, cd = gg.conv_list[0], gg.conv_list[1], gd.conv
-    emb = gg.embedding.detach()
-    w0, w1, w2 = emb.shape[1], c1.out_channels, c2.out_channels
-    if w0 not in (16, 32, 48) or w1 % 4 or w2 % 4 or w0 + w1 + w2 != 64 or (cd.in_channels, cd.out_channels) != (64, 16):
-        return None
-    if any(c.table_storage != "fp32" or c.arithmetic != "fp32" or not c.weight.is_contiguous() for c in (c1, c2, cd)):
-        return None
-    if emb.dtype != torch.float32 or not emb.is_contiguous() or emb.data_ptr() % 16 or not gd.target_feat.is_contiguous():
-        return None
-    _hip.require_gpu(emb, gg_edge_index, edge_weight, gd_edge_index)
-    n, dev = emb.shape[0], emb.device
-    p1, p2 = c1._gcn_plan(gg_edge_index, n, edge_weight), c2._gcn_plan(gg_edge_index, n, edge_weight)
-    pd = cd._plan(gd_edge_index, lambda: _hip.GraphPlan.bipartite(gd_edge_index, n, gd.n_target, None))
-    out = torch.empty((gd.n_target, gd.target_dim + gd.target_feat_dim), dtype=torch.float32, device=dev)
+    emb, (c1, c2, cd), (p1, p2, pd), out = found
+    n, dev, w1, w2 = emb.shape[0], emb.device, c1.out_channels, c2.out_channels
 
     def run():
         layers = torch.empty((n, w1 + w2), dtype=torch.float32, device=dev)      # [h1 | h2], internal

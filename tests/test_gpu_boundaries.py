@@ -45,7 +45,8 @@ Guard by guard (csrc line numbers as of ABI 159; "formula": the size is found by
   host_layout.hpp:1414,1436, rel_grad.hip:342  n <= 65534                    test_relational_layer_at_the_16_bit_node_limit[65534|65535|65536]
   rel_grad.hip:388         (n + 1) * out * 4 + ... <= 160 KB (formula)       test_relational_weight_gradient_at_the_lds_limit
   rel_grad.hip:399         (n + 1) * ld_x < 2^31                             left out: memory
-  gcn_blocked.hip:382,387  N <= 65534; (N + 1) * 4 <= 160 KB (formula)       test_gcn_gather_at_the_lds_limit (bisected; 65534 is unreachable,
+  gcn_blocked.hip gn_graph_plan_build_blocked  N <= 65534; (N + 1) * 4 <= 160 KB (formula)
+                                                                            test_gcn_gather_at_the_lds_limit (bisected; 65534 is unreachable,
                                                                             the LDS fit binds first), test_gcn_layer_at_the_16_bit_node_limit
   rgcn_fast.hip:671-673    N <= 32767, geometry(N).tiles > 0 (formula)       test_relational_layer_at_the_lds_accumulator_limit (bisected; 32767
                                                                             is unreachable, the geometry binds first); R * tiles < 2^20: left out
@@ -53,7 +54,8 @@ Guard by guard (csrc line numbers as of ABI 159; "formula": the size is found by
   rgcn_pair.hip:776-778    up to 768 nodes, a formula of the widths          test_relational_layer_at_the_destination_major_limit (bisected)
   rgcn.hip:179-181         relation slabs of 32768                           test_relational_table_path_relation_slabs[32768|32769]
   plan.hip:459             ELL rows <= 2^20                                  test_short_row_gather_at_2_to_the_20_rows
-  aggregate.cuh:828        LDS-table short-row gather, rows >= 65536         test_plain_sum_at_65536_rows[65535|65536] (no query: parity only)
+  gather_route.hpp gather_route (lds_table rule, kLdsTableRows)  LDS-table short-row gather, rows >= 65536
+                                                                            test_plain_sum_at_65536_rows[65535|65536] (no query: parity only)
   dense_route.hpp:66       batch <= 65535                                    test_dense_batch_limit
   adam.hip:35,94           64 tensors per launch; alignment                  test_adam_tensor_counts_and_update
   class_metrics.hip:23     1024 classes                                      C = 1025 is refused in tests/test_class_metrics_host.py already
@@ -551,7 +553,7 @@ def run_gcn_layer(dev, n, fin, fout, seed, e=120000):
 
 def test_gcn_gather_at_the_lds_limit(gpu, monkeypatch):
     """The LDS-staged gather keeps a column group of the table, N rows and a zero row, in 160 KB: the last N that gets the
-    encoding is found by bisecting plan builds (the N <= 65534 of gcn_blocked.hip:382 lies behind it); it runs on the staged
+    encoding is found by bisecting plan builds (the N <= 65534 of gcn_blocked.hip, gn_graph_plan_build_blocked, lies behind it); it runs on the staged
     kernels, N + 1 on the wave-per-row ones."""
     monkeypatch.setenv("GN_BLOCKED_ANY", "1")
     ring = torch.tensor([[0, 1, 2, 3, 4, 5], [1, 2, 3, 4, 5, 0]], device=gpu)
@@ -579,7 +581,7 @@ def test_gcn_layer_at_the_16_bit_node_limit(gpu, n, monkeypatch):
 
 @pytest.mark.parametrize("rows", [65535, 65536])
 def test_plain_sum_at_65536_rows(gpu, rows):
-    """A plain sum over many short rows gathers a small table from LDS from 65536 rows on (aggregate.cuh:828; row
+    """A plain sum over many short rows gathers a small table from LDS from 65536 rows on (gather_route.hpp, the lds_table rule of gather_route; row
     table_rows is its zero row).  The library has no query for it: both sizes are held to the float64 sums."""
     n_src, f = 2000, 16
     gen = torch.Generator().manual_seed(rows)
