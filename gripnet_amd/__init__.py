@@ -11,8 +11,9 @@ need a GPU, running a layer does.
 from .layers import myGCN, myRGCN, homoGraph, interGraph, gene_stack_to_external, gene_stack_path
 from .decoder import multiRelaInnerProductDecoder, multiClassInnerProductDecoder
 from .kge import KGEModel
+from .gat import GATConv
 from . import utils, synth, optim
 
 __all__ = ["myGCN", "myRGCN", "homoGraph", "interGraph", "multiRelaInnerProductDecoder",
-           "multiClassInnerProductDecoder", "KGEModel", "utils", "synth", "optim"]
+           "multiClassInnerProductDecoder", "KGEModel", "GATConv", "utils", "synth", "optim"]
 __version__ = "0.1.0"

@@ -28,7 +28,7 @@ RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}         
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 166                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 167                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -110,6 +110,12 @@ SIGNATURES = {
     "gn_kge_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),
     "gn_kge_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
+    "gn_gat_logits_f32": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "gn_gat_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, C.c_float, _p, _int, _int, _p, _i64, _p, _p, _p, _p]),
+    "gn_gat_backward_dst_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, C.c_float, _p, _i64, _int, _p, _p, _p, _p]),
+    "gn_gat_backward_src_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, C.c_float, _p, _i64, _int, _p, _p, _p, _i64, _p, _p]),
+    "gn_gat_att_grad_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "gn_gat_att_grad_f32": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_rank_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "gn_kge_rank_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_topk_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
@@ -892,6 +898,14 @@ class GraphPlan(Handle):
               ptr(out), ld(out), _ref(sc), stream_ptr(xw.device), tag="gn_graph_aggregate_bf16[{}]".format(self.kind))
         return out
 
+    def build_transpose(self):
+        """Add the source-major CSR (once; synchronises the stream): what a caller whose backward must not wait does up front."""
+        if not getattr(self, "_has_t", False):
+            with torch.cuda.device(self.device):
+                check(load().gn_graph_plan_build_transpose(self._h, stream_ptr(self.device)))
+            self._has_t = True
+        return self
+
     def aggregate_t(self, g: torch.Tensor, out: torch.Tensor):
         """out[s] = sum over edges leaving s of coef * g[dst]: gradient of `aggregate` w.r.t. its table."""
         if not getattr(self, "_has_t", False):
@@ -1389,6 +1403,44 @@ def kge_backward(model, ent, rel, sample, et, divisor, grad_out, raw, d_ent, d_r
           float(divisor), ptr(grad_out), ptr(raw), ptr(d_ent), ld(d_ent), ptr(d_rel), ld(d_rel),
           GN_DM_TYPES_SORTED if types_sorted else 0, ptr(ws), need, stream_ptr(ent.device))
     return d_ent, d_rel
+
+
+GAT_MAX_ROW = 128                                                              # GN_GAT_MAX_ROW: floats of a row (heads x channels)
+
+
+def gat_forward(plan, h, att, heads, negative_slope, bias, concat, relu, out, o_save=None):
+    """gn_gat_logits_f32 + gn_gat_forward_f32: the attention layer's output into `out` from h = x W [N, heads * C] (contiguous)
+    over `plan` (GraphPlan.gcn of the edge list: its working list is the layer's).  Returns (a_dst, a_src, m, rinv), [N, heads]
+    each, what the backward recomputes alpha from; `o_save` [N, heads * C] receives the output before mean, bias and ReLU."""
+    n, f = h.shape
+    c = f // heads
+    dev = h.device
+    a_dst, a_src, m, rinv = (torch.empty((n, heads), dtype=torch.float32, device=dev) for _ in range(4))
+    _call("gn_gat_logits_f32", ptr(h), ld(h), n, heads, c, ptr(att), ptr(a_dst), ptr(a_src), stream_ptr(dev))
+    _call("gn_gat_forward_f32", plan._h, ptr(h), ld(h), heads, c, ptr(a_dst), ptr(a_src), float(negative_slope), ptr(bias),
+          int(bool(concat)), int(bool(relu)), ptr(out), ld(out), ptr(o_save), ptr(m), ptr(rinv), stream_ptr(dev))
+    return a_dst, a_src, m, rinv
+
+
+def gat_backward(plan, h, att, heads, negative_slope, concat, g, o, a_dst, a_src, m, rinv):
+    """(dh [N, heads * C], d_att like `att`) from g = dL/d(output before bias and ReLU): [N, heads * C], or [N, C] for the head
+    mean.  gn_gat_backward_dst_f32, gn_gat_backward_src_f32 (the plan's source-major CSR must exist: `build_transpose`) and
+    gn_gat_att_grad_f32; every sum in a fixed order."""
+    n, f = h.shape
+    c = f // heads
+    dev = h.device
+    pack = torch.empty((n, heads, 4), dtype=torch.float32, device=dev)
+    da_dst, da_src = torch.empty((n, heads), dtype=torch.float32, device=dev), torch.empty((n, heads), dtype=torch.float32, device=dev)
+    dh, d_att = torch.empty_like(h), torch.empty_like(att)
+    slope, cc = float(negative_slope), int(bool(concat))
+    _call("gn_gat_backward_dst_f32", plan._h, ptr(h), ld(h), heads, c, ptr(a_dst), ptr(a_src), ptr(m), ptr(rinv), slope, ptr(g), ld(g),
+          cc, ptr(o), ptr(pack), ptr(da_dst), stream_ptr(dev))
+    _call("gn_gat_backward_src_f32", plan._h, ptr(h), ld(h), heads, c, ptr(a_src), ptr(pack), slope, ptr(g), ld(g), cc, ptr(da_dst),
+          ptr(att), ptr(dh), ld(dh), ptr(da_src), stream_ptr(dev))
+    need = int(load().gn_gat_att_grad_workspace_bytes(n, heads, c))
+    ws = torch.empty((max(need, 4),), dtype=torch.uint8, device=dev)
+    _call("gn_gat_att_grad_f32", ptr(h), ld(h), n, heads, c, ptr(da_dst), ptr(da_src), ptr(d_att), ptr(ws), need, stream_ptr(dev))
+    return dh, d_att
 
 
 def link_loss_forward(pos, neg, eps):

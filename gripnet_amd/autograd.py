@@ -346,6 +346,48 @@ class KgeScoreFn(torch.autograd.Function):
         return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None
 
 
+class GatConvFn(torch.autograd.Function):
+    """``act(softmax-weighted sum over the in-edges of (x W) + b)`` per head (GATConv.forward of torch_geometric 1.4 / 1.5 as
+    baselines/NC_baselines/GAT.py:66-67 calls it, with the ReLU that follows).  The forward's launches are the same with and
+    without gradients: the product, the logits, the gather.  Kept for the backward: x, h = x W, the logits' two halves, the
+    maximum and 1 / denominator of every (node, head) and the output before mean and bias - alpha is recomputed from them."""
+
+    @staticmethod
+    def forward(ctx, x, weight, att, bias, plan, heads, concat, negative_slope, relu):
+        ctx.set_materialize_grads(False)
+        x = _hip.f32_rows(x.detach())
+        w, a = weight.detach(), att.detach().contiguous()
+        b = None if bias is None else bias.detach()
+        n, f = x.shape[0], w.shape[1]
+        h = torch.empty((n, f), dtype=torch.float32, device=x.device)
+        _hip.gemm(x, w, h)
+        out = torch.empty((n, f if concat else f // heads), dtype=torch.float32, device=x.device)
+        o = torch.empty_like(h) if any(ctx.needs_input_grad[:4]) else None
+        a_dst, a_src, m, rinv = _hip.gat_forward(plan, h, a, heads, negative_slope, b, concat, relu, out, o)
+        ctx.plan, ctx.heads, ctx.concat, ctx.slope, ctx.relu, ctx.has_bias = plan, heads, bool(concat), negative_slope, bool(relu), bias is not None
+        ctx.save_for_backward(x, w, a, h, o, a_dst, a_src, m, rinv, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, a, h, o, a_dst, a_src, m, rinv, out = ctx.saved_tensors
+        if g is None:
+            return (None,) * 9
+        need_db = ctx.has_bias and ctx.needs_input_grad[3]
+        if ctx.relu or need_db or g.dtype != torch.float32 or g.stride(1) != 1:
+            gm, _, db = _hip.grad_prologue(g, out if ctx.relu else None, None, True, need_db)   # ReLU mask by the saved output, column sums
+        else:
+            gm, db = _hip.f32_rows(g), None
+        dh, d_att = _hip.gat_backward(ctx.plan.build_transpose(), h, a, ctx.heads, ctx.slope, ctx.concat, gm, o, a_dst, a_src, m, rinv)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            _hip.gemm(dh, w, dx, b_transposed=True)                # dh W^T, W as it is stored
+        if ctx.needs_input_grad[1]:
+            dw = _hip.xtg(x, dh)
+        return dx, dw, (d_att if ctx.needs_input_grad[2] else None), db, None, None, None, None, None
+
+
 class LinkLossFn(torch.autograd.Function):
     """``-mean(log(pos + eps)) - mean(log(1 - neg + eps))`` (the loss of GripNet-pose.py:140-142) in one launch forward and
     one backward, instead of the ~20 element-wise and reduction launches of the torch expression."""

@@ -191,3 +191,23 @@ def make_nc(name: str = "tiny", seed: int = 11, **override) -> Data:
         aa_edge_weight=torch.ones(aa.shape[1]),
         a_label=labels,
     )
+
+
+def make_nc_homogeneous(name: str = "tiny", seed: int = 11, split_seed: int = 13, train_ratio: float = 0.9, **override) -> Data:
+    """The node-classification supergraph of `make_nc` as the reference's stock baselines read it
+    (baselines/NC_baselines/GAT.py:35-52: `edge_index`, `num_classes`, `train_idx` / `train_y`, `test_idx` / `test_y`): ONE node
+    set - the labelled nodes first, then the two feature supervertices - and ONE bidirectional `edge_index`: the three
+    internal edge lists as they are (already bidirectional), the two bipartite lists in both directions.  The labelled nodes
+    are split once, seeded, `train_ratio` of them for training."""
+    base = make_nc(name, seed=seed, **override)
+    n_a, n_p, n_q = int(base.n_a_node), int(base.n_p_node), int(base.n_q_node)
+    off_p, off_q = n_a, n_a + n_p
+    pa = torch.stack([base.pa_edge_idx[0] + off_p, base.pa_edge_idx[1]])
+    qa = torch.stack([base.qa_edge_idx[0] + off_q, base.qa_edge_idx[1]])
+    edge_index = torch.cat([base.aa_edge_idx, base.pp_edge_idx + off_p, base.qq_edge_idx + off_q,
+                            to_bidirection(pa), to_bidirection(qa)], dim=1).long().contiguous()
+    order = torch.randperm(n_a, generator=torch.Generator().manual_seed(split_seed))
+    n_train = max(1, min(n_a - 1, int(round(train_ratio * n_a))))
+    train_idx, test_idx = order[:n_train].sort().values, order[n_train:].sort().values
+    return Data(name="gat-" + name, num_nodes=n_a + n_p + n_q, num_classes=int(base.n_a_type), edge_index=edge_index,
+                train_idx=train_idx, train_y=base.a_label[train_idx], test_idx=test_idx, test_y=base.a_label[test_idx])

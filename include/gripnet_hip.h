@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 166 /* 0.1.60 */
+#define GN_VERSION 167 /* 0.1.61 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -629,6 +629,50 @@ GN_API gn_status gn_kge_backward_f32(int model, const float* ent, int64_t ld_ent
                               const int64_t* tail, const int64_t* edge_type, int64_t num_edges, float phase_divisor,
                               const float* grad_out, const float* raw_scores /* nullable */, float* d_ent, int64_t ld_dent,
                               float* d_rel, int64_t ld_drel, int flags, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Graph attention: GATConv of torch_geometric 1.4 / 1.5 as baselines/NC_baselines/GAT.py uses it (single `weight`, single
+ * `att`).  The graph is a plan of gn_gcn_plan_create: it is the layer's working list already - input loops dropped, one
+ * loop per node, duplicate edges kept, in-edges of a node in input order - and an id outside [0, N) is refused there as
+ * for myGCN (GN_ERR_INDEX_RANGE); its coefficients are not read.  With h = x W [N, H * C] (gn_gemm_f32), att [H, 2 C]
+ * (a head's target half, then its source half) and l_e = leaky_relu(a_dst[i] + a_src[j]) for an edge j -> i:
+ *   gn_gat_logits_f32        a_dst[i, h] = sum_c h[i, h, c] att[h, c],  a_src[i, h] = sum_c h[i, h, c] att[h, C + c]
+ *   gn_gat_forward_f32       m[i, h] = max_e l_e,  s = sum_e exp(l_e - m),  o[i, h, :] = (sum_e exp(l_e - m) h[j_e, h, :]) / s,
+ *                            out = act(o as [N, H * C] + bias)  (concat)  or  act(mean_h o + bias) [N, C];  o_save (nullable,
+ *                            [N, H * C] contiguous) receives o, rinv = 1 / s.  (PyG's 1e-16 in the denominator is below half
+ *                            a unit of s >= 1 and is left out.)  exp is 2^(x log2 e) on the hardware instruction.
+ *   gn_gat_backward_dst_f32  from g = dL/d(out before bias and act) ([N, H * C], or [N, C] for the head mean, whose 1 / H the
+ *                            kernel applies): D[i, h] = g[i, h, :] . o[i, h, :],  dz_e = alpha_e (g[i, h, :] . h[j, h, :] - D)
+ *                            (z_e > 0 ? 1 : slope),  da_dst[i, h] = sum_{e into i} dz_e;  pack [N, H, 4] (16-byte aligned)
+ *                            receives (a_dst, m, rinv, D) for the next pass.
+ *   gn_gat_backward_src_f32  over the plan's source-major CSR (gn_graph_plan_build_transpose first):  da_src[j, h] =
+ *                            sum_{e out of j} dz_e,  dh[j, h, :] = sum_{e out of j} alpha_e g[i_e, h, :] + da_dst[j, h] att[h, :C]
+ *                            + da_src[j, h] att[h, C:].
+ *   gn_gat_att_grad_f32      d_att[h, :C] = sum_i da_dst[i, h] h[i, h, :],  d_att[h, C:] likewise with da_src: blocks of 32
+ *                            nodes, 64 blocks each, then what is left in order.  Scratch: gn_gat_att_grad_workspace_bytes bytes, 4-byte aligned.
+ * alpha_e is recomputed from (a_dst, a_src, m, rinv): nothing of size [E', H] is kept.  No float atomics, every sum in a
+ * fixed order: two calls give the same bits.  A node of any degree is one wave's (its edges in turns of the wave's lane
+ * groups).  GN_ERR_INVALID_ARG: H * C above GN_GAT_MAX_ROW, a plan of another kind, a null operand, a leading dimension
+ * below the row length. */
+#define GN_GAT_MAX_ROW 128
+GN_API gn_status gn_gat_logits_f32(const float* h, int64_t ld_h, int64_t num_nodes, int64_t heads, int64_t channels,
+                            const float* att, float* a_dst, float* a_src, void* stream);
+GN_API gn_status gn_gat_forward_f32(const gn_graph_plan* plan, const float* h, int64_t ld_h, int64_t heads, int64_t channels,
+                             const float* a_dst, const float* a_src, float negative_slope, const float* bias /* nullable */,
+                             int concat, int relu, float* out, int64_t ld_out, float* o_save /* nullable */, float* m,
+                             float* rinv, void* stream);
+GN_API gn_status gn_gat_backward_dst_f32(const gn_graph_plan* plan, const float* h, int64_t ld_h, int64_t heads, int64_t channels,
+                                  const float* a_dst, const float* a_src, const float* m, const float* rinv,
+                                  float negative_slope, const float* g, int64_t ld_g, int concat, const float* o, float* pack,
+                                  float* da_dst, void* stream);
+GN_API gn_status gn_gat_backward_src_f32(const gn_graph_plan* plan, const float* h, int64_t ld_h, int64_t heads, int64_t channels,
+                                  const float* a_src, const float* pack, float negative_slope, const float* g, int64_t ld_g,
+                                  int concat, const float* da_dst, const float* att, float* dh, int64_t ld_dh, float* da_src,
+                                  void* stream);
+GN_API size_t gn_gat_att_grad_workspace_bytes(int64_t num_nodes, int64_t heads, int64_t channels);
+GN_API gn_status gn_gat_att_grad_f32(const float* h, int64_t ld_h, int64_t num_nodes, int64_t heads, int64_t channels,
+                              const float* da_dst, const float* da_src, float* d_att, void* workspace, size_t workspace_bytes,
                               void* stream);
 
 /* ---------------------------------------------------------------------------------------
