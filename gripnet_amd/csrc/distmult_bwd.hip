@@ -9,9 +9,10 @@
 // (key, a, b) = (u, v, r), (v, u, r) and (r, u, v).  Scatter with float atomics is the wrong tool here:
 // LDS float atomics retire at about one lane per three cycles per CU (measured: 1.7 ms for 2 M edges),
 // and the targets are hit thousands of times each.  Instead every pass sorts 12-byte records
-// (a, b, g) by key (rocPRIM radix sort, stable), and one workgroup per output row streams its records
-// with coalesced loads, gathers the two factor rows from L2, sums in registers and folds the 16 edge
-// lanes in a fixed order: no atomics, bitwise reproducible gradients.  dz is the sum of two passes.
+// (a, b, g) by key (rocPRIM radix sort, stable), and the chunked segmented reduction of seg_reduce.cuh (shared
+// with the KGE scorers' backward, kge.hip) streams the sorted records with coalesced loads, gathers the two
+// factor rows from L2, sums in registers and folds the record lanes in a fixed order: no atomics, bitwise
+// reproducible gradients.  dz is the sum of two passes.
 //
 // That general path gathers both factor rows of every record from L2 (2.5 GB per call at 2 M edges x 80
 // features) behind three radix sorts.  When the tables are small - the drug supervertex: a few hundred nodes,
@@ -29,7 +30,7 @@
 #include "common.h"
 #include "layout_decoder_bwd.hpp"
 #include "plan_device.cuh"
-#include "seg_sort.cuh"
+#include "seg_reduce.cuh"
 
 #include <unordered_map>
 #include <vector>
@@ -117,101 +118,28 @@ __global__ void k_make_recs(int mode, const int64_t* __restrict__ u, const int64
     }
 }
 
-using gn::k_key_offsets;                      // rowptr[i] = first position whose sorted key is >= i (seg_sort.cuh)
-
-// Chunked segmented reduction.  The sorted record array is cut into chunks of kChunkRecs records, one
-// workgroup each (hub rows of 10^5 records and rows of a few records cost the same per record).  A
-// chunk holds a run of rows; for every row the workgroup sums  g * A[a, c..] * B[b, c..]  over the row's
-// records inside the chunk: 256 threads = (256 / LPE) records in flight x LPE lanes of 16 bytes, folded
-// in a fixed order.  A row that lies wholly inside the chunk is final and goes to `out`; the chunk's
-// first / last row may continue in a neighbour chunk and goes to partial slot 2b / 2b+1 (columns
-// [c0, c0+64)), which k_seg_combine adds up in chunk order: bitwise reproducible.
-constexpr int kChunkRecs = gn::kSegChunkRecs;
-
-template <int LPE>
-__global__ __launch_bounds__(256) void k_seg_reduce(const int32_t* __restrict__ rowptr, const uint32_t* __restrict__ keys,
-                                                    const Rec* __restrict__ recs, int64_t n_recs, int rows,
-                                                    const float* __restrict__ A, int64_t ld_a,
-                                                    const float* __restrict__ B, int64_t ld_b, float* __restrict__ out,
-                                                    int64_t ld_out, float* __restrict__ partial, int c0, int width,
-                                                    int accumulate) {
-    constexpr int S = 256 / LPE;                       // records per step
-    __shared__ f32x4 part[S][LPE];
-    const int j = threadIdx.x % LPE, slot = threadIdx.x / LPE;
-    const int lo = blockIdx.x * kChunkRecs;
-    const int hi = (int)min((int64_t)lo + kChunkRecs, n_recs);
-    const bool col_ok = 4 * j < width;                 // width is a multiple of 4
-    const int col = c0 + 4 * j;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    if (threadIdx.x < 2 * 16) {                        // both partial slots start at zero (64 columns each)
-        reinterpret_cast<f32x4*>(partial)[(size_t)blockIdx.x * 32 + threadIdx.x] = zero4;
-    }
-    const int r_first = (int)min(keys[lo], (uint32_t)rows), r_last = (int)min(keys[hi - 1], (uint32_t)rows);
-    for (int row = r_first; row <= r_last && row < rows; ++row) {
-        const int rb = rowptr[row], re = rowptr[row + 1];
-        const int begin = max(lo, rb), end = min(hi, re);
-        if (begin >= end) continue;                    // workgroup-uniform
-        f32x4 acc = zero4;
-        for (int base = begin; base < end; base += 2 * S) {     // two records per thread and trip: four gathers in flight
-            const int i0 = base + slot, i1 = base + S + slot;
-            Rec r0 = {0, 0, 0.f}, r1 = {0, 0, 0.f};
-            if (i0 < end) r0 = recs[i0];
-            if (i1 < end) r1 = recs[i1];
-            if (col_ok) {
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(A + (int64_t)r0.a * ld_a + col);
-                const f32x4 b0 = *reinterpret_cast<const f32x4*>(B + (int64_t)r0.b * ld_b + col);
-                const f32x4 a1 = *reinterpret_cast<const f32x4*>(A + (int64_t)r1.a * ld_a + col);
-                const f32x4 b1 = *reinterpret_cast<const f32x4*>(B + (int64_t)r1.b * ld_b + col);
-                acc += i0 < end ? r0.g * (a0 * b0) : zero4;   // loads past the end read row 0 and are dropped
-                acc += i1 < end ? r1.g * (a1 * b1) : zero4;
-            }
-        }
-        __syncthreads();                               // previous row's fold is done with `part`
-        part[slot][j] = acc;
-        __syncthreads();
-        if (slot == 0 && col_ok) {
-            f32x4 s = part[0][j];
+// The contribution of a record to its key's row, columns [4 unit, 4 unit + 4):  A[a, :] * B[b, :], which seg_reduce.cuh
+// accumulates as acc + g * (a * b) - three roundings, none fused, as this backward always has.
+struct PairTerm {
+    using Rec = ::Rec;
+    static constexpr int P = 1;
+    static constexpr bool kFused = false;
+    const float* A; int64_t ld_a;
+    const float* B; int64_t ld_b;
+    static __device__ __forceinline__ bool skip(const Rec&) { return false; }    // (a bad id's record is sorted behind the last row)
+    template <int VEC>
+    __device__ __forceinline__ void terms(const Rec& r, int unit, float (&d)[1][VEC]) const {
+#pragma clang fp contract(off)
+        static_assert(VEC == 4, "float4 rows; the rest goes to k_seg_reduce_scalar");
+        const f32x4 a = *reinterpret_cast<const f32x4*>(A + (int64_t)r.a * ld_a + 4 * unit);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(B + (int64_t)r.b * ld_b + 4 * unit);
 #pragma unroll
-            for (int k = 1; k < S; ++k) s += part[k][j];   // fixed order
-            if (rb >= lo && re <= hi) {                // the whole row is here: final
-                float* o = out + (int64_t)row * ld_out + col;
-                if (accumulate) s += *reinterpret_cast<const f32x4*>(o);
-                *reinterpret_cast<f32x4*>(o) = s;
-            } else {                                   // shared with a neighbour chunk
-                const int which = (row == r_first) ? 0 : 1;
-                reinterpret_cast<f32x4*>(partial)[((size_t)blockIdx.x * 2 + which) * 16 + j] = s;
-            }
-        }
+        for (int v = 0; v < 4; ++v) d[0][v] = a[v] * b[v];
     }
-}
+};
 
-// Rows that straddle chunks: out[row, c0 + c] (+)= sum of the chunks' partials, in chunk order.
-__global__ void k_seg_combine(const int32_t* __restrict__ rowptr, const uint32_t* __restrict__ keys, int64_t n_recs,
-                              int rows, const float* __restrict__ partial, float* __restrict__ out, int64_t ld_out,
-                              int c0, int width, int accumulate) {
-    const int row = blockIdx.x, c = threadIdx.x;
-    if (c >= width) return;
-    const int rb = rowptr[row], re = rowptr[row + 1];
-    float* o = out + (int64_t)row * ld_out + c0 + c;
-    if (rb >= re) {                                    // no record at all
-        if (!accumulate) *o = 0.f;
-        return;
-    }
-    const int cb = rb / kChunkRecs, ce = (re - 1) / kChunkRecs;
-    if (cb == ce && rb >= cb * kChunkRecs && re <= min((int64_t)(cb + 1) * kChunkRecs, n_recs)) {
-        // candidate for "whole row inside one chunk": final value already written by k_seg_reduce
-        return;
-    }
-    float s = 0.f;
-    for (int b = cb; b <= ce; ++b) {
-        const int first = (int)min(keys[(size_t)b * kChunkRecs], (uint32_t)rows);
-        const int which = (row == first) ? 0 : 1;
-        s += partial[((size_t)b * 2 + which) * 64 + c];
-    }
-    *o = accumulate ? *o + s : s;
-}
-
-// scalar-column variant for shapes the float4 kernel cannot take (features % 4 != 0 or unaligned rows)
+// scalar-column variant for shapes the float4 kernel cannot take (features % 4 != 0 or unaligned rows): a row per
+// workgroup, a serial sum per column - not the engine's VEC = 1 form, whose summation order is another
 __global__ __launch_bounds__(256) void k_seg_reduce_scalar(const int32_t* __restrict__ rowptr, const Rec* __restrict__ recs,
                                                            const float* __restrict__ A, int64_t ld_a,
                                                            const float* __restrict__ B, int64_t ld_b,
@@ -712,25 +640,9 @@ __global__ __launch_bounds__(256) void k_seg_lds_combine(CombineSet first, int f
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-// The general path's scratch, and the LDS path's over the same bytes (a call that takes the LDS path for dD only runs its
-// general passes after it).
-struct WsLayout { size_t keys, keys_sorted, recs, recs_sorted, rowptr, partial, sort_tmp, total; };
-
-WsLayout ws_layout(int64_t e, int64_t max_rows) {
-    WsLayout l;
-    size_t sort_bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const Rec*)nullptr,
-                                    (Rec*)nullptr, (size_t)e, 0, 32, (hipStream_t)0);
-    l.keys = 0;
-    l.keys_sorted = l.keys + align_up(e * sizeof(uint32_t));
-    l.recs = l.keys_sorted + align_up(e * sizeof(uint32_t));
-    l.recs_sorted = l.recs + align_up(e * sizeof(Rec));
-    l.rowptr = l.recs_sorted + align_up(e * sizeof(Rec));
-    l.partial = l.rowptr + align_up((max_rows + 2) * sizeof(int32_t));
-    l.sort_tmp = l.partial + align_up((size_t)gn::ceil_div(e, kChunkRecs) * 2 * 64 * sizeof(float));
-    l.total = l.sort_tmp + align_up(sort_bytes);
-    return l;
-}
+// The general path's scratch (seg_reduce.cuh: one output part, no tail), and the LDS path's over the same bytes (a call that
+// takes the LDS path for dD only runs its general passes after it).
+gn::SegLayout ws_layout(int64_t e, int64_t max_rows) { return gn::seg_layout<Rec>(e, max_rows, 1, 0); }
 
 // A table block of 16 columns is 64 bytes per row; the LDS path keeps z and D (node-major reduction) or z alone
 // (relation-major) in LDS.  The counting sort takes every node count that fits, and the 16-bit ids of the packed record hold
@@ -958,13 +870,11 @@ gn_status dd_lds(const Call& c, const LdsWs& w, const Route& rt, const int32_t* 
     if (rt.types_sorted && type_offsets) {
         rowptr = type_offsets;                             // the caller keeps them with its static edge_type
     } else if (rt.types_sorted) {
-        k_key_offsets<int64_t><<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(c.edges.et, e, (int)r, w.rowptr);
-        GN_LAUNCH_CHECK();
+        GN_OK_OR_RETURN(gn::first_at_least(c.edges.et, e, r, w.rowptr, st));
     } else {
         size_t sort_bytes = w.sort_tmp_bytes;
         GN_HIP(rocprim::radix_sort_pairs(w.sort_tmp, sort_bytes, w.keys, w.keys_sorted, w.recs, w.recs_sorted, (size_t)e, 0, bits_for(r + 1), st));
-        k_key_offsets<uint32_t><<<(int)gn::ceil_div(r + 1, 256), 256, 0, st>>>(w.keys_sorted, e, (int)r, w.rowptr);
-        GN_LAUNCH_CHECK();
+        GN_OK_OR_RETURN(gn::first_at_least(w.keys_sorted, e, r, w.rowptr, st));
         recs = w.recs_sorted;
     }
     int32_t* taskptr = w.taskptr;
@@ -977,52 +887,33 @@ gn_status dd_lds(const Call& c, const LdsWs& w, const Route& rt, const int32_t* 
     return launch_seg_lds(recs, rowptr, 1, taskptr, tasks, r, c.z, c.ld_z, c.n, c.z, c.ld_z, c.n, c.f, w.partial_dd, c.dd, c.ld_dd, st, rt.listed, defer);
 }
 
-// One pass of the general path: records of the mode (k_make_recs), radix sort, row offsets, segmented reduction from L2.
-gn_status general_pass(int mode, const Call& c, bool vec, char* ws, const WsLayout& l) {
-    uint32_t* keys = reinterpret_cast<uint32_t*>(ws + l.keys);
-    uint32_t* keys_sorted = reinterpret_cast<uint32_t*>(ws + l.keys_sorted);
-    Rec* recs = reinterpret_cast<Rec*>(ws + l.recs);
-    Rec* recs_sorted = reinterpret_cast<Rec*>(ws + l.recs_sorted);
-    int32_t* rowptr = reinterpret_cast<int32_t*>(ws + l.rowptr);
-    float* partial = reinterpret_cast<float*>(ws + l.partial);
-    size_t sort_bytes = l.total - l.sort_tmp;
-    const int64_t e = c.e, f = c.f;
+// One pass of the general path: records of the mode (k_make_recs), then seg_reduce.cuh's sort, row offsets and reduction from L2.
+// The column-block rule, kept from the parent (the bits depend on it): blocks of 64 columns; 16 lanes of four columns per
+// record for a block wider than 32 columns, 8 for one wider than 16, 4 otherwise.
+gn_status general_pass(int mode, const Call& c, bool vec, const gn::SegWs<Rec>& w) {
+    const int64_t e = c.e;
     hipStream_t st = c.st;
-    const unsigned chunks = (unsigned)gn::ceil_div(e, kChunkRecs);
     const int64_t rows = mode == 2 ? c.r : c.n;
-    const float* A = c.z;                                // a is always a node id
-    const int64_t ld_a = c.ld_z;
-    const float* B = mode == 2 ? c.z : c.d;              // b: relation row of D, or the other endpoint's z row
-    const int64_t ld_b = mode == 2 ? c.ld_z : c.ld_d;
-    float* out = mode == 2 ? c.dd : c.dz;
-    const int64_t ld_out = mode == 2 ? c.ld_dd : c.ld_dz;
-    const int accumulate = mode == 1;                    // dz = u-side pass, then + v-side pass
-    k_make_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(mode, c.edges.u, c.edges.v, c.edges.et, c.grad, e, c.n, c.r, (uint32_t)rows, keys, recs);
-    GN_LAUNCH_CHECK();
-    GN_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, sort_bytes, keys, keys_sorted, recs, recs_sorted, (size_t)e, 0, bits_for(rows + 1), st));
-    k_key_offsets<uint32_t><<<(int)gn::ceil_div(rows + 1, 256), 256, 0, st>>>(keys_sorted, e, (int)rows, rowptr);
+    // a is always a node id; b: relation row of D, or the other endpoint's z row
+    const PairTerm term = {c.z, c.ld_z, mode == 2 ? c.z : c.d, mode == 2 ? c.ld_z : c.ld_d};
+    const gn::SegOut o = {mode == 2 ? c.dd : c.dz, mode == 2 ? c.ld_dd : c.ld_dz, 0, 1, mode == 1};   // dz = u-side pass, then + v-side pass
+    k_make_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(mode, c.edges.u, c.edges.v, c.edges.et, c.grad, e, c.n, c.r, (uint32_t)rows, w.keys, w.recs);
     GN_LAUNCH_CHECK();
     if (!vec) {
-        k_seg_reduce_scalar<<<(unsigned)rows, 256, 0, st>>>(rowptr, recs_sorted, A, ld_a, B, ld_b, out, ld_out, (int)f, accumulate);
+        const Rec* sorted;
+        GN_OK_OR_RETURN(gn::seg_sort(w, e, rows, nullptr, &sorted, st));
+        k_seg_reduce_scalar<<<(unsigned)rows, 256, 0, st>>>(w.rowptr, sorted, term.A, term.ld_a, term.B, term.ld_b, o.out, o.ld_out, (int)c.f, o.accumulate);
         GN_LAUNCH_CHECK();
         return GN_OK;
     }
-    for (int c0 = 0; c0 < f; c0 += 64) {
-        const int width = (int)std::min<int64_t>(64, f - c0);
-        if (width > 32)
-            k_seg_reduce<16><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b, out, ld_out, partial, c0, width,
-                                                     accumulate);
-        else if (width > 16)
-            k_seg_reduce<8><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b, out, ld_out, partial, c0, width,
-                                                    accumulate);
-        else
-            k_seg_reduce<4><<<chunks, 256, 0, st>>>(rowptr, keys_sorted, recs_sorted, e, (int)rows, A, ld_a, B, ld_b, out, ld_out, partial, c0, width,
-                                                    accumulate);
-        GN_LAUNCH_CHECK();
-        k_seg_combine<<<(unsigned)rows, 64, 0, st>>>(rowptr, keys_sorted, e, (int)rows, partial, out, ld_out, c0, width, accumulate);
-        GN_LAUNCH_CHECK();
-    }
-    return GN_OK;
+    return gn::seg_pass(w, e, rows, nullptr, o, (int)(c.f / 4), 4, 16,
+                        [&](const gn::SegFrame<Rec>& f, int units, unsigned chunks) {
+                            const gn::SegArgs<PairTerm> a = {term, f};
+                            if (units > 8) gn::k_seg_reduce<PairTerm, 4, 16><<<chunks, 256, 0, st>>>(a);
+                            else if (units > 4) gn::k_seg_reduce<PairTerm, 4, 8><<<chunks, 256, 0, st>>>(a);
+                            else gn::k_seg_reduce<PairTerm, 4, 4><<<chunks, 256, 0, st>>>(a);
+                        },
+                        st);
 }
 
 // gradients of an empty sum
@@ -1053,7 +944,7 @@ gn_status backward_impl(const float* z, int64_t ld_z, int64_t n, int64_t f, cons
     GN_REQUIRE(z && d && (loss ? sigmoid_scores != nullptr : grad_logit != nullptr) &&
                (from_words ? edges.rel16 != nullptr : (edges.u && edges.v && edges.et)), "operand pointer is null");
     GN_REQUIRE(ld_z >= f && ld_d >= f, "leading dimension smaller than the row length");
-    const WsLayout l = ws_layout(e, std::max(n, r));
+    const gn::SegLayout l = ws_layout(e, std::max(n, r));
     const LdsLayout ll = lds_layout(e, n, r, f);
     GN_REQUIRE(workspace && workspace_bytes >= std::max(l.total, ll.total), "workspace too small: need %zu bytes",
                std::max(l.total, ll.total));
@@ -1074,9 +965,10 @@ gn_status backward_impl(const float* z, int64_t ld_z, int64_t n, int64_t f, cons
         cz.add = dz_add; cz.ld_add = ld_dz_add; cd.add = dd_add; cd.ld_add = ld_dd_add;
         rc = combine_both(cz, n, cd, r, f, st);
     }
-    if (rc == GN_OK && !rt.counting_dz) rc = general_pass(0, c, rt.vec, ws, l);        // key = u
-    if (rc == GN_OK && !rt.counting_dz) rc = general_pass(1, c, rt.vec, ws, l);        // + key = v
-    if (rc == GN_OK && !rt.lds_dd) rc = general_pass(2, c, rt.vec, ws, l);
+    const gn::SegWs<Rec> gw(ws, l);
+    if (rc == GN_OK && !rt.counting_dz) rc = general_pass(0, c, rt.vec, gw);        // key = u
+    if (rc == GN_OK && !rt.counting_dz) rc = general_pass(1, c, rt.vec, gw);        // + key = v
+    if (rc == GN_OK && !rt.lds_dd) rc = general_pass(2, c, rt.vec, gw);
     return rc;
 }
 
@@ -1269,8 +1161,7 @@ gn_status build_bwd_plan(gn_distmult_bwd_plan* p, hipStream_t st) {
     gn_status rc = count_half_edges(EdgeSrc{p->eu.p, p->ev.p, p->er.p, nullptr, nullptr}, none, E, n, R, p->offsets.p, totals, p->he_taskptr.p,
                                     reinterpret_cast<int4*>(p->he_tasks.p), st);
     if (rc != GN_OK) return rc;
-    k_key_offsets<int64_t><<<(int)gn::ceil_div(R + 1, 256), 256, 0, st>>>(p->er.p, E, (int)R, rp);
-    GN_LAUNCH_CHECK();
+    GN_OK_OR_RETURN(gn::first_at_least(p->er.p, E, R, rp, st));
     k_task_ptr<<<1, 1024, 0, st>>>(rp, 1, (int)R, p->pr_taskptr.p, reinterpret_cast<int4*>(p->pr_tasks.p));
     GN_LAUNCH_CHECK();
     rc = place_static_records(p, tmp, st);

@@ -13,15 +13,14 @@
 // Infinity Cache; nothing is planned, the negatives change every step.  RotatE's cos / sin are evaluated once per call for
 // the [R, H] relation table (k_kge_trig), not once per triple and column.
 //
-// Backward: the rule of distmult_bwd.hip - no float atomics.  Per pass (key = head, key = tail, key = relation) 16-byte
-// records (head, tail, relation, g) are sorted by key (rocPRIM radix sort, stable); the sorted array is cut into chunks of
-// kChunkRecs records, one workgroup each; a row that lies inside a chunk is final, a row that continues in a neighbour chunk
-// leaves a partial that k_kge_combine adds in chunk order.  g = grad_out * sigma(-s) when the forward returned the
-// log-sigmoid.  The contribution of a record is g * ds/d(row), a function of the three rows per model and role.
+// Backward: no float atomics.  Per pass (key = head, key = tail, key = relation) 16-byte records (head, tail, relation, g)
+// go through the chunked segmented reduction of seg_reduce.cuh, which the DistMult decoder's general backward shares: sorted
+// by key, cut into chunks, summed per row in a fixed order.  g = grad_out * sigma(-s) when the forward returned the
+// log-sigmoid.  The contribution of a record is g * ds/d(row), a function of the three rows per model and role (KgeTerm).
 #include "common.h"
 #include "kge_term.cuh"
 #include "plan_device.cuh"
-#include "seg_sort.cuh"
+#include "seg_reduce.cuh"
 
 namespace {
 
@@ -168,10 +167,6 @@ __global__ __launch_bounds__(256) void k_kge_forward(FwdArgs a) {
 // ---- backward ----------------------------------------------------------------------------------------------------------
 struct Rec { uint32_t h, t, r; float g; };      // 16 bytes; h = kSkip: a triple with an id outside its table
 constexpr uint32_t kSkip = 0xffffffffu;
-constexpr int kChunkRecs = gn::kSegChunkRecs;
-constexpr int kPartialPerChunk = 2 * 2 * 64;    // floats: [first / last row of the chunk][part][64 columns]
-
-size_t align_up(size_t v) { return gn::seg_align_up(v); }
 
 // keys == null: the records stay in list order (a relation pass over a sorted edge_type)
 __global__ void k_kge_recs(int role, const int64_t* __restrict__ head, const int64_t* __restrict__ tail,
@@ -197,126 +192,35 @@ __global__ void k_kge_recs(int role, const int64_t* __restrict__ head, const int
     }
 }
 
-struct BwdArgs {
-    Tables t;
-    const int32_t* rowptr; const Rec* recs; int64_t n_recs; int rows;
-    float* out; int64_t ld_out; int out_h;          // part p of the output row starts at column p * out_h
-    float* partial; int u0;                         // first unit (of VEC columns) of this launch's column block
-    float divisor; int accumulate;
+// What a record contributes to the row of ROLE: ds / d(row), per part and column (seg_reduce.cuh accumulates g times it with
+// one fused multiply-add per element, as the backward always has).
+template <int M, int ROLE>
+struct KgeTerm {
+    using Rec = ::Rec;
+    static constexpr int P = ROLE == kRelation ? (M == kComplEx ? 2 : 1) : Traits<M>::ent_parts;
+    static constexpr bool kFused = true;
+    Tables t; float divisor;
+    static __device__ __forceinline__ bool skip(const Rec& r) { return r.h == kSkip; }
+    template <int VEC>
+    __device__ __forceinline__ void terms(const Rec& r, int unit, float (&d)[P][VEC]) const {
+        Col col[VEC];
+        load_cols<M, VEC>(t, (int)r.h, (int)r.t, (int)r.r, unit * VEC, col);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float d0, d1;
+            dscore<M, ROLE>(col[v], divisor, d0, d1);
+            d[0][v] = d0;
+            if constexpr (P == 2) d[1][v] = d1;
+        }
+    }
 };
 
-// Chunked segmented reduction (the scheme of k_seg_reduce, distmult_bwd.hip).  256 threads = (256 / LPE) records in flight
-// x LPE lanes of VEC columns; per row of the chunk the lanes' sums are folded through LDS in a fixed order.
-template <int M, int ROLE, int VEC, int LPE>
-__global__ __launch_bounds__(256) void k_kge_reduce(BwdArgs a) {
-    constexpr int S = 256 / LPE;
-    constexpr int P = ROLE == kRelation ? (M == kComplEx ? 2 : 1) : Traits<M>::ent_parts;
-    __shared__ float part[P][S][LPE * VEC];
-    const int j = threadIdx.x % LPE, slot = threadIdx.x / LPE;
-    const int lo = blockIdx.x * kChunkRecs;
-    const int hi = (int)min((int64_t)lo + kChunkRecs, a.n_recs);
-    const int unit = a.u0 + j;
-    const bool col_ok = unit * VEC < a.t.h;                 // (h is a multiple of VEC)
-    // the first row with a record at or behind `lo`: the last row that begins at or before it
-    int r_first = 0;
-    {
-        int l = 0, h = a.rows;                              // largest row in [0, rows) with rowptr[row] <= lo, 0 if none
-        while (l < h) {
-            const int mid = (l + h) >> 1;
-            if (a.rowptr[mid] <= lo) l = mid + 1; else h = mid;
-        }
-        r_first = max(l - 1, 0);
-    }
-    for (int row = r_first; row < a.rows; ++row) {
-        const int rb = a.rowptr[row], re = a.rowptr[row + 1];
-        if (rb >= hi) break;                                // workgroup-uniform
-        const int begin = max(lo, rb), end = min(hi, re);
-        if (begin >= end) continue;
-        float acc[P][VEC];
-#pragma unroll
-        for (int p = 0; p < P; ++p)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[p][v] = 0.f;
-        if (col_ok) {
-            for (int i = begin + slot; i < end; i += S) {
-                const Rec rec = a.recs[i];
-                if (rec.h == kSkip) continue;
-                Col col[VEC];
-                load_cols<M, VEC>(a.t, (int)rec.h, (int)rec.t, (int)rec.r, unit * VEC, col);
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) {
-                    float d0, d1;
-                    dscore<M, ROLE>(col[v], a.divisor, d0, d1);
-                    acc[0][v] += rec.g * d0;
-                    if constexpr (P == 2) acc[1][v] += rec.g * d1;
-                }
-            }
-        }
-        __syncthreads();                                    // the previous row's fold is done with `part`
-#pragma unroll
-        for (int p = 0; p < P; ++p)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) part[p][slot][j * VEC + v] = acc[p][v];
-        __syncthreads();
-        // thread (p, column) folds the S slots in slot order
-        for (int idx = threadIdx.x; idx < P * LPE * VEC; idx += 256) {
-            const int p = idx / (LPE * VEC), c = idx % (LPE * VEC);
-            const int column = a.u0 * VEC + c;
-            if (column >= a.t.h) continue;
-            float s = part[p][0][c];
-            for (int k = 1; k < S; ++k) s += part[p][k][c];
-            if (rb >= lo && re <= hi) {                     // the whole row is here: final
-                float* o = a.out + (int64_t)row * a.ld_out + (int64_t)p * a.out_h + column;
-                *o = a.accumulate ? *o + s : s;
-            } else {                                        // shared with a neighbour chunk
-                const int which = rb <= lo ? 0 : 1;
-                a.partial[(size_t)blockIdx.x * kPartialPerChunk + (which * 2 + p) * 64 + c] = s;
-            }
-        }
-    }
+size_t trig_bytes(int model, int64_t r, int64_t h) { return model == kRotatE ? gn::seg_align_up((size_t)2 * r * h * sizeof(float)) : 0; }
+
+// the backward's scratch: the reduction's (up to two output parts), RotatE's cos / sin tables in its tail
+gn::SegLayout ws_layout(int model, int64_t n, int64_t r, int64_t h, int64_t e) {
+    return gn::seg_layout<Rec>(e, std::max(n, r), 2, trig_bytes(model, r, h));
 }
-
-// Rows that straddle chunks: out[row, block] (+)= the chunks' partials in chunk order; rows without a record: zeros.
-__global__ void k_kge_combine(const int32_t* __restrict__ rowptr, const float* __restrict__ partial, float* __restrict__ out,
-                              int64_t ld_out, int out_h, int parts, int c0, int width, int accumulate) {
-    const int row = blockIdx.x, c = threadIdx.x % 64, p = threadIdx.x / 64;
-    if (c >= width || p >= parts) return;
-    const int rb = rowptr[row], re = rowptr[row + 1];
-    float* o = out + (int64_t)row * ld_out + (int64_t)p * out_h + c0 + c;
-    if (rb >= re) {
-        if (!accumulate) *o = 0.f;
-        return;
-    }
-    const int cb = rb / kChunkRecs, ce = (re - 1) / kChunkRecs;
-    if (cb == ce) return;                                   // inside one chunk: k_kge_reduce wrote the final value
-    float s = 0.f;
-    for (int b = cb; b <= ce; ++b) {
-        const int which = rb <= b * kChunkRecs ? 0 : 1;
-        s += partial[(size_t)b * kPartialPerChunk + (which * 2 + p) * 64 + c];
-    }
-    *o = accumulate ? *o + s : s;
-}
-
-struct WsLayout { size_t keys, keys_sorted, recs, recs_sorted, rowptr, partial, trig, sort_tmp, total; };
-
-WsLayout ws_layout(int model, int64_t n, int64_t r, int64_t h, int64_t e) {
-    WsLayout l;
-    size_t sort_bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const Rec*)nullptr,
-                                    (Rec*)nullptr, (size_t)e, 0, 32, (hipStream_t)0);
-    l.keys = 0;
-    l.keys_sorted = l.keys + align_up(e * sizeof(uint32_t));
-    l.recs = l.keys_sorted + align_up(e * sizeof(uint32_t));
-    l.recs_sorted = l.recs + align_up(e * sizeof(Rec));
-    l.rowptr = l.recs_sorted + align_up(e * sizeof(Rec));
-    l.partial = l.rowptr + align_up((std::max(n, r) + 2) * sizeof(int32_t));
-    l.trig = l.partial + align_up((size_t)gn::ceil_div(e, kChunkRecs) * kPartialPerChunk * sizeof(float));
-    l.sort_tmp = l.trig + align_up(model == kRotatE ? (size_t)2 * r * h * sizeof(float) : 0);
-    l.total = l.sort_tmp + align_up(sort_bytes);
-    return l;
-}
-
-size_t trig_bytes(int model, int64_t r, int64_t h) { return model == kRotatE ? align_up((size_t)2 * r * h * sizeof(float)) : 0; }
 
 // The relation operand as the kernels read it: the table itself, or (RotatE) cos / sin of its phases in `trig`.
 gn_status relation_operand(int model, Tables& t, const float* rel, int64_t ld_rel, float divisor, float* trig, hipStream_t st) {
@@ -339,7 +243,7 @@ gn_status check_shapes(int model, const float* ent, int64_t ld_ent, int64_t n, c
                        int64_t h, int64_t e) {
     GN_REQUIRE(model >= kTransE && model <= kRotatE, "unknown model %d (0 TransE, 1 DistMult, 2 ComplEx, 3 RotatE)", model);
     GN_REQUIRE(n >= 0 && r >= 0 && h >= 0 && e >= 0, "negative size");
-    if (n >= (1ll << 31) - 512 || r >= (1ll << 31) - 512 || h >= (1ll << 29) || e >= (1ll << 31) - kChunkRecs)   // (grids of 256 threads over rows + 1)
+    if (n >= (1ll << 31) - 512 || r >= (1ll << 31) - 512 || h >= (1ll << 29) || e >= (1ll << 31) - gn::kSegChunkRecs)   // (grids of 256 threads over rows + 1)
         return gn::fail(GN_ERR_UNSUPPORTED, "a table or the triple list is beyond the 32-bit record encoding");
     if (e == 0) return GN_OK;
     GN_REQUIRE(n > 0 && r > 0, "triples given but the entity or relation table is empty");
@@ -354,20 +258,6 @@ void launch_forward(const FwdArgs& a, bool vec, int grid, hipStream_t st) {
     if (vec) k_kge_forward<M, 4><<<grid, 256, 0, st>>>(a); else k_kge_forward<M, 1><<<grid, 256, 0, st>>>(a);
 }
 
-template <int M, int ROLE>
-void launch_reduce(const BwdArgs& a, bool vec, int lpe, unsigned chunks, hipStream_t st) {
-    if (!vec) k_kge_reduce<M, ROLE, 1, 16><<<chunks, 256, 0, st>>>(a);
-    else if (lpe == 8) k_kge_reduce<M, ROLE, 4, 8><<<chunks, 256, 0, st>>>(a);
-    else k_kge_reduce<M, ROLE, 4, 16><<<chunks, 256, 0, st>>>(a);
-}
-
-template <int M>
-void launch_reduce_role(int role, const BwdArgs& a, bool vec, int lpe, unsigned chunks, hipStream_t st) {
-    if (role == kHead) launch_reduce<M, kHead>(a, vec, lpe, chunks, st);
-    else if (role == kTail) launch_reduce<M, kTail>(a, vec, lpe, chunks, st);
-    else launch_reduce<M, kRelation>(a, vec, lpe, chunks, st);
-}
-
 struct BwdCall {
     int model; Tables t;
     const int64_t* head; const int64_t* tail; const int64_t* et; int64_t e;
@@ -376,57 +266,49 @@ struct BwdCall {
     bool types_sorted, vec; hipStream_t st;
 };
 
-// one pass: records keyed by `role`, sorted (or left in list order), reduced per row
-gn_status pass(int role, const BwdCall& c, char* ws, const WsLayout& l) {
-    uint32_t* keys = reinterpret_cast<uint32_t*>(ws + l.keys);
-    uint32_t* keys_sorted = reinterpret_cast<uint32_t*>(ws + l.keys_sorted);
-    Rec* recs = reinterpret_cast<Rec*>(ws + l.recs);
-    Rec* recs_sorted = reinterpret_cast<Rec*>(ws + l.recs_sorted);
-    int32_t* rowptr = reinterpret_cast<int32_t*>(ws + l.rowptr);
-    float* partial = reinterpret_cast<float*>(ws + l.partial);
-    size_t sort_bytes = l.total - l.sort_tmp;
-    hipStream_t st = c.st;
-    const int64_t e = c.e;
+// The column-block rule, kept from the parent (the bits depend on it): float4 rows take blocks of 8 units on 8 lanes when a
+// row has no more than 8 units, of 16 on 16 lanes otherwise; rows that are not float4 rows take 16 lanes of one column.
+template <int M, int ROLE>
+void launch_reduce(const BwdCall& c, const gn::SegFrame<Rec>& f, int lpe, unsigned chunks) {
+    const gn::SegArgs<KgeTerm<M, ROLE>> a = {{c.t, c.divisor}, f};
+    if (!c.vec) gn::k_seg_reduce<KgeTerm<M, ROLE>, 1, 16><<<chunks, 256, 0, c.st>>>(a);
+    else if (lpe == 8) gn::k_seg_reduce<KgeTerm<M, ROLE>, 4, 8><<<chunks, 256, 0, c.st>>>(a);
+    else gn::k_seg_reduce<KgeTerm<M, ROLE>, 4, 16><<<chunks, 256, 0, c.st>>>(a);
+}
+
+template <int M>
+void launch_reduce_role(int role, const BwdCall& c, const gn::SegFrame<Rec>& f, int lpe, unsigned chunks) {
+    if (role == kHead) launch_reduce<M, kHead>(c, f, lpe, chunks);
+    else if (role == kTail) launch_reduce<M, kTail>(c, f, lpe, chunks);
+    else launch_reduce<M, kRelation>(c, f, lpe, chunks);
+}
+
+// one pass: records keyed by `role`, sorted (or left in list order: a relation pass over a sorted edge_type), reduced per row
+gn_status pass(int role, const BwdCall& c, const gn::SegWs<Rec>& w) {
     const int64_t rows = role == kRelation ? c.t.r : c.t.n;
     const bool in_place = role == kRelation && c.types_sorted;
-    k_kge_recs<<<gn::stream_grid(e, 256), 256, 0, st>>>(role, c.head, c.tail, c.et, c.grad_out, c.raw, e, c.t.n, c.t.r, (uint32_t)rows,
-                                                         in_place ? nullptr : keys, recs);
+    k_kge_recs<<<gn::stream_grid(c.e, 256), 256, 0, c.st>>>(role, c.head, c.tail, c.et, c.grad_out, c.raw, c.e, c.t.n, c.t.r, (uint32_t)rows,
+                                                             in_place ? nullptr : w.keys, w.recs);
     GN_LAUNCH_CHECK();
-    const int off_grid = (int)gn::ceil_div(rows + 1, 256);
-    if (in_place) {
-        gn::k_key_offsets<int64_t><<<off_grid, 256, 0, st>>>(c.et, e, (int)rows, rowptr);
-        GN_LAUNCH_CHECK();
-    } else {
-        GN_HIP(rocprim::radix_sort_pairs(ws + l.sort_tmp, sort_bytes, keys, keys_sorted, recs, recs_sorted, (size_t)e, 0,
-                                         gn::bits_for(rows + 1), st));
-        gn::k_key_offsets<uint32_t><<<off_grid, 256, 0, st>>>(keys_sorted, e, (int)rows, rowptr);
-        GN_LAUNCH_CHECK();
-    }
-    BwdArgs a;
-    a.t = c.t; a.rowptr = rowptr; a.recs = in_place ? recs : recs_sorted; a.n_recs = e; a.rows = (int)rows;
-    a.out = role == kRelation ? c.d_rel : c.d_ent;
-    a.ld_out = role == kRelation ? c.ld_drel : c.ld_dent;
-    a.out_h = c.t.h; a.partial = partial; a.divisor = c.divisor;
-    a.accumulate = role == kTail;                           // d_ent = head pass, then + tail pass
-    const int parts = role == kRelation ? (c.model == kComplEx ? 2 : 1) : ((c.model == kComplEx || c.model == kRotatE) ? 2 : 1);
+    gn::SegOut o;
+    o.out = role == kRelation ? c.d_rel : c.d_ent;
+    o.ld_out = role == kRelation ? c.ld_drel : c.ld_dent;
+    o.out_h = c.t.h;
+    o.parts = role == kRelation ? (c.model == kComplEx ? 2 : 1) : ((c.model == kComplEx || c.model == kRotatE) ? 2 : 1);
+    o.accumulate = role == kTail;                           // d_ent = head pass, then + tail pass
     const int vecw = c.vec ? 4 : 1;
     const int units = c.t.h / vecw;
     const int lpe = (c.vec && units <= 8) ? 8 : 16;
-    const unsigned chunks = (unsigned)gn::ceil_div(e, kChunkRecs);
-    for (int u0 = 0; u0 < units; u0 += lpe) {
-        a.u0 = u0;
-        switch (c.model) {
-            case kTransE: launch_reduce_role<kTransE>(role, a, c.vec, lpe, chunks, st); break;
-            case kDistMult: launch_reduce_role<kDistMult>(role, a, c.vec, lpe, chunks, st); break;
-            case kComplEx: launch_reduce_role<kComplEx>(role, a, c.vec, lpe, chunks, st); break;
-            default: launch_reduce_role<kRotatE>(role, a, c.vec, lpe, chunks, st); break;
-        }
-        GN_LAUNCH_CHECK();
-        const int width = std::min(lpe * vecw, c.t.h - u0 * vecw);
-        k_kge_combine<<<(unsigned)rows, 64 * parts, 0, st>>>(rowptr, partial, a.out, a.ld_out, a.out_h, parts, u0 * vecw, width, a.accumulate);
-        GN_LAUNCH_CHECK();
-    }
-    return GN_OK;
+    return gn::seg_pass(w, c.e, rows, in_place ? c.et : nullptr, o, units, vecw, lpe,
+                        [&](const gn::SegFrame<Rec>& f, int, unsigned chunks) {
+                            switch (c.model) {
+                                case kTransE: launch_reduce_role<kTransE>(role, c, f, lpe, chunks); break;
+                                case kDistMult: launch_reduce_role<kDistMult>(role, c, f, lpe, chunks); break;
+                                case kComplEx: launch_reduce_role<kComplEx>(role, c, f, lpe, chunks); break;
+                                default: launch_reduce_role<kRotatE>(role, c, f, lpe, chunks); break;
+                            }
+                        },
+                        c.st);
 }
 
 }  // namespace
@@ -491,7 +373,7 @@ extern "C" gn_status gn_kge_backward_f32(int model, const float* ent, int64_t ld
         return GN_OK;
     }
     GN_REQUIRE(head && tail && et && grad_out, "operand pointer is null");
-    const WsLayout l = ws_layout(model, n, r, h, e);
+    const gn::SegLayout l = ws_layout(model, n, r, h, e);
     GN_REQUIRE(workspace && workspace_bytes >= l.total, "workspace too small: need %zu bytes", l.total);
     GN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
     char* ws = static_cast<char*>(workspace);
@@ -499,14 +381,15 @@ extern "C" gn_status gn_kge_backward_f32(int model, const float* ent, int64_t ld
     c.model = model;
     c.t.ent = ent; c.t.ld_ent = ld_ent; c.t.n = n; c.t.r = r; c.t.h = (int)h;
     if (model == kRotatE) GN_REQUIRE(phase_divisor != 0.f, "RotatE: the phase divisor is zero");
-    GN_OK_OR_RETURN(relation_operand(model, c.t, rel, ld_rel, phase_divisor, reinterpret_cast<float*>(ws + l.trig), st));
+    GN_OK_OR_RETURN(relation_operand(model, c.t, rel, ld_rel, phase_divisor, reinterpret_cast<float*>(ws + l.tail), st));
     c.head = head; c.tail = tail; c.et = et; c.e = e; c.grad_out = grad_out; c.raw = raw_scores;
     c.divisor = model == kRotatE ? phase_divisor : 1.0f;
     c.d_ent = d_ent; c.ld_dent = ld_dent; c.d_rel = d_rel; c.ld_drel = ld_drel;
     c.types_sorted = (flags & GN_DM_TYPES_SORTED) != 0;
     c.vec = vector_rows(c.t);                              // (the gradients are stored a float at a time: any ld)
     c.st = st;
-    GN_OK_OR_RETURN(pass(kHead, c, ws, l));
-    GN_OK_OR_RETURN(pass(kTail, c, ws, l));
-    return pass(kRelation, c, ws, l);
+    const gn::SegWs<Rec> w(ws, l);
+    GN_OK_OR_RETURN(pass(kHead, c, w));
+    GN_OK_OR_RETURN(pass(kTail, c, w));
+    return pass(kRelation, c, w);
 }

@@ -1,5 +1,6 @@
 // Device stages that several plan builders share: the rocprim size-query / scratch / run triples, the two binary searches and
-// the row-pointer kernel.  Plan construction only: the step-path kernels keep their own searches.
+// the row-pointer kernel.  Plan construction, and the row offsets of the sort-based backwards (seg_reduce.cuh); the other
+// step-path kernels keep their own searches.
 #pragma once
 
 #include "common.h"
@@ -75,16 +76,24 @@ __device__ __forceinline__ int lower_bound(const T* __restrict__ keys, int n, T 
     return lo;
 }
 
-// out[i] = first position whose key is >= i, for i in [0, count]: the row pointers of a sorted key list.
+// out[i] = first position whose key is >= i, for i in [0, count]: the row pointers of a sorted key list - a plan's, or a
+// step's (seg_reduce.cuh).  The compare is signed and 64 bits wide: the ids below 0 of a sorted int64 edge_type sit in
+// front of row 0 (ids >= count behind the last row), and a uint32 sort key compares as itself.
 template <typename T>
-__global__ void k_first_at_least(const T* __restrict__ sorted, int n, int64_t count, int32_t* __restrict__ out) {
+__global__ void k_first_at_least(const T* __restrict__ sorted, int64_t n, int64_t count, int32_t* __restrict__ out) {
     const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-    if (i <= count) out[i] = lower_bound(sorted, n, (T)i);
+    if (i > count) return;
+    int64_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)sorted[mid] < i) lo = mid + 1; else hi = mid;
+    }
+    out[i] = (int32_t)lo;
 }
 
 template <typename T>
 gn_status first_at_least(const T* sorted, int64_t n, int64_t count, int32_t* out, hipStream_t st) {
-    k_first_at_least<T><<<(int)ceil_div(count + 1, 256), 256, 0, st>>>(sorted, (int)n, count, out);
+    k_first_at_least<T><<<(int)ceil_div(count + 1, 256), 256, 0, st>>>(sorted, n, count, out);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }

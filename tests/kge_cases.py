@@ -16,7 +16,7 @@ MODELS = ("TransE", "DistMult", "ComplEx", "RotatE")
 EPS = 1e-13                                                       # gripnet/utils.py:10
 PI = 3.14159265358979323846                                       # :214
 U = 2.0 ** -24                                                    # unit roundoff of fp32
-CHUNK = 2048                                                      # records per workgroup of the backward's reduction (csrc/kge.hip)
+CHUNK = 2048                                                      # records per workgroup of the backward's reduction (csrc/seg_reduce.cuh: kSegChunkRecs)
 
 
 def dims(model, H):

@@ -546,6 +546,63 @@ def test_decoder_backward_large_sorted_lists(gpu, n, f, R, use_probs):
     _hip.raise_if_index_errors(gpu)
 
 
+SEG_CHUNK = 2048                                               # records per workgroup of the general path's reduction (csrc/seg_reduce.cuh)
+SEG_COUNTS = (SEG_CHUNK - 1, SEG_CHUNK, SEG_CHUNK + 1, 5000)   # a row that ends one short of / at / one behind a chunk; three chunks
+
+
+def chunk_boundary_triples(n, R, e, gen):
+    """(u_v [2, e], edge_type [e]) in which - as u, as v and as relation alike - keys 0..3 have SEG_COUNTS records and
+    the last key has none; the three columns are shuffled independently, so every pass's sorted order is its own."""
+    def column(keys):
+        fixed = torch.cat([torch.full((c,), k, dtype=torch.int64) for k, c in enumerate(SEG_COUNTS)])
+        rest = torch.randint(4, keys - 1, (e - fixed.numel(),), generator=gen)
+        col = torch.cat([fixed, rest])
+        col = col[torch.randperm(e, generator=gen)]
+        count = torch.bincount(col, minlength=keys)
+        assert count[:4].tolist() == list(SEG_COUNTS) and int(count[keys - 1]) == 0 and int(count.sum()) == e
+        return col
+    return torch.stack([column(n), column(n)]), column(R)
+
+
+@pytest.mark.parametrize("f", [80, 24])
+def test_decoder_backward_chunk_boundaries_general_path(gpu, f, monkeypatch):
+    """The general path (tables beyond the LDS: n = 3,000) on a list whose u, v and relation keys each have rows of 2047,
+    2048, 2049 and 5,000 records and a row of none: rows that end at, next to and across the reduction's chunks.  Against
+    float64 at the gradient's own scale, the same bits on every call, and the same bits again with the fast paths switched
+    off - where only the general path is left, so it served the first calls too."""
+    n, R, e = 3000, 6, 20000
+    gen = torch.Generator().manual_seed(977 + f)
+    ei, et = chunk_boundary_triples(n, R, e, gen)
+    ei, et = ei.to(gpu), et.to(gpu)
+    z = (torch.randn(n, f, generator=gen) * 0.5).to(gpu)
+    w = (torch.randn(R, f, generator=gen) * 0.5).to(gpu)
+    g = torch.randn(e, generator=gen).to(gpu)
+    gd = g.double()
+    zu, zv, wr = z.double()[ei[0]], z.double()[ei[1]], w.double()[et]
+    ref_dz = torch.zeros(n, f, dtype=torch.float64, device=gpu)
+    ref_dz.index_add_(0, ei[0], gd[:, None] * zv * wr)
+    ref_dz.index_add_(0, ei[1], gd[:, None] * zu * wr)
+    ref_dd = torch.zeros(R, f, dtype=torch.float64, device=gpu).index_add_(0, et, gd[:, None] * zu * zv)
+    assert float(ref_dz[n - 1].abs().max()) == 0.0 and float(ref_dd[R - 1].abs().max()) == 0.0
+    tol_z, tol_d = 2e-5 * float(ref_dz.abs().max()), 2e-5 * float(ref_dd.abs().max())      # (at the gradient's own scale)
+    outs = []
+    for call in range(3):
+        if call == 2:
+            monkeypatch.setenv("GN_DISABLE_FAST", "1")
+        dz, dd = torch.full_like(z, 7.0), torch.full_like(w, 7.0)
+        with _hip.Recorder() as rec:
+            _hip.distmult_backward(z, ei, et, w, g, dz, dd)
+        assert [name for _, _, name, _ in rec.calls] == ["gn_distmult_backward_ex_f32"]
+        err_z, err_d = float((dz.double() - ref_dz).abs().max()), float((dd.double() - ref_dd).abs().max())
+        print("call {}: dz err {:.3e} (allowed {:.3e}), dD err {:.3e} (allowed {:.3e})".format(call, err_z, tol_z, err_d, tol_d))
+        assert err_z <= tol_z and err_d <= tol_d
+        assert float(dz[n - 1].abs().max()) == 0.0 and float(dd[R - 1].abs().max()) == 0.0
+        outs.append((dz, dd))
+    for dz, dd in outs[1:]:
+        assert torch.equal(outs[0][0], dz) and torch.equal(outs[0][1], dd)
+    _hip.raise_if_index_errors(gpu)
+
+
 def _sharded_hip_worker(rank, world, port, q):
     """One rank of a 2-way sharded training step on the HIP kernels; both ranks share cuda:0, the exchanges travel
     over gloo through host copies (the product uses RCCL on the ranks' own GPUs: gripnet_amd/sharded.py)."""

@@ -24,13 +24,13 @@ Guard by guard (csrc line numbers as of ABI 159; "formula": the size is found by
                                                                             n > 8192 before the layout is built.
   distmult_fast.hip:177,247 n <= 65535, r <= 65535                           n: unreachable (the LDS fit above, n <= 2400, binds first);
                                                                             r: behind Python's 32767, test_decoder_relation_counts
-  distmult_bwd.hip:764,1356,1374  n <= 65535 / <= 65536                      the n, r <= 65535 test of the LDS path is gone: tables_fit_lds
+  distmult_bwd.hip:652,1215,1233  n <= 65535 / <= 65536                      the n, r <= 65535 test of the LDS path is gone: tables_fit_lds
                                                                             (:762, n + r <= 2400) binds first, and the static_assert
                                                                             kLdsTableBudget / 64 <= 65535 (:764) says so.  r <= 65535 stays
                                                                             for the relation-major reduction alone (:857: it decides at 200
                                                                             nodes x 65536 relations, test_decoder_relation_counts[65536]);
                                                                             <= 65536 stays as the packed entry points' argument contract
-  distmult_bwd.hip:339,763        kSortMaxKeys = 4096                        no run-time test left: static_assert kLdsTableBudget / 64 <=
+  distmult_bwd.hip:243,651        kSortMaxKeys = 4096                        no run-time test left: static_assert kLdsTableBudget / 64 <=
                                                                             kSortMaxKeys (:763).  The binding limit is the formula
                                                                             n + r <= 2400 (route_of_shapes, :851): test_decoder_backward_at_the_lds_limit
                                                                             (planned, packed and loss-fed launches; bisected on plan builds)
@@ -342,7 +342,7 @@ def loss_fed_step(dev, n, R, f, seed, expect_planned, expect_packed):
 
 
 def test_decoder_backward_at_the_lds_limit(gpu):
-    """The planned, the packed and the loss-fed backward keep dz and dD in LDS: nodes + relations <= 2400 (distmult_bwd.hip:762,851).
+    """The planned, the packed and the loss-fed backward keep dz and dD in LDS: nodes + relations <= 2400 (distmult_bwd.hip:650,739).
     The last admitted node count is found by bisecting backward-plan builds; it and the next one run every backward form."""
     R, f = 8, 16
     gen = torch.Generator().manual_seed(1)
