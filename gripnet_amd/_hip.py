@@ -25,6 +25,7 @@ GN_OK, GN_ERR_INVALID_ARG, GN_ERR_HIP, GN_ERR_INDEX_RANGE, GN_ERR_UNSUPPORTED, G
 GN_RGCN_PARTIAL, GN_RGCN_ARITH_FAST, GN_RGCN_BASIS_TRANSPOSED = 1, 4, 64        # flags of gn_rgcn_forward_f32
 GN_RGCN_PATH_SHIFT = 8
 RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}                  # kernel choice (tests, measurements)
+RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
@@ -937,40 +938,55 @@ class RgcnPlan(Handle):
         self.num_nodes, self.num_relations, self.num_edges = int(num_nodes), int(rl.shape[0]), e
         self.edge_lo, self.edge_hi = lo, hi
         self._ws = None
-        self._edge_index, self._range_list, self._grad, self._wgrad = ei, rl, None, None
+        self._edge_index, self._range_list, self._wgrad = ei, rl, None
+        self._deg = self._rev = self._pairs = None
 
-    def grad_plans(self):
-        """(reversed-graph relational plan, (relation, source)-major sum plan, in-degree divisor) for the
-        backward pass; built on first use.  For a shard (edge_lo / edge_hi) the two plans cover the shard's edges only -
-        its share of the sums over edges - while the divisor is the in-degree over the FULL graph, as in the forward."""
-        if self._grad is None:
+    # What the backward pass needs of the graph, each part built on first use.  For a shard (edge_lo / edge_hi) the two plans
+    # cover the shard's edges only - its share of the sums over edges - while the divisor is the in-degree over the FULL
+    # graph, as in the forward.
+    def in_degree(self):
+        """[n] fp32: the mean's divisor of every destination, max(1, in-degree)."""
+        if self._deg is None:
+            ei = self._edge_index
+            deg = torch.zeros(self.num_nodes, dtype=torch.float32, device=self.device)
+            deg.index_add_(0, ei[1], torch.ones(e_count(ei), dtype=torch.float32, device=self.device))
+            self._deg = deg.clamp_(min=1.0)
+        return self._deg
+
+    def reversed_plan(self):
+        """The relational plan of the same edge positions with their endpoints swapped (dx is the layer on it)."""
+        if self._rev is None:
+            self._rev = RgcnPlan(self._edge_index.flip(0).contiguous(), self._range_list, self.num_nodes, self.edge_lo, self.edge_hi)
+        return self._rev
+
+    def pair_sums(self):
+        """The plain-sum plan dst -> (relation, source) row: its aggregation of gm is Q [R * n, fout] of dW_r = X^T Q_r."""
+        if self._pairs is None:
             ei, n, R = self._edge_index, self.num_nodes, self.num_relations
-            lo, hi = self.edge_lo, self.edge_hi
-            rev = RgcnPlan(ei.flip(0).contiguous(), self._range_list, n, lo, hi)   # same edge positions, endpoints swapped
             sizes = (self._range_list[:, 1] - self._range_list[:, 0]).to(self.device)
             rel = torch.repeat_interleave(torch.arange(R, device=self.device), sizes)      # relation of every edge
-            keyed = torch.stack([ei[1], rel * n + ei[0]])[:, lo:hi].contiguous()           # dst -> (relation, src) row
-            pairs = GraphPlan.plain_sum(keyed, n, R * n)
-            deg = torch.zeros(n, dtype=torch.float32, device=self.device)
-            deg.index_add_(0, ei[1], torch.ones(e_count(ei), dtype=torch.float32, device=self.device))
-            self._grad = (rev, pairs, deg.clamp_(min=1.0))
-        return self._grad
+            keyed = torch.stack([ei[1], rel * n + ei[0]])[:, self.edge_lo:self.edge_hi].contiguous()
+            self._pairs = GraphPlan.plain_sum(keyed, n, R * n)
+        return self._pairs
 
     def weight_grad_plan(self):
         """RelGradPlan of this layer's (shard's) edges, or None where the fused kernel does not apply (> 65534 nodes)."""
         if self._wgrad is None:
             try:
-                self._wgrad = RelGradPlan(self.grad_plans()[1], self.num_nodes, self.num_relations)
+                self._wgrad = RelGradPlan(self.pair_sums(), self.num_nodes, self.num_relations)
             except Unsupported:
                 self._wgrad = False
         return self._wgrad or None
 
-    def general_weight_grad(self, x, gm):
+    def general_weight_grad_supported(self, fin, fout) -> bool:
+        return bool(load().gn_rgcn_weight_grad_supported(self._h, int(fin), int(fout)))
+
+    def general_weight_grad(self, x, gm, supported=None):
         """dw [R, fin * fout] = sum over each relation's edges of x[src]^T gm[dst] on gn_rgcn_weight_grad_f32 (any number of
-        nodes), or None where it does not cover the shapes."""
+        nodes), or None where it does not cover the shapes (`supported`: that answer, from a caller that has asked)."""
         fin, fout = x.shape[1], gm.shape[1]
         lib = load()
-        if not lib.gn_rgcn_weight_grad_supported(self._h, fin, fout):
+        if not (self.general_weight_grad_supported(fin, fout) if supported is None else supported):
             return None
         ei = self._edge_index
         dw = torch.empty((self.num_relations, fin * fout), dtype=torch.float32, device=x.device)
@@ -1002,7 +1018,7 @@ class RgcnPlan(Handle):
             code = int(load().gn_rgcn_forward_choice(self._h, x.data_ptr(), ld(x), fin, fout, bases, self.mode_flags(fast, path), None))
         else:
             code = int(load().gn_rgcn_forward_path(self._h, fin, fout, bases, self.mode_flags(fast, path)))
-        return {v: k for k, v in RGCN_PATHS.items()}.get(code, "?")
+        return RGCN_PATH_NAMES.get(code, "?")
 
     def forward(self, x, basis, att, root, bias, relu, out, partial=False, side=None, fast=False, path="auto", x_planes=None,
                 basis_transposed=False):

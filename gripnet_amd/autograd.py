@@ -8,13 +8,17 @@ DistMult scatter), and so do the dense contractions: the tall-skinny weight grad
 dW_r = X^T Q_r (gn_rel_weight_grad_f32), dx = g W^T and the basis / attention gradients (gn_gemm_f32 with operands given
 transposed; x^T g wider than 64 x 32 outputs in tiles), the class decoder's row gather / scatter-add through a one-edge-per-node
 plan, the merges of the external layer's mod="add" branches and of freebase-c, the relational weight gradient of graphs beyond
-the fused kernel per relation on gn_rgcn_weight_grad_f32 (the all-nodes baseline of rgcn_pose.py).  torch arithmetic is left
-for shapes outside every kernel only (a relational layer with more than 128 input or 64 output features: rgcn_edge_gradients'
-index_add_ + batched matmul per slab of relations; more than 64 bases: att^T dW).
+the fused kernel per relation on gn_rgcn_weight_grad_f32 (the all-nodes baseline of rgcn_pose.py).  Which of these the
+relational layer's backward takes is decided in one place, relational_backward_route, and each route is one function
+(_dx_* / _dw_*; rgcn_edge_route names a call's routes without running it).  torch arithmetic is left for shapes outside
+every kernel only: where neither weight-gradient kernel takes the operands (more than 128 input or 64 output features, a
+strided x or gm) dW_r is the HIP (relation, source) sums + a batched matmul (route "dense"), or index_add_ + a batched
+matmul per slab of relations when those sums would exceed Q_BUDGET_FLOATS ("slabs"); more than 64 bases: att^T dW.
 """
 from __future__ import annotations
 
 import threading
+from collections import namedtuple
 
 import torch
 
@@ -195,7 +199,7 @@ class RgcnConvFn(torch.autograd.Function):
         x, basis, att, root, out = ctx.saved_tensors
         if g is None:
             return (g_pass if ctx.needs_input_grad[0] else None,) + (None,) * 10
-        deg = ctx.plan.grad_plans()[2]
+        deg = ctx.plan.in_degree()
         # one launch: ReLU mask, gm = g / deg (the gradient of the un-normalised sum), the bias gradient
         g, gm, dbias = _hip.grad_prologue(g, out if ctx.relu else None, deg, True, bool(ctx.needs_input_grad[4]))
         # dbasis, datt and droot are independent, deep and small: they leave as ONE launch at the end of the block
@@ -217,70 +221,130 @@ class RgcnConvFn(torch.autograd.Function):
 # with 10^3 relations x 10^5 nodes would need over 12 GB where the reference's per-relation loop needs O(E))
 Q_BUDGET_FLOATS = 1 << 26
 
+RelBackwardRoute = namedtuple("RelBackwardRoute", "dx dw dbasis")
+
+
+def relational_backward_route(fin, fout, bases, *, relations, nodes, q_budget, need_x, need_basis, need_att, rev_kernel=None,
+                              basis_in_place=False, unit_strides=False, fused_ok=False, general_ok=False) -> RelBackwardRoute:
+    """Which route each part of `rgcn_edge_gradients` takes for a layer fin -> fout on `bases` bases: names of `_DX_ROUTES`
+    and `_DW_ROUTES` and "gemm" / "torch" for dbasis (datt has one route), None for a part that is not needed.  Plain values
+    only.  `rev_kernel`: the reversed plan's kernel for (fout, fin, bases) (RgcnPlan.path); `basis_in_place`: the forward's
+    basis is contiguous and 16-byte aligned; `unit_strides`: x and gm have unit column stride; `fused_ok` / `general_ok`:
+    gn_rel_weight_grad_supported (and its plan exists) / gn_rgcn_weight_grad_supported; `q_budget`: Q_BUDGET_FLOATS."""
+    dx = dw = None
+    if need_x:
+        if rev_kernel != "pair" and fout == 32 and fin > 32 and fin % 32 != 0:
+            dx = "blocks"
+        else:
+            dx = "transposed" if rev_kernel == "pair" and basis_in_place else "direct"
+    if need_basis or need_att:
+        if unit_strides and fused_ok:
+            dw = "fused"
+        elif unit_strides and general_ok:
+            dw = "general"
+        else:
+            dw = "dense" if relations * nodes * fout <= q_budget else "slabs"
+    return RelBackwardRoute(dx, dw, ("gemm" if bases <= 64 else "torch") if need_basis else None)
+
 
 def rgcn_edge_gradients(plan, x, basis, att, gm, need_x=True, need_basis=True, need_att=True):
     """The parts of the relational layer's gradient that are sums over the plan's edges (a shard's edge range gives
     that shard's share; the shares add up): for P = sum_e x[src_e] W_{r(e)} and gm = dL/dP,
         dx[s]  = sum_{e: src=s} gm[dst_e] W_{r(e)}^T
         dW_r   = X^T Q_r,  Q_r[s] = sum_{e in r, src=s} gm[dst_e];   dbasis = att^T dW,  datt = dW basis^T."""
-    n, fin = x.shape
-    B, _, fout = basis.shape
-    R = att.shape[0]
-    rev, pairs, _ = plan.grad_plans()
+    route = rgcn_edge_route(plan, x, basis, att, gm, need_x, need_basis, need_att)
+    B, fin, fout = basis.shape
     dxe = dbasis = datt = None
-    if need_x:
-        # the same relational layer on the reversed graph with the transposed bases, un-normalised (one launch of the
-        # destination-major kernel where it applies: any output width that is a multiple of 4 up to 64)
-        dxe = torch.empty((n, fin), dtype=torch.float32, device=x.device)
-        bt = basis.transpose(1, 2)                                           # [B, fout, fin]: W_r^T = sum_b att[r,b] bt[b]
-        if rev.path(fout, fin, B) != "pair" and fout == 32 and fin % 32 != 0 and fin > 32:
-            # the LDS-resident kernel produces 32 output features: run it per 32-column block of W_r^T
-            # (the last block zero-padded) instead of falling back to the HBM-table path
-            for c0 in range(0, fin, 32):
-                w = min(32, fin - c0)
-                if w == 32:                                    # a full block: straight into its columns of dx
-                    rev.forward(gm, bt[:, :, c0:c0 + 32].contiguous(), att, None, None, False, dxe[:, c0:c0 + 32], partial=True)
-                    continue
-                blk = torch.zeros((B, fout, 32), dtype=torch.float32, device=x.device)
-                blk[:, :, :w] = bt[:, :, c0:c0 + w]
-                tmp = torch.empty((n, 32), dtype=torch.float32, device=x.device)
-                rev.forward(gm, blk, att, None, None, False, tmp, partial=True)
-                dxe[:, c0:c0 + w] = tmp[:, :w]
-        elif rev.path(fout, fin, B) == "pair" and basis.is_contiguous() and basis.data_ptr() % 16 == 0:
-            # (the destination-major kernel reads W_r^T out of the forward's own parameter: no transposed copy per step)
-            rev.forward(gm, basis, att, None, None, False, dxe, partial=True, basis_transposed=True)
-        else:
-            rev.forward(gm, bt.contiguous(), att, None, None, False, dxe, partial=True)
-    if need_basis or need_att:
-        # (HIP gather-reduce over (relation, source) rows, then library GEMMs; relation slabs when Q would be huge)
-        wg = plan.weight_grad_plan()
-        if wg is not None and x.stride(1) == 1 and gm.stride(1) == 1 and wg.supported(fin, fout):
-            dw = wg.weight_grad(x, gm)                                       # X^T Q_r in one launch, Q never in memory
-        elif x.stride(1) == 1 and gm.stride(1) == 1 and (dw_general := plan.general_weight_grad(x, gm)) is not None:
-            dw = dw_general                                                  # per relation x[src]^T gm[dst], O(E) memory, any size
-        elif R * n * fout <= Q_BUDGET_FLOATS:
-            q = torch.empty((R * n, fout), dtype=torch.float32, device=x.device)
-            pairs.aggregate(gm, None, False, q)
-            dw = torch.matmul(x.t(), q.view(R, n, fout)).reshape(R, fin * fout)            # [R, fin*fout]
-        else:
-            dw = _relation_slab_dw(plan, x, gm, R, n, fin, fout)
+    if route.dx is not None:
+        dxe = torch.empty((x.shape[0], fin), dtype=torch.float32, device=x.device)
+        _DX_ROUTES[route.dx](plan.reversed_plan(), gm, basis, att, dxe)
+    if route.dw is not None:
+        dw = _DW_ROUTES[route.dw](plan, x, gm)                               # [R, fin * fout]
         # dbasis = att^T dW, datt = dW basis^T (layers.py:172-173): deep, narrow products (gn_gemm_f32, operands as they are stored)
-        if need_basis:
-            if B <= 64:
-                dbasis = torch.empty((B, fin * fout), dtype=torch.float32, device=x.device)
-                _hip.gemm(att.contiguous(), dw, dbasis, a_transposed=True, join_batch=True)
-                dbasis = dbasis.view(B, fin, fout)
-            else:
-                dbasis = (att.t() @ dw).view(B, fin, fout)
+        if route.dbasis == "gemm":
+            dbasis = torch.empty((B, fin * fout), dtype=torch.float32, device=x.device)
+            _hip.gemm(att.contiguous(), dw, dbasis, a_transposed=True, join_batch=True)
+            dbasis = dbasis.view(B, fin, fout)
+        elif route.dbasis == "torch":
+            dbasis = (att.t() @ dw).view(B, fin, fout)
         if need_att:
-            datt = torch.empty((R, B), dtype=torch.float32, device=x.device)
+            datt = torch.empty((att.shape[0], B), dtype=torch.float32, device=x.device)
             _hip.gemm(dw, basis.reshape(B, fin * fout), datt, b_transposed=True, join_batch=True)
     return dxe, dbasis, datt
 
 
-def _relation_slab_dw(plan, x, gm, R, n, fin, fout):
+def rgcn_edge_route(plan, x, basis, att, gm, need_x=True, need_basis=True, need_att=True) -> RelBackwardRoute:
+    """The routes `rgcn_edge_gradients` takes for these operands, without running them (the plans it asks are built):
+    the answers gathered here, the decision in `relational_backward_route`."""
+    B, fin, fout = basis.shape
+    # the operands' properties and the library's answers, each asked once and only where the rules can come to read it
+    # (the general kernel only when the fused one is refused; per call: the answers depend on environment hooks)
+    rev_kernel = plan.reversed_plan().path(fout, fin, B) if need_x else None
+    unit_strides = x.stride(1) == 1 and gm.stride(1) == 1
+    fused_ok = general_ok = False
+    if need_basis or need_att:
+        wg = plan.weight_grad_plan()
+        fused_ok = wg is not None and unit_strides and wg.supported(fin, fout)
+        general_ok = unit_strides and not fused_ok and plan.general_weight_grad_supported(fin, fout)
+    return relational_backward_route(fin, fout, B, relations=att.shape[0], nodes=x.shape[0], q_budget=Q_BUDGET_FLOATS,
+                                     need_x=need_x, need_basis=need_basis, need_att=need_att, rev_kernel=rev_kernel,
+                                     basis_in_place=basis.is_contiguous() and basis.data_ptr() % 16 == 0,
+                                     unit_strides=unit_strides, fused_ok=fused_ok, general_ok=general_ok)
+
+
+# ---- dx: the same relational layer on the reversed graph with the transposed bases W_r^T = sum_b att[r,b] basis[b]^T, un-normalised ----
+def _dx_transposed(rev, gm, basis, att, dxe):
+    """One launch of the destination-major kernel, which reads W_r^T out of the forward's own parameter."""
+    rev.forward(gm, basis, att, None, None, False, dxe, partial=True, basis_transposed=True)
+
+
+def _dx_direct(rev, gm, basis, att, dxe):
+    """One launch of whichever kernel the reversed plan takes, on a transposed copy of the bases [B, fout, fin]."""
+    rev.forward(gm, basis.transpose(1, 2).contiguous(), att, None, None, False, dxe, partial=True)
+
+
+def _dx_blocks(rev, gm, basis, att, dxe):
+    """A launch per 32-column block of W_r^T, the last block zero-padded to 32 columns and copied out: the reversed layer
+    32 -> fin as ceil(fin / 32) layers 32 -> 32.  Written for the LDS-accumulator kernel, which produces 32 output
+    features; the rule that picks this route asks only that the kernel is not the destination-major one, so it runs on
+    the general O(E) kernel and on the table kernel as well, where one launch would do."""
+    B, fin, fout = basis.shape
+    bt = basis.transpose(1, 2)
+    for c0 in range(0, fin, 32):
+        w = min(32, fin - c0)
+        if w == 32:                                            # a full block: straight into its columns of dx
+            rev.forward(gm, bt[:, :, c0:c0 + 32].contiguous(), att, None, None, False, dxe[:, c0:c0 + 32], partial=True)
+            continue
+        blk = torch.zeros((B, fout, 32), dtype=torch.float32, device=gm.device)
+        blk[:, :, :w] = bt[:, :, c0:c0 + w]
+        tmp = torch.empty((dxe.shape[0], 32), dtype=torch.float32, device=gm.device)
+        rev.forward(gm, blk, att, None, None, False, tmp, partial=True)
+        dxe[:, c0:c0 + w] = tmp[:, :w]
+
+
+# ---- dw [R, fin * fout]: dW_r = X^T Q_r ----
+def _dw_fused(plan, x, gm):
+    """gn_rel_weight_grad_f32: X^T Q_r in one launch, Q never in memory."""
+    return plan.weight_grad_plan().weight_grad(x, gm)
+
+
+def _dw_general(plan, x, gm):
+    """gn_rgcn_weight_grad_f32: per relation x[src]^T gm[dst], O(E) memory, any number of nodes."""
+    return plan.general_weight_grad(x, gm, supported=True)
+
+
+def _dw_dense(plan, x, gm):
+    """Q by the HIP gather-reduce over (relation, source) rows, then one batched library product."""
+    R, n, fin, fout = plan.num_relations, x.shape[0], x.shape[1], gm.shape[1]
+    q = torch.empty((R * n, fout), dtype=torch.float32, device=x.device)
+    plan.pair_sums().aggregate(gm, None, False, q)
+    return torch.matmul(x.t(), q.view(R, n, fout)).reshape(R, fin * fout)
+
+
+def _dw_slabs(plan, x, gm):
     """dW_r = X^T Q_r without the dense [R n, fout] Q: relations in slabs whose Q fits the budget, each slab's
     (relation, source) sums scattered from its edge range (O(edges) memory, like the reference's per-relation loop)."""
+    R, n, fin, fout = plan.num_relations, x.shape[0], x.shape[1], gm.shape[1]
     ei, rl = plan._edge_index, plan._range_list
     dw = torch.zeros((R, fin * fout), dtype=torch.float32, device=x.device)
     slab = max(1, Q_BUDGET_FLOATS // max(1, n * fout))
@@ -295,6 +359,10 @@ def _relation_slab_dw(plan, x, gm, R, n, fin, fout):
         q.index_add_(0, rel * n + ei[0, lo:hi], gm.index_select(0, ei[1, lo:hi]))
         dw[r0:r1] = torch.matmul(x.t(), q.view(r1 - r0, n, fout)).reshape(r1 - r0, fin * fout)
     return dw
+
+
+_DX_ROUTES = {"transposed": _dx_transposed, "direct": _dx_direct, "blocks": _dx_blocks}
+_DW_ROUTES = {"fused": _dw_fused, "general": _dw_general, "dense": _dw_dense, "slabs": _dw_slabs}
 
 
 class DistMultFn(torch.autograd.Function):

@@ -100,7 +100,7 @@ class HipShardKernels:
         return c.basis, c.att, c.root, c.bias
 
     def in_degree(self):
-        return self.plan.grad_plans()[2]
+        return self.plan.in_degree()
 
     def score_edges(self, z, edge_index, sigmoid=True):
         """Scores of my edge range's relations on another edge list of the same length (negative samples)."""

@@ -1333,3 +1333,70 @@ def test_relational_layer_gradients_beyond_the_lds_kernels(gpu, n, fin, fout, ba
     parts = [_hip.RgcnPlan(eig, rl, n, lo, hi).general_weight_grad(xd, gm) for lo, hi in ((0, E // 3), (E // 3, E))]
     assert float(((parts[0] + parts[1]).double() - ref).abs().max()) <= 2e-6 * scale
     _hip.raise_if_index_errors(gpu)
+
+
+# entry points a call of rgcn_edge_gradients makes on each route: (gn_rgcn_forward_f32) for dx at a layer fin -> 32 or
+# fin -> fout, (gn_rel_weight_grad_f32, gn_rgcn_weight_grad_f32, gn_graph_aggregate_f32) for dW
+DX_LAUNCHES = {None: lambda fin: 0, "transposed": lambda fin: 1, "direct": lambda fin: 1, "blocks": lambda fin: (fin + 31) // 32}
+DW_LAUNCHES = {None: (0, 0, 0), "fused": (1, 0, 0), "general": (0, 1, 0), "dense": (0, 0, 1), "slabs": (0, 0, 0)}
+
+
+@pytest.mark.parametrize("case,n,fin,fout,bases,want", [
+    ("pose",          37,  32, 16, 4,  ("transposed", "fused", "gemm")),
+    ("basis-view",    37,  32, 16, 4,  ("direct", "fused", "gemm")),
+    ("no-fast",       100, 48, 32, 4,  ("blocks", "general", "gemm")),
+    ("strided-x",     300, 48, 32, 4,  (None, "dense", "gemm")),
+    ("strided-slabs", 300, 48, 32, 4,  (None, "slabs", "gemm")),
+    ("many-bases",    300, 48, 24, 80, (None, None, "torch")),
+])
+def test_relational_backward_takes_the_route_it_names(gpu, monkeypatch, case, n, fin, fout, bases, want):
+    """autograd.rgcn_edge_route names the route of a call, rgcn_edge_gradients makes exactly that route's launches (recorded
+    entry points: DX_LAUNCHES / DW_LAUNCHES; `want` holds the parts a case is built for, None: whatever is named), and the
+    three gradients match float64 index_add + matmul - dbasis and datt (sums over dW) within 2e-6 of their largest entry, dx
+    within 1e-4 of its largest entry."""
+    from gripnet_amd import autograd as ag
+    monkeypatch.setenv("GN_DISABLE_FAST", "1" if case == "no-fast" else "0")
+    if case == "strided-slabs":
+        monkeypatch.setattr(ag, "Q_BUDGET_FLOATS", 2 * n * fout)      # (two relations per slab)
+    gen = torch.Generator().manual_seed(n + fin + bases)
+    R, sizes = 6, [900, 0, 1, 300, 40, 120]
+    blocks = [torch.randint(0, n - n // 11, (2, s), generator=gen) for s in sizes]
+    ei = torch.cat(blocks, dim=1).to(gpu)
+    rl = gripnet_amd.utils.get_range_list(blocks)
+    x = torch.randn(n, 2 * fin, generator=gen).to(gpu)[:, ::2] if case.startswith("strided") else torch.randn(n, fin, generator=gen).to(gpu)
+    gm = torch.randn(n, fout, generator=gen).to(gpu)
+    att = (torch.randn(R, bases, generator=gen) * 0.2).to(gpu)
+    if case == "basis-view":                                               # [B, fin, fout] as a view of [B, fout, fin] storage
+        basis = (torch.randn(bases, fout, fin, generator=gen) * 0.1).to(gpu).transpose(1, 2)
+        assert not basis.is_contiguous()
+    else:
+        basis = (torch.randn(bases, fin, fout, generator=gen) * 0.1).to(gpu)
+    plan = _hip.RgcnPlan(ei, rl, n)
+    plan.in_degree()
+    assert plan._rev is None and plan._pairs is None                       # the divisor alone builds neither plan
+    route = ag.rgcn_edge_route(plan, x, basis, att, gm)
+    print("case {}: route {}".format(case, route))
+    assert all(w is None or w == got for w, got in zip(want, route)), (want, route)
+    with _hip.Recorder() as rec:
+        dx, dbasis, datt = ag.rgcn_edge_gradients(plan, x, basis, att, gm)
+    names = [name for _, _, name, _ in rec.calls]
+    assert names.count("gn_rgcn_forward_f32") == DX_LAUNCHES[route.dx](fin), names
+    assert tuple(names.count(e) for e in ("gn_rel_weight_grad_f32", "gn_rgcn_weight_grad_f32", "gn_graph_aggregate_f32")) == DW_LAUNCHES[route.dw], names
+    assert ag.rgcn_edge_route(plan, x, basis, att, gm) == route
+    # float64: dx[s] = sum_{e: src=s} gm[dst_e] W_{r(e)}^T;  dW_r = X^T Q_r;  dbasis = att^T dW;  datt = dW basis^T
+    xd, gd, bd, ad = x.double(), gm.double(), basis.double(), att.double()
+    rel = torch.repeat_interleave(torch.arange(R), torch.tensor(sizes)).to(gpu)
+    w = torch.einsum("rb,bio->rio", ad, bd)
+    dx_ref = torch.zeros(n, fin, dtype=torch.float64, device=gpu)
+    dx_ref.index_add_(0, ei[0], torch.bmm(gd[ei[1]].unsqueeze(1), w[rel].transpose(1, 2)).squeeze(1))
+    q = torch.zeros(R * n, fout, dtype=torch.float64, device=gpu)
+    q.index_add_(0, rel * n + ei[0], gd.index_select(0, ei[1]))
+    dw_ref = torch.matmul(xd.t(), q.view(R, n, fout)).reshape(R, fin * fout)
+    dbasis_ref = (ad.t() @ dw_ref).view(bases, fin, fout)
+    datt_ref = dw_ref @ bd.reshape(bases, fin * fout).t()
+    for name, got, ref in (("dbasis", dbasis, dbasis_ref), ("datt", datt, datt_ref)):
+        scale, err = float(ref.abs().max()), float((got.double() - ref).abs().max())
+        print("gradient {}: err {:.3e}, largest entry {:.3e}, allowed {:.3e}".format(name, err, scale, 2e-6 * scale))
+        assert got.shape == ref.shape and err <= 2e-6 * scale, (name, err, scale)
+    gclose(dx, dx_ref, 1e-4, what="dx", per_scale=True)
+    _hip.raise_if_index_errors(gpu)

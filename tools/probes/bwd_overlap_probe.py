@@ -60,7 +60,7 @@ print("decoder backward  positives {:.0f} us, negatives {:.0f} us, one after the
     clock(pos), clock(negs), clock(serial), clock(forked)))
 
 rp = _hip.RgcnPlan(d.train_idx, d.train_range, n)
-rev, pairs, deg = rp.grad_plans()
+rev = rp.reversed_plan()
 wg = rp.weight_grad_plan()
 x, gm = torch.randn(n, 48, device=dev), torch.randn(n, 32, device=dev)
 bt = (torch.randn(32, 32, 48, device=dev) * 0.1).contiguous()

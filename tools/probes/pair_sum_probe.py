@@ -10,7 +10,7 @@ from gripnet_amd.synth import make_pose
 dev = torch.device("cuda:0")
 d = make_pose(sys.argv[1] if len(sys.argv) > 1 else "pose0-syn").to(dev)
 plan = _hip.RgcnPlan(d.train_idx, d.train_range, d.n_d_node)
-rev, pairs, deg = plan.grad_plans()
+pairs = plan.pair_sums()
 torch.manual_seed(3)
 gm = torch.randn(d.n_d_node, 32, device=dev)
 q = torch.empty(d.n_dd_edge_type * d.n_d_node, 32, device=dev)

@@ -27,4 +27,6 @@ timed("  + blocked encoding (16 cols)", lambda: g.build_blocked(16))
 timed("bipartite plan (gd)", lambda: _hip.GraphPlan.bipartite(d.gd_edge_index, d.n_g_node, d.n_d_node, None))
 r = timed("relational plan (dd)", lambda: _hip.RgcnPlan(d.train_idx, d.train_range, d.n_d_node))
 timed("decoder plan (positives)", lambda: _hip.DistMultPlan(d.train_idx, d.train_et, d.n_d_node, d.n_dd_edge_type))
-timed("relational grad plans", lambda: r.grad_plans())
+timed("relational backward: in-degree", lambda: r.in_degree())
+timed("relational backward: reversed plan", lambda: r.reversed_plan())
+timed("relational backward: pair sums", lambda: r.pair_sums())

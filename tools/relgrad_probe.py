@@ -18,7 +18,7 @@ torch.manual_seed(3)
 x, gm = torch.randn(n, 48, device=dev), torch.randn(n, 32, device=dev)
 plan = _hip.RgcnPlan(d.train_idx, d.train_range, n)
 wg = plan.weight_grad_plan()
-pairs = plan.grad_plans()[1]
+pairs = plan.pair_sums()
 
 
 def clock(fn, reps=50):
