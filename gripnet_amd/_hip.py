@@ -22,14 +22,14 @@ _lib = None
 _lock = threading.Lock()
 
 GN_OK, GN_ERR_INVALID_ARG, GN_ERR_HIP, GN_ERR_INDEX_RANGE, GN_ERR_UNSUPPORTED, GN_ERR_EDGE_COUNT = range(6)
-GN_RGCN_PARTIAL, GN_RGCN_ARITH_FAST, GN_RGCN_BASIS_TRANSPOSED = 1, 4, 64        # flags of gn_rgcn_forward_f32
+GN_RGCN_PARTIAL, GN_RGCN_ARITH_FAST, GN_RGCN_BASIS_TRANSPOSED, GN_RGCN_SUM = 1, 4, 64, 128   # flags of gn_rgcn_forward_f32
 GN_RGCN_PATH_SHIFT = 8
 RGCN_PATHS = {"auto": 0, "pair": 1, "lds": 3, "general": 4, "table": 5}                  # kernel choice (tests, measurements)
 RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 167                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 168                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -83,6 +83,11 @@ SIGNATURES = {
     "gn_cast_bf16": (_int, [_p, _i64, _p, _i64, _i64, _i64, _p]),
     "gn_graph_aggregate_bf16": (_int, [_p, _p, _i64, _i64, _p, _int, _p, _i64, _p, _p]),
     "gn_rgcn_forward_f32": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _int, _int, _p, _i64, _p, _p, _p, _sz, _p]),
+    "gn_rgcn_plan_build_positions": (_int, [_p, _p, _p, _p]),
+    "gn_rgcn_weighted_supported": (_int, [_p, _i64, _i64, _i64]),
+    "gn_rgcn_weighted_workspace_bytes": (_sz, [_p, _i64, _i64, _i64]),
+    "gn_rgcn_forward_weighted_f32": (_int, [_p, _p, _i64, _i64, _p, _p, _i64, _p, _p, _i64, _int, _int, _p, _p, _i64, _p, _sz, _p]),
+    "gn_rgcn_weight_grad_weighted_f32": (_int, [_p, _p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _sz, _p]),
     "gn_rgcn_finalize_f32": (_int, [_p, _p, _i64, _p, _i64, _i64, _p, _p, _i64, _int, _p, _i64, _p, _p]),
     "gn_distmult_forward_f32": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _p, _i64, _i64, _i64, _int, _p, _p, _p]),
     "gn_distmult_packed_forward_f32": (_int, [_p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, _p, _p, _p]),
@@ -920,9 +925,10 @@ class RgcnPlan(Handle):
     """Owner of a gn_rgcn_plan handle (static multi-relational graph of one supervertex)."""
     _destroy = "gn_rgcn_plan_destroy"
 
-    def __init__(self, edge_index, range_list, num_nodes, edge_lo=None, edge_hi=None, light=False):
+    def __init__(self, edge_index, range_list, num_nodes, edge_lo=None, edge_hi=None, light=False, perm=None):
         """`light`: only what the general O(E) kernel reads (GN_RGCN_PLAN_LIGHT) - no host-built schedules: the plan of an edge
-        list that will not be seen again."""
+        list that will not be seen again.  `perm` ([E] int64, or None): the position of every listed edge in the caller's own
+        list, where `edge_index` is a type-sorted copy of it (RGCNConv): a weighted call reads the caller's factors through it."""
         load()
         require_gpu(edge_index)
         ei, src, dst, e = edge_rows(edge_index)
@@ -940,6 +946,7 @@ class RgcnPlan(Handle):
         self._ws = None
         self._edge_index, self._range_list, self._wgrad = ei, rl, None
         self._deg = self._rev = self._pairs = None
+        self._perm, self._has_pos = perm, False
 
     # What the backward pass needs of the graph, each part built on first use.  For a shard (edge_lo / edge_hi) the two plans
     # cover the shard's edges only - its share of the sums over edges - while the divisor is the in-degree over the FULL
@@ -956,7 +963,8 @@ class RgcnPlan(Handle):
     def reversed_plan(self):
         """The relational plan of the same edge positions with their endpoints swapped (dx is the layer on it)."""
         if self._rev is None:
-            self._rev = RgcnPlan(self._edge_index.flip(0).contiguous(), self._range_list, self.num_nodes, self.edge_lo, self.edge_hi)
+            self._rev = RgcnPlan(self._edge_index.flip(0).contiguous(), self._range_list, self.num_nodes, self.edge_lo, self.edge_hi,
+                                 perm=self._perm)           # (the same edge positions: the same permutation)
         return self._rev
 
     def pair_sums(self):
@@ -981,9 +989,10 @@ class RgcnPlan(Handle):
     def general_weight_grad_supported(self, fin, fout) -> bool:
         return bool(load().gn_rgcn_weight_grad_supported(self._h, int(fin), int(fout)))
 
-    def general_weight_grad(self, x, gm, supported=None):
+    def general_weight_grad(self, x, gm, supported=None, edge_weight=None):
         """dw [R, fin * fout] = sum over each relation's edges of x[src]^T gm[dst] on gn_rgcn_weight_grad_f32 (any number of
-        nodes), or None where it does not cover the shapes (`supported`: that answer, from a caller that has asked)."""
+        nodes), or None where it does not cover the shapes (`supported`: that answer, from a caller that has asked).
+        `edge_weight` ([E] fp32 in the order of the plan's own list): every edge's term times its factor."""
         fin, fout = x.shape[1], gm.shape[1]
         lib = load()
         if not (self.general_weight_grad_supported(fin, fout) if supported is None else supported):
@@ -993,8 +1002,12 @@ class RgcnPlan(Handle):
         need = int(lib.gn_rgcn_weight_grad_workspace_bytes(self._h, fin, fout))
         ws = torch.empty((need,), dtype=torch.uint8, device=x.device)
         base = ei.data_ptr()
-        _call("gn_rgcn_weight_grad_f32", self._h, base, base + 8 * self.num_edges, ptr(x), ld(x), fin, ptr(gm), ld(gm), fout, ptr(dw),
-              ptr(ws), need, stream_ptr(x.device))
+        if edge_weight is None:
+            _call("gn_rgcn_weight_grad_f32", self._h, base, base + 8 * self.num_edges, ptr(x), ld(x), fin, ptr(gm), ld(gm), fout, ptr(dw),
+                  ptr(ws), need, stream_ptr(x.device))
+        else:
+            _call("gn_rgcn_weight_grad_weighted_f32", self._h, base, base + 8 * self.num_edges, ptr(edge_weight), ptr(x), ld(x), fin,
+                  ptr(gm), ld(gm), fout, ptr(dw), ptr(ws), need, stream_ptr(x.device))
         if _recorder is not None:
             _recorder.keep.append(ei)
         return dw
@@ -1020,12 +1033,37 @@ class RgcnPlan(Handle):
             code = int(load().gn_rgcn_forward_path(self._h, fin, fout, bases, self.mode_flags(fast, path)))
         return RGCN_PATH_NAMES.get(code, "?")
 
+    def weighted_supported(self, fin, fout, bases) -> bool:
+        return bool(load().gn_rgcn_weighted_supported(self._h, int(fin), int(fout), int(bases)))
+
+    def build_positions(self):
+        """The position list of the weighted calls (4 bytes per edge, built on the device; it synchronises the stream once)."""
+        if not self._has_pos:
+            ei = self._edge_index
+            with torch.cuda.device(self.device):
+                check(load().gn_rgcn_plan_build_positions(self._h, ei.data_ptr() + 8 * self.num_edges, ptr(self._perm), stream_ptr(self.device)))
+            self._has_pos = True
+        return self
+
+    def forward_weighted(self, x, basis, att, root, bias, relu, out, edge_weight, partial=False):
+        """The sum (or, `partial`, the bare edge sums) with the factor `edge_weight[e]` on every message: [E] fp32 in the
+        caller's order (the order `perm` maps to), read through the position list.  General kernel only."""
+        fin, fout, bases = x.shape[1], basis.shape[2], basis.shape[0]
+        self.build_positions()
+        need = int(load().gn_rgcn_weighted_workspace_bytes(self._h, fin, fout, bases))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
+        _call("gn_rgcn_forward_weighted_f32", self._h, ptr(x), ld(x), fin, ptr(basis), ptr(att), bases, ptr(root), ptr(bias), fout,
+              int(bool(relu)), GN_RGCN_PARTIAL if partial else GN_RGCN_SUM, ptr(edge_weight), ptr(out), ld(out), ptr(self._ws), need,
+              stream_ptr(x.device))
+        return out
+
     def forward(self, x, basis, att, root, bias, relu, out, partial=False, side=None, fast=False, path="auto", x_planes=None,
-                basis_transposed=False):
+                basis_transposed=False, sum_edges=False):
         """`x_planes`: SplitPlanes of x left by its producer (the destination-major kernel then skips its own split of x;
         the other kernels ignore them).  `basis_transposed`: `basis` is [bases, out, in] (the forward's parameter seen from
         the reversed layer of its backward; destination-major kernel only: GN_RGCN_BASIS_TRANSPOSED)."""
-        mode = self.mode_flags(fast, path)
+        mode = self.mode_flags(fast, path) | (GN_RGCN_SUM if sum_edges else 0)    # (sum_edges: GN_RGCN_SUM - no divisor, root may be None)
         fout = basis.shape[1] if basis_transposed else basis.shape[2]
         ws, need = self._workspace(x, x.shape[1], fout, basis.shape[0], mode)
         sc = side_copy(side)

@@ -365,6 +365,114 @@ _DX_ROUTES = {"transposed": _dx_transposed, "direct": _dx_direct, "blocks": _dx_
 _DW_ROUTES = {"fused": _dw_fused, "general": _dw_general, "dense": _dw_dense, "slabs": _dw_slabs}
 
 
+# ---- the relational SUM with an optional per-edge factor (RGCNConv of torch_geometric 1.4 / 1.5) ----
+RelSumRoute = namedtuple("RelSumRoute", "forward backward")
+
+
+def relational_sum_route(weighted: bool) -> RelSumRoute:
+    """Which functions serve a call of RgcnSumConvFn: with `edge_norm` the weighted instantiation of the general kernel,
+    forward and backward; without it the unweighted sum (GN_RGCN_SUM) and the relational layer's own backward routes -
+    no [E] vector of ones exists on that side.  Plain values only."""
+    return RelSumRoute("weighted", "weighted") if weighted else RelSumRoute("plain", "plain")
+
+
+def _sum_forward_plain(plan, x, basis, att, root, bias, relu, out, w):
+    """GN_RGCN_SUM: the general kernel's slab product (or the table kernel's gather) without the divisor."""
+    plan.forward(x, basis, att, root, bias, relu, out, sum_edges=True)
+
+
+def _sum_forward_weighted(plan, x, basis, att, root, bias, relu, out, w):
+    """The weighted instantiation: att[r(e), b] * w_e on the A operand, w read in the caller's order."""
+    plan.forward_weighted(x, basis, att, root, bias, relu, out, w)
+
+
+def _sum_backward_plain(plan, x, basis, att, gm, w, w_sorted, need_x, need_basis, need_att):
+    return rgcn_edge_gradients(plan, x, basis, att, gm, need_x, need_basis, need_att)
+
+
+def dw_column_blocks(fin: int, fout: int):
+    """Column blocks [lo, hi) of gm that gn_rgcn_weight_grad_f32 takes for `fin` input features: 16 ceil(fin / 16) / 16 tiles of
+    rows leave room for 16 / that many tiles of columns (at most four)."""
+    width = 16 * max(1, min(4, 16 // -(-fin // 16)))
+    return [(lo, min(fout, lo + width)) for lo in range(0, fout, width)]
+
+
+def _sum_backward_weighted(plan, x, basis, att, gm, w, w_sorted, need_x, need_basis, need_att):
+    """dx: the weighted kernel on the reversed plan with the transposed bases (the same edge positions, so the same factors
+    through the reversed plan's own position list); dW_r = sum_{e in r} w_e x[src_e]^T gm[dst_e] on the general weight-gradient
+    kernel, which walks the type-sorted list (w_sorted), a launch per block of output columns it takes."""
+    B, fin, fout = basis.shape
+    dxe = dbasis = datt = None
+    if need_x:
+        dxe = torch.empty((x.shape[0], fin), dtype=torch.float32, device=x.device)
+        plan.reversed_plan().forward_weighted(gm, basis.transpose(1, 2).contiguous(), att, None, None, False, dxe, w, partial=True)
+    if need_basis or need_att:
+        blocks = dw_column_blocks(fin, fout)
+        if len(blocks) == 1:
+            dw = plan.general_weight_grad(x, gm, edge_weight=w_sorted)
+        else:
+            dw = torch.empty((att.shape[0], fin, fout), dtype=torch.float32, device=x.device)
+            for lo, hi in blocks:
+                part = plan.general_weight_grad(x, gm[:, lo:hi], edge_weight=w_sorted)
+                if part is None:
+                    dw = None
+                    break
+                dw[:, :, lo:hi] = part.view(att.shape[0], fin, hi - lo)
+            dw = None if dw is None else dw.view(att.shape[0], fin * fout)
+        if dw is None:
+            raise ValueError("RGCNConv: the weighted weight gradient does not cover this graph (a relation of more than 65,535 x 512 edges)")
+        if need_basis:
+            dbasis = torch.empty((B, fin * fout), dtype=torch.float32, device=x.device)
+            _hip.gemm(att.contiguous(), dw, dbasis, a_transposed=True, join_batch=True)
+            dbasis = dbasis.view(B, fin, fout)
+        if need_att:
+            datt = torch.empty((att.shape[0], B), dtype=torch.float32, device=x.device)
+            _hip.gemm(dw, basis.reshape(B, fin * fout), datt, b_transposed=True, join_batch=True)
+    return dxe, dbasis, datt
+
+
+_SUM_FORWARD = {"plain": _sum_forward_plain, "weighted": _sum_forward_weighted}
+_SUM_BACKWARD = {"plain": _sum_backward_plain, "weighted": _sum_backward_weighted}
+
+
+class RgcnSumConvFn(torch.autograd.Function):
+    """``act(sum_{e: dst=i} w_e x[src_e] W_{r(e)} (+ x[i] root) (+ b))`` (RGCNConv.forward of torch_geometric 1.4 / 1.5 as
+    baselines/NC_baselines/RGCN_MLP.py:62-63 calls it, with the ReLU that follows).  `plan`: the RgcnPlan of the type-sorted
+    list; `w`: edge_norm in the caller's order or None; `w_sorted`: the same factors in the plan's order."""
+
+    @staticmethod
+    def forward(ctx, x, basis, att, root, bias, plan, w, w_sorted, relu):
+        ctx.set_materialize_grads(False)
+        xc = _hip.f32_rows(x.detach())
+        route = relational_sum_route(w is not None)
+        out = torch.empty((xc.shape[0], basis.shape[2]), dtype=torch.float32, device=xc.device)
+        _SUM_FORWARD[route.forward](plan, xc, basis.detach(), att.detach(), None if root is None else root.detach(),
+                                    None if bias is None else bias.detach(), relu, out, w)
+        ctx.plan, ctx.relu, ctx.route, ctx.has_bias = plan, bool(relu), route, bias is not None
+        ctx.save_for_backward(xc, basis, att, root, w, w_sorted, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, basis, att, root, w, w_sorted, out = ctx.saved_tensors
+        if g is None:
+            return (None,) * 9
+        need = ctx.needs_input_grad
+        need_db = ctx.has_bias and need[4]
+        if ctx.relu or need_db or g.dtype != torch.float32 or g.stride(1) != 1:
+            gm, _, dbias = _hip.grad_prologue(g, out if ctx.relu else None, None, True, need_db)   # ReLU mask by the saved output, column sums
+        else:
+            gm, dbias = _hip.f32_rows(g), None
+        with _hip.dense_batch(x.device):
+            dxe, dbasis, datt = _SUM_BACKWARD[ctx.route.backward](ctx.plan, x, basis.detach(), att.detach(), gm, w, w_sorted,
+                                                                  need[0], need[1], need[2])
+            dx = dxe
+            if need[0] and root is not None:                      # dx = the edge sums + gm root^T, added onto them
+                dx = _hip.gemm(gm, root.detach(), dxe, b_transposed=True, accumulate=True, join_batch=True)
+            droot = _hip.xtg(x, gm, join_batch=True) if root is not None and need[3] else None
+        return dx, dbasis, datt, droot, dbias, None, None, None, None
+
+
 class DistMultFn(torch.autograd.Function):
     """``sigma?(sum_k z[u,k] z[v,k] D[r,k])`` (decoder.py:19-23) with the scatter gradients in HIP."""
 

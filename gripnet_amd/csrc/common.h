@@ -276,6 +276,8 @@ struct gn_rgcn_plan {
     gn::DevBuf<uint32_t> key;      // [shard_edges]
     gn::DevBuf<int32_t> row_order; // [N] destination rows by the shard's in-degree, largest first (rgcn_basis.hip deals rows in this order)
     int64_t heavy_rows = 0;        // rows of more than gn_layout::kBasisHeavyEdges edges (the first entries of row_order)
+    gn::DevBuf<int32_t> pos;       // [shard_edges] of every key: its edge's position in the caller's own list (weighted calls only:
+    int has_pos = 0;               // gn_rgcn_plan_build_positions, on first use)
     // relation-major work items of the general weight gradient (rgcn_basis.hip): (relation, first edge, end edge, part | parts << 16)
     // over the shard's edges in the caller's (type-sorted) order, <= gn_layout::kRelDwItemEdges edges each
     gn::DevBuf<int32_t> dw_items;  // [n_dw_items][4]

@@ -342,6 +342,28 @@ __global__ void k_rel_keys(const int64_t* __restrict__ src, const int64_t* __res
     }
 }
 
+// dst32[e] = dst[lo + e], iota[e] = e  (the position list's sort input)
+__global__ void k_pos_input(const int64_t* __restrict__ dst, int64_t lo, int64_t n, int64_t N, int32_t* __restrict__ dst32,
+                            int32_t* __restrict__ iota, int32_t* __restrict__ err) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        int64_t d = dst[lo + e];
+        if ((uint64_t)d >= (uint64_t)N) { atomicOr(err, 1); d = 0; }
+        dst32[e] = (int32_t)d;
+        iota[e] = (int32_t)e;
+    }
+}
+
+// pos[p] = perm[lo + at[p]] (the caller's own position of the listed edge), or lo + at[p] without a permutation
+__global__ void k_pos_compose(const int32_t* __restrict__ at, const int64_t* __restrict__ perm, int64_t lo, int64_t n, int64_t E,
+                              int32_t* __restrict__ pos, int32_t* __restrict__ err) {
+    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        int64_t v = lo + at[p];
+        if (perm) v = perm[v];
+        if ((uint64_t)v >= (uint64_t)E) { atomicOr(err, 2); v = 0; }
+        pos[p] = (int32_t)v;
+    }
+}
+
 }  // namespace
 
 // Implemented in rgcn_fast.hip: relation-major segments for the LDS-resident path.
@@ -566,6 +588,39 @@ gn_status gn_rgcn_plan_create_ex(const int64_t* src, const int64_t* dst, const i
         GN_LAP("rgcn: destination-major units (total)");
     }
     *out = p.release();
+    return GN_OK;
+}
+
+// The position list of a weighted call: the same stable sort by destination that ordered the keys, carrying the listed edges'
+// own indices (then through `perm` to the caller's order) - 4 bytes per key, built once, never for a plan without weighted calls.
+gn_status gn_rgcn_plan_build_positions(gn_rgcn_plan* plan, const int64_t* dst, const int64_t* perm, void* stream) {
+    GN_REQUIRE(plan != nullptr, "plan is null");
+    if (plan->has_pos) return GN_OK;
+    const int64_t n = plan->shard_edges, N = plan->num_nodes;
+    if (n == 0) { plan->has_pos = 1; return GN_OK; }
+    GN_REQUIRE(dst != nullptr, "dst is null");
+    hipStream_t st = gn::as_stream(stream);
+    Temp tmp;
+    int32_t *dst32, *sorted_dst, *iota, *at, *err;
+    GN_HIP(tmp.get(&dst32, n));
+    GN_HIP(tmp.get(&sorted_dst, n));
+    GN_HIP(tmp.get(&iota, n));
+    GN_HIP(tmp.get(&at, n));
+    GN_HIP(tmp.get(&err, 1));
+    GN_HIP(hipMemsetAsync(err, 0, sizeof(int32_t), st));
+    gn::DevBuf<int32_t> pos;
+    GN_HIP(pos.alloc(n));
+    k_pos_input<<<gn::stream_grid(n, 256), 256, 0, st>>>(dst, plan->edge_lo, n, N, dst32, iota, err);
+    GN_LAUNCH_CHECK();
+    GN_OK_OR_RETURN(gn::sort_pairs(tmp, dst32, sorted_dst, iota, at, (size_t)n, bits_for(N), st));
+    k_pos_compose<<<gn::stream_grid(n, 256), 256, 0, st>>>(at, perm, plan->edge_lo, n, plan->input_edges, pos.p, err);
+    GN_LAUNCH_CHECK();
+    int32_t bad = 0;
+    GN_HIP(hipMemcpyAsync(&bad, err, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    GN_HIP(hipStreamSynchronize(st));                      // (scratch is freed on return)
+    if (bad) return gn::fail(GN_ERR_INDEX_RANGE, "position list: %s", (bad & 1) ? "dst holds a node id outside the plan's nodes" : "perm holds a position outside [0, E)");
+    plan->pos = std::move(pos);
+    plan->has_pos = 1;
     return GN_OK;
 }
 

@@ -31,12 +31,12 @@ gn_status gn_rgcn_fast_finalize(const gn_rgcn_plan* plan, const float* summed, c
                                 const gn_side_copy& side, hipStream_t st);
 
 // rgcn_basis.hip
-bool gn_rgcn_basis_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases);
+bool gn_rgcn_basis_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases, bool sum = false);
 size_t gn_rgcn_basis_workspace_bytes(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases);
 gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* basis,
                                 const float* att, int64_t bases, const float* root, const float* bias, int64_t fout, int relu,
                                 int partial, int fast_arith, float* out, int64_t ld_out, const gn_side_copy& side, void* ws,
-                                size_t ws_bytes, hipStream_t st);
+                                size_t ws_bytes, hipStream_t st, int sum = 0, const float* edge_weight = nullptr);
 
 namespace {
 
@@ -48,6 +48,8 @@ size_t align_up(size_t v) { return (v + 255) & ~size_t(255); }
 int select_path(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases, int flags, const void* basis,
                 const float* x = nullptr, int64_t ld_x = 0) {
     const int forced = (flags >> GN_RGCN_PATH_SHIFT) & 7;
+    if (flags & GN_RGCN_SUM)                               // the sum's epilogue lives in the general kernel's slab product and in the table kernel's gather
+        return (forced != GN_RGCN_PATH_TABLE && gn_rgcn_basis_applicable(plan, fin, fout, bases, true)) ? GN_RGCN_PATH_GENERAL : GN_RGCN_PATH_TABLE;
     const bool pair_ok = gn_rgcn_pair_applicable(plan, fin, fout, bases) && (reinterpret_cast<uintptr_t>(basis) & 15) == 0;
     const bool lds_ok = gn_rgcn_fast_applicable(plan, fin, fout, bases) &&
                         (!x || (ld_x % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0));    // (16-byte row loads)
@@ -130,11 +132,14 @@ gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, int64_t 
     const int partial = flags & GN_RGCN_PARTIAL;
     GN_REQUIRE(plan != nullptr, "plan is null");
     GN_REQUIRE(fin > 0 && fout > 0 && bases > 0, "feature / basis counts must be positive");
-    GN_REQUIRE((flags & ~(GN_RGCN_PARTIAL | GN_RGCN_ARITH_FAST | GN_RGCN_BASIS_TRANSPOSED | (7 << GN_RGCN_PATH_SHIFT))) == 0,
+    GN_REQUIRE((flags & ~(GN_RGCN_PARTIAL | GN_RGCN_ARITH_FAST | GN_RGCN_BASIS_TRANSPOSED | GN_RGCN_SUM | (7 << GN_RGCN_PATH_SHIFT))) == 0,
                "flags 0x%x: bits this entry point does not define", flags);
+    const int sum = (flags & GN_RGCN_SUM) ? 1 : 0;
+    GN_REQUIRE(!(sum && partial), "GN_RGCN_SUM and GN_RGCN_PARTIAL exclude each other");
+    GN_REQUIRE(!sum || !side || !side->dst, "GN_RGCN_SUM takes no side copy");
     const int64_t N = plan->num_nodes, R = plan->num_relations;
     if (N == 0) return GN_OK;
-    GN_REQUIRE(x && basis && att && out && (partial || root), "operand pointer is null");
+    GN_REQUIRE(x && basis && att && out && (partial || sum || root), "operand pointer is null");
     GN_REQUIRE(ld_x >= fin && ld_out >= fout, "leading dimension smaller than the row length");
     // the workspace is checked against the kernel THIS call takes (a forced general or table path, or a basis pointer the
     // destination-major kernel cannot use, needs its own scratch whatever gn_rgcn_workspace_bytes said for the
@@ -158,7 +163,7 @@ gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, int64_t 
                                     out, ld_out, sc, workspace, workspace_bytes, st);
     if (path == GN_RGCN_PATH_GENERAL)
         return gn_rgcn_basis_forward(plan, x, ld_x, fin, basis, att, bases, root, bias, fout, relu, partial,
-                                     flags & GN_RGCN_ARITH_FAST, out, ld_out, sc, workspace, workspace_bytes, st);
+                                     flags & GN_RGCN_ARITH_FAST, out, ld_out, sc, workspace, workspace_bytes, st, sum);
 
     const GeneralWs l = general_layout(plan, fin, fout);
     char* ws = static_cast<char*>(workspace);
@@ -178,7 +183,8 @@ gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, int64_t 
             if (s != GN_OK) return s;
         }
     }
-    if (!partial) {
+    const bool with_root = !partial && root != nullptr;
+    if (with_root) {
         // K12: x @ root (+ bias) goes in as the addend of the gather epilogue (layers.py:193-196)
         s = gn_gemm_f32(x, ld_x, 0, nullptr, 0, root, fout, 0, XR, fout, 0, N, fout, fin, 1, bias, 0, stream);
         if (s != GN_OK) return s;
@@ -190,16 +196,46 @@ gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, int64_t 
     a.table = H;
     a.ld_table = fout;
     a.features = (int)fout;
-    a.rowdiv = partial ? nullptr : plan->indeg.p;
-    a.addend = partial ? nullptr : XR;
+    a.rowdiv = (partial || sum) ? nullptr : plan->indeg.p;
+    a.addend = with_root ? XR : nullptr;
     a.ld_addend = fout;
-    a.bias = nullptr;
+    a.bias = (!partial && !with_root) ? bias : nullptr;    // (the sum without a root term: the bias rides in the gather's epilogue)
     a.relu = partial ? 0 : relu;
     a.out = out;
     a.ld_out = ld_out;
     a.rows = (int)N;
     a.side = sc;
     return gn::launch_aggregate(a, st);
+}
+
+int gn_rgcn_weighted_supported(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
+    return gn_rgcn_basis_applicable(plan, fin, fout, bases, true) ? 1 : 0;
+}
+
+size_t gn_rgcn_weighted_workspace_bytes(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
+    return gn_rgcn_weighted_supported(plan, fin, fout, bases) ? gn_rgcn_basis_workspace_bytes(plan, fin, fout, bases) : 0;
+}
+
+gn_status gn_rgcn_forward_weighted_f32(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* basis,
+                                       const float* att, int64_t bases, const float* root, const float* bias, int64_t fout,
+                                       int relu, int flags, const float* edge_weight, float* out, int64_t ld_out, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    GN_REQUIRE(plan != nullptr, "plan is null");
+    GN_REQUIRE(fin > 0 && fout > 0 && bases > 0, "feature / basis counts must be positive");
+    GN_REQUIRE(flags == GN_RGCN_SUM || flags == GN_RGCN_PARTIAL, "flags 0x%x: a weighted call is GN_RGCN_SUM or GN_RGCN_PARTIAL", flags);
+    if (!gn_rgcn_weighted_supported(plan, fin, fout, bases))
+        return gn::fail(GN_ERR_UNSUPPORTED, "the weighted relational layer covers up to 64 bases and 128 input features");
+    if (plan->num_nodes == 0) return GN_OK;
+    GN_REQUIRE(x && basis && att && out, "operand pointer is null");
+    GN_REQUIRE(edge_weight || plan->shard_edges == 0, "edge_weight is null");
+    GN_REQUIRE(plan->has_pos || plan->shard_edges == 0, "the plan has no position list: call gn_rgcn_plan_build_positions first");
+    GN_REQUIRE(ld_x >= fin && ld_out >= fout, "leading dimension smaller than the row length");
+    const size_t need = gn_rgcn_basis_workspace_bytes(plan, fin, fout, bases);
+    GN_REQUIRE(workspace && workspace_bytes >= need, "workspace too small: this call needs %zu bytes, got %zu", need, workspace_bytes);
+    const int partial = flags & GN_RGCN_PARTIAL;
+    return gn_rgcn_basis_forward(plan, x, ld_x, fin, basis, att, bases, root, bias, fout, relu, partial, 0, out, ld_out,
+                                 gn_side_copy{nullptr, 0, nullptr, 0, 0, 0, 0}, workspace, workspace_bytes, gn::as_stream(stream),
+                                 partial ? 0 : 1, plan->shard_edges > 0 ? edge_weight : nullptr);
 }
 
 gn_status gn_rgcn_finalize_f32(const gn_rgcn_plan* plan, const float* summed, int64_t ld_summed, const float* x,

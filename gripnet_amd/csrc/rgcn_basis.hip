@@ -28,6 +28,7 @@ __device__ __forceinline__ f32x4 basis_mfma(float a, float b, f32x4 c) { return 
 
 constexpr int kBasisThreads = 512, kBasisWaves = kBasisThreads / 64;   // eight waves: a destination row per wave at a time, or a heavy row per workgroup
 constexpr int kHeavyEdges = gn_layout::kBasisHeavyEdges;               // rows with more incoming edges are walked by a whole workgroup
+constexpr int kBasisTiles = 16, kBasisTilesSum = 32;                   // accumulator tiles (16 bases x 16 features) of a row: the mean's kernels; the sum's and the weighted ones (64 bases x 128 features)
 constexpr int64_t kSlabBytes = 256ll << 20;        // rows of U in flight between the gather and the dense product (round 6: 64 MB cut the all-nodes
                                                    // baseline's first layer - 19,726 rows of 4.3 KB - into two slabs: two gather launches that each
                                                    // drew every work item of all rows, two products)
@@ -47,11 +48,13 @@ struct BasisArgs {
     int n_heavy;                                   // rows of more than kHeavyEdges edges: the first entries of `order`
     unsigned int* next_item;                       // this launch's work counter (zeroed by k_basis_weights)
     gn_side_copy side;
+    const int32_t* pos; const float* ew;           // (weighted instantiation) w_e = ew[pos[p]] of the key at p: the caller's [E] factors, in the caller's order
 };
 
 // One chunk of up to 64 edges, any shape: lane L holds edge L's (source, relation); step j contracts edges 4 j + kg.
-template <int BT, int NT>
-__device__ __forceinline__ void chunk_any(const BasisArgs& a, f32x4 (&acc)[BT][NT], uint32_t src, uint32_t rel, int cnt, int c, int kg) {
+// WT: lane L also holds edge L's factor w; it multiplies the A operand, att[r(e), b] * w_e - one multiply per edge and base tile.
+template <int BT, int NT, bool WT>
+__device__ __forceinline__ void chunk_any(const BasisArgs& a, f32x4 (&acc)[BT][NT], uint32_t src, uint32_t rel, float w, int cnt, int c, int kg) {
     const int steps = (cnt + 3) >> 2;
     for (int j0 = 0; j0 < steps; j0 += 4) {
         float av[4][BT], xv[4][NT];
@@ -66,6 +69,11 @@ __device__ __forceinline__ void chunk_any(const BasisArgs& a, f32x4 (&acc)[BT][N
             for (int t = 0; t < NT; ++t) xv[q][t] = (live && NT * c + t < a.fin) ? xr[t] : 0.f;
 #pragma unroll
             for (int jm = 0; jm < BT; ++jm) av[q][jm] = (live && 16 * jm + c < a.bases) ? ar[16 * jm] : 0.f;
+            if constexpr (WT) {
+                const float wq = __shfl(w, sel & 63);
+#pragma unroll
+                for (int jm = 0; jm < BT; ++jm) av[q][jm] *= wq;
+            }
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q)
@@ -81,8 +89,8 @@ __device__ __forceinline__ void chunk_any(const BasisArgs& a, f32x4 (&acc)[BT][N
 // lane L turns its edge into two 32-bit byte offsets once; a step is two ds_bpermute (the offsets of lane group kg's edge,
 // lane and step folded into the instruction's immediate), two adds of this lane's column offset, the loads in the
 // scalar-base form and the matrix instructions - sixteen steps unrolled, four steps' loads requested together.
-template <int BT, int NT>
-__device__ __forceinline__ void chunk_full(const BasisArgs& a, f32x4 (&acc)[BT][NT], uint32_t xo, uint32_t ao, uint32_t sel0,
+template <int BT, int NT, bool WT>
+__device__ __forceinline__ void chunk_full(const BasisArgs& a, f32x4 (&acc)[BT][NT], uint32_t xo, uint32_t ao, float w, uint32_t sel0,
                                            uint32_t lane_x, const uint32_t (&lane_a)[BT], const bool (&base_ok)[BT]) {
     const char* __restrict__ xb = reinterpret_cast<const char*>(a.x);
     const char* __restrict__ ab = reinterpret_cast<const char*>(a.att);
@@ -120,6 +128,11 @@ __device__ __forceinline__ void chunk_full(const BasisArgs& a, f32x4 (&acc)[BT][
                 const float v = *reinterpret_cast<const float*>(ab + (as + lane_a[jm]));
                 av[q][jm] = base_ok[jm] ? v : 0.f;
             }
+            if constexpr (WT) {
+                const float wq = __int_as_float(__builtin_amdgcn_ds_bpermute((int)addr, __float_as_int(w)));
+#pragma unroll
+                for (int jm = 0; jm < BT; ++jm) av[q][jm] *= wq;
+            }
         }
 #pragma unroll
         for (int q = 0; q < G; ++q)
@@ -132,7 +145,7 @@ __device__ __forceinline__ void chunk_full(const BasisArgs& a, f32x4 (&acc)[BT][
 }
 
 // acc += sum over the edges of chunks first, first + step, ... (64 edges each) of [e0, e1): K = four edges per instruction
-template <int BT, int NT>
+template <int BT, int NT, bool WT>
 __device__ __forceinline__ void accumulate_chunks(const BasisArgs& a, f32x4 (&acc)[BT][NT], int e0, int e1, int first, int step, int lane,
                                                   int c, int kg) {
     const uint32_t lane_x = (uint32_t)(NT * c) * 4u, sel0 = (uint32_t)kg * 4u;
@@ -146,14 +159,18 @@ __device__ __forceinline__ void accumulate_chunks(const BasisArgs& a, f32x4 (&ac
     const uint32_t ldx4 = (uint32_t)a.ld_x * 4u, b4 = (uint32_t)a.bases * 4u;
     int eb = e0 + 64 * first;
     uint32_t k_next = (eb < e1 && eb + lane < e1) ? a.key[eb + lane] : 0u;
+    float w_next = 0.f;
+    if constexpr (WT) w_next = (eb < e1 && eb + lane < e1) ? a.ew[a.pos[eb + lane]] : 0.f;
     for (; eb < e1; eb += 64 * step) {
         const int cnt = min(64, e1 - eb);
         const uint32_t k = k_next;
+        const float w = w_next;
         const int en = eb + 64 * step + lane;                                  // the next chunk's keys travel while this one is contracted
         k_next = en < e1 ? a.key[en] : 0u;
+        if constexpr (WT) w_next = en < e1 ? a.ew[a.pos[en]] : 0.f;            // (and its factors, through the position list)
         const uint32_t rel = k / a.n, src = k - rel * a.n;                     // (one division per lane and 64 edges)
-        if (cnt == 64 && a.fast_addr) chunk_full<BT, NT>(a, acc, src * ldx4, rel * b4, sel0, lane_x, lane_a, base_ok);
-        else chunk_any<BT, NT>(a, acc, src, rel, cnt, c, kg);
+        if (cnt == 64 && a.fast_addr) chunk_full<BT, NT, WT>(a, acc, src * ldx4, rel * b4, w, sel0, lane_x, lane_a, base_ok);
+        else chunk_any<BT, NT, WT>(a, acc, src, rel, w, cnt, c, kg);
     }
 }
 
@@ -165,7 +182,7 @@ __device__ __forceinline__ void write_tail(const BasisArgs& a, float* __restrict
     for (int col = tail + (a.with_x ? a.fin : 0) + lane; col < a.kp; col += 64) ur[col] = 0.f;
 }
 
-template <int BT, int NT>
+template <int BT, int NT, bool WT>
 __global__ __launch_bounds__(kBasisThreads) void k_rgcn_basis(BasisArgs a) {
     __shared__ f32x4 red[kBasisWaves][64];                                     // one accumulator tile of every wave (heavy rows)
     if (a.side.dst) {                                                          // concat slot 0 (layers.py:264-266), by the whole grid
@@ -203,7 +220,7 @@ __global__ __launch_bounds__(kBasisThreads) void k_rgcn_basis(BasisArgs a) {
             for (int jm = 0; jm < BT; ++jm)
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[jm][t] = (f32x4)(0.f);
-            accumulate_chunks<BT, NT>(a, acc, e0, e1, wv, kBasisWaves, lane, c, kg);
+            accumulate_chunks<BT, NT, WT>(a, acc, e0, e1, wv, kBasisWaves, lane, c, kg);
             const float inv = a.scale ? 1.0f / fmaxf(a.indeg[row], 1.0f) : 1.0f;
             float* __restrict__ ur = a.u + (size_t)(row - a.row_lo) * a.ld_u;
 #pragma unroll
@@ -238,7 +255,7 @@ __global__ __launch_bounds__(kBasisThreads) void k_rgcn_basis(BasisArgs a) {
         for (int jm = 0; jm < BT; ++jm)
 #pragma unroll
             for (int t = 0; t < NT; ++t) acc[jm][t] = (f32x4)(0.f);
-        accumulate_chunks<BT, NT>(a, acc, e0, e1, 0, 1, lane, c, kg);
+        accumulate_chunks<BT, NT, WT>(a, acc, e0, e1, 0, 1, lane, c, kg);
         // acc[jm][t][i] = U_i[base 16 jm + 4 kg + i][feature NT c + t]
         const float inv = a.scale ? 1.0f / fmaxf(a.indeg[row], 1.0f) : 1.0f;
         float* __restrict__ ur = a.u + (size_t)(row - a.row_lo) * a.ld_u;
@@ -336,9 +353,10 @@ BasisLayout basis_layout(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, in
     return l;
 }
 
-template <int BT>
+// (up to kBasisTiles accumulator tiles for the mean, kBasisTilesSum for the sum and the weighted calls: gn_rgcn_basis_applicable)
+template <int BT, bool WT>
 gn_status launch_bt(int nt, const BasisArgs& a, int grid, hipStream_t st) {
-#define GN_BASIS_CASE(N) case N: if constexpr (BT * N <= 16) { k_rgcn_basis<BT, N><<<grid, kBasisThreads, 0, st>>>(a); break; } else return gn::fail(GN_ERR_UNSUPPORTED, "unsupported shape")
+#define GN_BASIS_CASE(N) case N: if constexpr (BT * N <= kBasisTilesSum) { k_rgcn_basis<BT, N, WT><<<grid, kBasisThreads, 0, st>>>(a); break; } else return gn::fail(GN_ERR_UNSUPPORTED, "unsupported shape")
     switch (nt) {
         GN_BASIS_CASE(1); GN_BASIS_CASE(2); GN_BASIS_CASE(3); GN_BASIS_CASE(4);
         GN_BASIS_CASE(5); GN_BASIS_CASE(6); GN_BASIS_CASE(7); GN_BASIS_CASE(8);
@@ -367,9 +385,10 @@ struct RelDwArgs {
     float* dw;                                     // [R][fin * fout]
     float* parts;                                  // [n_parts][fin * fout]
     int vec;
+    const float* ew;                               // (weighted instantiation) [E] factor of every edge of the type-sorted list
 };
 
-template <int MT, int NT>
+template <int MT, int NT, bool WT>
 __global__ __launch_bounds__(256) void k_rel_dw(RelDwArgs a) {
     const int lane = threadIdx.x & 63, c = lane & 15, kg = lane >> 4;
     const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), W = gridDim.x * 4;
@@ -377,17 +396,27 @@ __global__ __launch_bounds__(256) void k_rel_dw(RelDwArgs a) {
     for (int it = wave; it < a.n_items; it += W) {
         const int32_t* __restrict__ d = a.items + 4 * (size_t)it;
         const int rel = d[0], e0 = d[1], e1 = d[2], slot = d[3];
-        f32x4 acc[MT][NT];
+        // WT: where the registers allow, the four steps of a round add into accumulator sets of their own, summed in set order
+        // behind the item's last edge - chains of a quarter (half) of the length: 512 edges are 32 (64) additions deep, not 128
+        constexpr int S = WT ? (MT * NT <= 4 ? 4 : (MT * NT <= 8 ? 2 : 1)) : 1;
+        f32x4 accs[S][MT][NT];
 #pragma unroll
-        for (int tm = 0; tm < MT; ++tm)
+        for (int k = 0; k < S; ++k)
 #pragma unroll
-            for (int tn = 0; tn < NT; ++tn) acc[tm][tn] = (f32x4)(0.f);
+            for (int tm = 0; tm < MT; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < NT; ++tn) accs[k][tm][tn] = (f32x4)(0.f);
+        f32x4 (&acc)[MT][NT] = accs[0];
         int64_t s_next = e0 + lane < e1 ? a.src[e0 + lane] : 0, d_next = e0 + lane < e1 ? a.dst[e0 + lane] : 0;
+        float w_next = 0.f;
+        if constexpr (WT) w_next = e0 + lane < e1 ? a.ew[e0 + lane] : 0.f;
         for (int eb = e0; eb < e1; eb += 64) {
             const int cnt = min(64, e1 - eb);
             const int64_t s_mine = s_next, d_mine = d_next;
+            const float w_mine = w_next;
             const int en = eb + 64 + lane;                                     // the next chunk's ids travel while this one is contracted
             s_next = en < e1 ? a.src[en] : 0; d_next = en < e1 ? a.dst[en] : 0;
+            if constexpr (WT) w_next = en < e1 ? a.ew[en] : 0.f;
             const int steps = (cnt + 3) >> 2;
             for (int j0 = 0; j0 < steps; j0 += 4) {
                 float xv[4][MT], gv[4][NT];
@@ -410,6 +439,11 @@ __global__ __launch_bounds__(256) void k_rel_dw(RelDwArgs a) {
                     }
 #pragma unroll
                     for (int tn = 0; tn < NT; ++tn) gv[q][tn] = (live && NT * c + tn < a.fout) ? gr[tn] : 0.f;
+                    if constexpr (WT) {                                         // w_e on the B operand: one multiply per edge and output tile
+                        const float wq = __shfl(w_mine, sel & 63);
+#pragma unroll
+                        for (int tn = 0; tn < NT; ++tn) gv[q][tn] *= wq;
+                    }
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
@@ -417,9 +451,15 @@ __global__ __launch_bounds__(256) void k_rel_dw(RelDwArgs a) {
                     for (int tm = 0; tm < MT; ++tm)
 #pragma unroll
                         for (int tn = 0; tn < NT; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[q][tm], gv[q][tn], acc[tm][tn], 0, 0, 0);
+                            accs[q % S][tm][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[q][tm], gv[q][tn], accs[q % S][tm][tn], 0, 0, 0);
             }
         }
+#pragma unroll
+        for (int k = 1; k < S; ++k)
+#pragma unroll
+            for (int tm = 0; tm < MT; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < NT; ++tn) acc[tm][tn] += accs[k][tm][tn];
         // acc[tm][tn][i] = dw[feature MT (4 kg + i) + tm][output NT c + tn]
         float* __restrict__ out = slot >= 0 ? a.parts + (size_t)slot * ff : a.dw + (size_t)rel * ff;
 #pragma unroll
@@ -454,9 +494,13 @@ __global__ __launch_bounds__(256) void k_rel_dw_combine(const int32_t* __restric
     }
 }
 
-template <int MT>
+__global__ void k_rel_dw_zero(float* __restrict__ dw, int64_t total) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) dw[t] = 0.f;
+}
+
+template <int MT, bool WT>
 gn_status launch_dw(int nt, const RelDwArgs& a, int grid, hipStream_t st) {
-#define GN_DW_CASE(N) case N: if constexpr (MT * N <= 16) { k_rel_dw<MT, N><<<grid, 256, 0, st>>>(a); break; } else return gn::fail(GN_ERR_UNSUPPORTED, "unsupported shape")
+#define GN_DW_CASE(N) case N: if constexpr (MT * N <= 16) { k_rel_dw<MT, N, WT><<<grid, 256, 0, st>>>(a); break; } else return gn::fail(GN_ERR_UNSUPPORTED, "unsupported shape")
     switch (nt) {
         GN_DW_CASE(1); GN_DW_CASE(2); GN_DW_CASE(3); GN_DW_CASE(4);
         default: return gn::fail(GN_ERR_UNSUPPORTED, "unsupported shape");
@@ -467,10 +511,10 @@ gn_status launch_dw(int nt, const RelDwArgs& a, int grid, hipStream_t st) {
 }
 
 // ---- called from rgcn.hip ----
-bool gn_rgcn_basis_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
+bool gn_rgcn_basis_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases, bool sum) {
     if (!plan || !plan->row_order.p || fin < 1 || fin > 128 || bases < 1 || bases > 64 || fout < 1) return false;
     const int64_t bt = gn::ceil_div(bases, 16), nt = gn::ceil_div(fin, 16);
-    return bt * nt <= 16;
+    return bt * nt <= (sum ? kBasisTilesSum : kBasisTiles);
 }
 
 size_t gn_rgcn_basis_workspace_bytes(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
@@ -490,9 +534,9 @@ int gn_rgcn_weight_grad_supported(const gn_rgcn_plan* plan, int64_t fin, int64_t
     return gn::ceil_div(fin, 16) * gn::ceil_div(fout, 16) <= 16;
 }
 
-gn_status gn_rgcn_weight_grad_f32(const gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst, const float* x, int64_t ld_x,
-                                  int64_t fin, const float* gm, int64_t ld_g, int64_t fout, float* dw, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+static gn_status weight_grad(const gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst, const float* ew, const float* x, int64_t ld_x,
+                             int64_t fin, const float* gm, int64_t ld_g, int64_t fout, float* dw, void* workspace,
+                             size_t workspace_bytes, void* stream) {
     GN_REQUIRE(plan != nullptr, "plan is null");
     if (!gn_rgcn_weight_grad_supported(plan, fin, fout))
         return gn::fail(GN_ERR_UNSUPPORTED, "the general relational weight gradient covers up to 128 input and 64 output features");
@@ -502,25 +546,32 @@ gn_status gn_rgcn_weight_grad_f32(const gn_rgcn_plan* plan, const int64_t* src, 
     GN_REQUIRE(plan->n_dw_parts == 0 || (workspace && workspace_bytes >= gn_rgcn_weight_grad_workspace_bytes(plan, fin, fout)),
                "workspace too small: need %zu bytes", gn_rgcn_weight_grad_workspace_bytes(plan, fin, fout));
     hipStream_t st = gn::as_stream(stream);
-    GN_HIP(hipMemsetAsync(dw, 0, (size_t)R * ff * sizeof(float), st));         // relations without edges in the shard
+    // relations without edges in the shard.  A kernel, not hipMemsetAsync: in a captured graph whose pool hands dw a block that
+    // an earlier node of the same graph used, the replayed memset node did not stay behind that node (an empty relation's
+    // row came back with the block's earlier contents on the second replay)
+    k_rel_dw_zero<<<gn::stream_grid(R * ff, 256), 256, 0, st>>>(dw, R * ff);
+    GN_LAUNCH_CHECK();
     if (plan->n_dw_items == 0) return GN_OK;
     RelDwArgs a;
     a.src = src; a.dst = dst; a.x = x; a.ld_x = ld_x; a.fin = (int)fin; a.gm = gm; a.ld_g = ld_g; a.fout = (int)fout;
     a.items = plan->dw_items.p; a.n_items = (int)plan->n_dw_items; a.dw = dw; a.parts = static_cast<float*>(workspace);
     a.vec = (fin % 16 == 0) && (ld_x % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+    a.ew = ew;
     const int mt = (int)gn::ceil_div(fin, 16), nt = (int)gn::ceil_div(fout, 16);
     const int grid = (int)std::min<int64_t>((int64_t)gn::compute_units() * 4, gn::ceil_div(plan->n_dw_items, 4));
     gn_status s;
+#define GN_DW_MT(M) (ew ? launch_dw<M, true>(nt, a, grid, st) : launch_dw<M, false>(nt, a, grid, st))
     switch (mt) {
-        case 1: s = launch_dw<1>(nt, a, grid, st); break;
-        case 2: s = launch_dw<2>(nt, a, grid, st); break;
-        case 3: s = launch_dw<3>(nt, a, grid, st); break;
-        case 4: s = launch_dw<4>(nt, a, grid, st); break;
-        case 5: s = launch_dw<5>(nt, a, grid, st); break;
-        case 6: s = launch_dw<6>(nt, a, grid, st); break;
-        case 7: s = launch_dw<7>(nt, a, grid, st); break;
-        default: s = launch_dw<8>(nt, a, grid, st); break;
+        case 1: s = GN_DW_MT(1); break;
+        case 2: s = GN_DW_MT(2); break;
+        case 3: s = GN_DW_MT(3); break;
+        case 4: s = GN_DW_MT(4); break;
+        case 5: s = GN_DW_MT(5); break;
+        case 6: s = GN_DW_MT(6); break;
+        case 7: s = GN_DW_MT(7); break;
+        default: s = GN_DW_MT(8); break;
     }
+#undef GN_DW_MT
     if (s != GN_OK) return s;
     if (plan->n_dw_multi > 0) {
         k_rel_dw_combine<<<(int)std::min<int64_t>(plan->n_dw_multi, 1024), 256, 0, st>>>(plan->dw_multi.p, (int)plan->n_dw_multi,
@@ -530,18 +581,34 @@ gn_status gn_rgcn_weight_grad_f32(const gn_rgcn_plan* plan, const int64_t* src, 
     return GN_OK;
 }
 
+gn_status gn_rgcn_weight_grad_f32(const gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst, const float* x, int64_t ld_x,
+                                  int64_t fin, const float* gm, int64_t ld_g, int64_t fout, float* dw, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    return weight_grad(plan, src, dst, nullptr, x, ld_x, fin, gm, ld_g, fout, dw, workspace, workspace_bytes, stream);
+}
+
+gn_status gn_rgcn_weight_grad_weighted_f32(const gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst, const float* edge_weight,
+                                           const float* x, int64_t ld_x, int64_t fin, const float* gm, int64_t ld_g, int64_t fout,
+                                           float* dw, void* workspace, size_t workspace_bytes, void* stream) {
+    GN_REQUIRE(edge_weight != nullptr || (plan && plan->shard_edges == 0), "edge_weight is null");
+    return weight_grad(plan, src, dst, edge_weight, x, ld_x, fin, gm, ld_g, fout, dw, workspace, workspace_bytes, stream);
+}
+
 }  // extern "C"
 
 gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* basis,
                                 const float* att, int64_t bases, const float* root, const float* bias, int64_t fout, int relu,
                                 int partial, int fast_arith, float* out, int64_t ld_out, const gn_side_copy& side, void* ws,
-                                size_t ws_bytes, hipStream_t st) {
+                                size_t ws_bytes, hipStream_t st, int sum, const float* ew) {
+    // sum (GN_RGCN_SUM): the slab's rows leave undivided and the product adds x root (where there is a root), the bias and the
+    // activation as for the mean; ew: the weighted instantiation (its position list has been built: rgcn.hip checks)
+    const bool with_root = !partial && root != nullptr;
     const BasisLayout l = basis_layout(plan, fin, fout, bases);
     GN_REQUIRE(ws && ws_bytes >= l.total, "workspace too small: the basis-space path needs %zu bytes, got %zu", l.total, ws_bytes);
     const int64_t N = plan->num_nodes;
     float* W = reinterpret_cast<float*>(static_cast<char*>(ws) + l.w_off);
     float* U = reinterpret_cast<float*>(static_cast<char*>(ws) + l.u_off);
-    const int64_t nb = bases * fin * fout, nr = partial ? 0 : fin * fout, total = (int64_t)l.kp * fout;
+    const int64_t nb = bases * fin * fout, nr = with_root ? fin * fout : 0, total = (int64_t)l.kp * fout;
     unsigned int* counters = reinterpret_cast<unsigned int*>(static_cast<char*>(ws) + l.q_off);
     GN_REQUIRE(l.slabs <= 256, "too many slabs of rows (%lld)", (long long)l.slabs);
     k_basis_weights<<<gn::stream_grid(total, 256), 256, 0, st>>>(basis, root, nb, nr, total, W, counters, (int)l.slabs);
@@ -557,7 +624,8 @@ gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_
         k_slab_orders<<<(int)l.slabs, 1024, 0, st>>>(plan->row_order.p, (int)N, (int)plan->heavy_rows, (int)l.slab_rows, slab_order, slab_heavy);
         GN_LAUNCH_CHECK();
     }
-    a.scale = partial ? 0 : 1; a.with_x = partial ? 0 : 1;
+    a.scale = (partial || sum) ? 0 : 1; a.with_x = with_root ? 1 : 0;
+    a.pos = ew ? plan->pos.p : nullptr; a.ew = ew;
     a.vec = (fin % 16 == 0) && (ld_x % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     // (measured and dropped: the att table staged in LDS - a fifth of the gathered bytes - made the layer 8 % SLOWER: the
     // fill costs more than the L2-resident 64-byte rows; what bounds the kernel is the rate of row gathers from L2 / the
@@ -574,10 +642,10 @@ gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_
         a.side = r0 == 0 ? side : gn_side_copy{nullptr, 0, nullptr, 0, 0, 0, 0};
         gn_status s;
         switch (bt) {
-            case 1: s = launch_bt<1>(nt, a, grid, st); break;
-            case 2: s = launch_bt<2>(nt, a, grid, st); break;
-            case 3: s = launch_bt<3>(nt, a, grid, st); break;
-            default: s = launch_bt<4>(nt, a, grid, st); break;
+            case 1: s = ew ? launch_bt<1, true>(nt, a, grid, st) : launch_bt<1, false>(nt, a, grid, st); break;
+            case 2: s = ew ? launch_bt<2, true>(nt, a, grid, st) : launch_bt<2, false>(nt, a, grid, st); break;
+            case 3: s = ew ? launch_bt<3, true>(nt, a, grid, st) : launch_bt<3, false>(nt, a, grid, st); break;
+            default: s = ew ? launch_bt<4, true>(nt, a, grid, st) : launch_bt<4, false>(nt, a, grid, st); break;
         }
         if (s != GN_OK) return s;
         s = gn_gemm_f32(U, l.kp, 0, nullptr, 0, W, fout, 0, out + r0 * ld_out, ld_out, 0, r1 - r0, fout, l.kp, 1,

@@ -211,3 +211,22 @@ def make_nc_homogeneous(name: str = "tiny", seed: int = 11, split_seed: int = 13
     train_idx, test_idx = order[:n_train].sort().values, order[n_train:].sort().values
     return Data(name="gat-" + name, num_nodes=n_a + n_p + n_q, num_classes=int(base.n_a_type), edge_index=edge_index,
                 train_idx=train_idx, train_y=base.a_label[train_idx], test_idx=test_idx, test_y=base.a_label[test_idx])
+
+
+def make_nc_relational(name: str = "tiny", seed: int = 11, split_seed: int = 13, train_ratio: float = 0.9, **override) -> Data:
+    """`make_nc_homogeneous` as baselines/NC_baselines/RGCN_MLP.py:36-38,52-63 reads it: the same node set, split and
+    `edge_index`, plus `edge_type` [E] - the block an edge came from (0 a-a, 1 p-p, 2 q-q, 3 p->a, 4 a->p, 5 q->a, 6 a->q) -
+    and `num_relations`.  The edges are then shuffled, seeded, so that `edge_type` arrives UNSORTED, as the pickled graphs'
+    does; `edge_index` and `edge_type` keep their pairing."""
+    base = make_nc(name, seed=seed, **override)
+    flat = make_nc_homogeneous(name, seed=seed, split_seed=split_seed, train_ratio=train_ratio, **override)
+    e_aa, e_pp, e_qq = int(base.aa_edge_idx.shape[1]), int(base.pp_edge_idx.shape[1]), int(base.qq_edge_idx.shape[1])
+    e_pa, e_qa = int(base.pa_edge_idx.shape[1]), int(base.qa_edge_idx.shape[1])
+    # to_bidirection lists every edge, then every reversed edge
+    sizes = [e_aa, e_pp, e_qq, e_pa, e_pa, e_qa, e_qa]
+    edge_type = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes))
+    assert edge_type.numel() == flat.edge_index.shape[1]
+    order = torch.randperm(edge_type.numel(), generator=torch.Generator().manual_seed(seed + 1))
+    return Data(name="rgcn-" + name, num_nodes=flat.num_nodes, num_classes=flat.num_classes,
+                edge_index=flat.edge_index[:, order].contiguous(), edge_type=edge_type[order].contiguous(), num_relations=len(sizes),
+                train_idx=flat.train_idx, train_y=flat.train_y, test_idx=flat.test_idx, test_y=flat.test_y)

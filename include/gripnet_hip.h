@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 167 /* 0.1.61 */
+#define GN_VERSION 168 /* 0.1.62 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -380,6 +380,11 @@ GN_API int gn_rgcn_forward_choice(const gn_rgcn_plan* plan, const float* x, int6
  * its backward (dx = the same layer on the reversed graph with W_r^T, autograd.rgcn_edge_gradients): no transposed copy per
  * step.  Read by the destination-major kernel only; GN_ERR_UNSUPPORTED on the others (pass a transposed copy there). */
 #define GN_RGCN_BASIS_TRANSPOSED 64
+/* GN_RGCN_SUM: the sum over the in-edges instead of their mean (RGCNConv of torch_geometric 1.4 / 1.5, aggr='add'):
+ *   out[i,:] = act( sum_{e: dst=i} x[src_e] W_{r(e)} + x[i] root + bias ),   root may be NULL (root_weight=False).
+ * Served by the general kernel, whose slab product with [basis ; root] carries the root term, the bias and the activation
+ * (the row's divisor is simply not applied), and by the table kernel beyond the general kernel's shapes. */
+#define GN_RGCN_SUM 128
 /* Kernel choice, for tests and measurements (0 = the library decides; a kernel that does not cover the shapes is not
  * forced): (GN_RGCN_PATH_x << GN_RGCN_PATH_SHIFT) in flags.  gn_rgcn_forward_path tells which one a call would take. */
 #define GN_RGCN_PATH_SHIFT 8
@@ -401,6 +406,23 @@ GN_API gn_status gn_rgcn_forward_f32(const gn_rgcn_plan* plan, const float* x, i
                               int64_t ld_out, const gn_side_copy* side /* nullable */,
                               const void* x_planes /* nullable: gn_split_planes.planes of x, written by its producer */,
                               void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same layer with a per-edge factor w_e on every message (edge_norm of RGCNConv):
+ *   flags & GN_RGCN_SUM:      out[i,:] = act( sum_{e: dst=i} w_e x[src_e] W_{r(e)} + x[i] root + bias )   (root may be NULL)
+ *   flags & GN_RGCN_PARTIAL:  out[i,:] = sum_{e: dst=i} w_e x[src_e] W_{r(e)}
+ * (one of the two; the mean has no weighted form).  General kernel only: w_e multiplies att[r(e), b] on the A operand of the
+ * fp32 matrix instruction.  edge_weight [E] fp32 is read in the CALLER's edge order through the plan's position list
+ * (gn_rgcn_plan_build_positions, once per plan).  Up to 64 bases and 128 input features (gn_rgcn_weighted_supported), else
+ * GN_ERR_UNSUPPORTED.  No atomics on floats: the same bits every run. */
+GN_API gn_status gn_rgcn_plan_build_positions(gn_rgcn_plan* plan, const int64_t* dst /* the list the plan was built from */,
+                                       const int64_t* perm /* nullable: position of every listed edge in the caller's own list */,
+                                       void* stream);
+GN_API int gn_rgcn_weighted_supported(const gn_rgcn_plan* plan, int64_t in_features, int64_t out_features, int64_t num_bases);
+GN_API size_t gn_rgcn_weighted_workspace_bytes(const gn_rgcn_plan* plan, int64_t in_features, int64_t out_features, int64_t num_bases);
+GN_API gn_status gn_rgcn_forward_weighted_f32(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t in_features,
+                                       const float* basis, const float* att, int64_t num_bases, const float* root,
+                                       const float* bias, int64_t out_features, int relu, int flags, const float* edge_weight,
+                                       float* out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* out[i,:] = act( summed[i,:] / max(1, indeg_i) + x[i] root + bias )  (layers.py:131,191-197). */
 GN_API gn_status gn_rgcn_finalize_f32(const gn_rgcn_plan* plan, const float* summed, int64_t ld_summed, const float* x,
@@ -429,6 +451,11 @@ GN_API int gn_rgcn_weight_grad_supported(const gn_rgcn_plan* plan, int64_t in_fe
 GN_API gn_status gn_rgcn_weight_grad_f32(const gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst, const float* x, int64_t ld_x,
                                   int64_t in_features, const float* gm, int64_t ld_g, int64_t out_features, float* dw, void* workspace,
                                   size_t workspace_bytes, void* stream);
+/* dw[r] = sum_{e in r} w_e x[src_e]^T gm[dst_e]: gn_rgcn_weight_grad_f32 with a per-edge factor, edge_weight [E] fp32 in the
+ * order of src / dst (the type-sorted list). */
+GN_API gn_status gn_rgcn_weight_grad_weighted_f32(const gn_rgcn_plan* plan, const int64_t* src, const int64_t* dst, const float* edge_weight,
+                                           const float* x, int64_t ld_x, int64_t in_features, const float* gm, int64_t ld_g,
+                                           int64_t out_features, float* dw, void* workspace, size_t workspace_bytes, void* stream);
 typedef struct gn_rel_grad_plan gn_rel_grad_plan;
 GN_API gn_status gn_rel_grad_plan_create(const gn_graph_plan* relation_source_sums, int64_t num_nodes, int64_t num_relations,
                                   void* stream, gn_rel_grad_plan** plan);
