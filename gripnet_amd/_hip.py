@@ -29,7 +29,7 @@ RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 168                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 169                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -116,6 +116,10 @@ SIGNATURES = {
     "gn_kge_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64]),
     "gn_kge_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
+    "gn_kge_batch_forward_workspace_bytes": (_sz, [_int, _i64, _i64]),
+    "gn_kge_batch_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
+    "gn_kge_batch_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64, _i64]),
+    "gn_kge_batch_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
     "gn_gat_logits_f32": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
     "gn_gat_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, C.c_float, _p, _int, _int, _p, _i64, _p, _p, _p, _p]),
     "gn_gat_backward_dst_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, C.c_float, _p, _i64, _int, _p, _p, _p, _p]),
@@ -1407,14 +1411,20 @@ def distmult_backward_planned(plan, z, u_v, edge_type, weight, grad_logit, dz, d
 KGE_MODELS = {"TransE": 0, "DistMult": 1, "ComplEx": 2, "RotatE": 3}          # GN_KGE_* of include/gripnet_hip.h
 
 
-def _kge_operands(model, ent, rel, sample, et):
-    """(hidden size, kept-alive index tensor, head pointer, tail pointer, E, edge_type) of a KGE call, shapes checked."""
+def _kge_hidden(model, ent, rel):
+    """(GN_KGE_* id, hidden size) of a pair of tables, their widths checked against each other."""
     m = KGE_MODELS[model]
     h = rel.shape[1] // 2 if model == "ComplEx" else rel.shape[1]
     de = 2 * h if model in ("ComplEx", "RotatE") else h
     if ent.shape[1] != de or (model == "ComplEx" and rel.shape[1] != 2 * h):
         raise ValueError("{}: entity rows of {} and relation rows of {} columns do not belong together".format(
             model, ent.shape[1], rel.shape[1]))
+    return m, h
+
+
+def _kge_operands(model, ent, rel, sample, et):
+    """(hidden size, kept-alive index tensor, head pointer, tail pointer, E, edge_type) of a KGE call, shapes checked."""
+    m, h = _kge_hidden(model, ent, rel)
     idx, head, tail, e = edge_rows(sample)
     types = i64_vec(et)
     if types.numel() != e:
@@ -1455,6 +1465,57 @@ def kge_backward(model, ent, rel, sample, et, divisor, grad_out, raw, d_ent, d_r
     ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=ent.device)
     _call("gn_kge_backward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, head, tail, ptr(types), e,
           float(divisor), ptr(grad_out), ptr(raw), ptr(d_ent), ld(d_ent), ptr(d_rel), ld(d_rel),
+          GN_DM_TYPES_SORTED if types_sorted else 0, ptr(ws), need, stream_ptr(ent.device))
+    return d_ent, d_rel
+
+
+def _kge_batch_operands(model, ent, rel, fixed, et, cand, side):
+    """(model id, hidden size, side id, fixed, edge_type, candidates as the kernels read them, B, K) of a candidate-block
+    call, shapes checked.  `cand` [B, K] int64 keeps a row stride above K (a column slice of a wider matrix); any other
+    layout is copied."""
+    m, h = _kge_hidden(model, ent, rel)
+    if side not in KGE_SIDES:
+        raise ValueError("side must be 'tail' or 'head', got {!r}".format(side))
+    fixed, types = i64_vec(fixed), i64_vec(et)
+    if fixed.dim() != 1 or types.dim() != 1 or types.numel() != fixed.numel():
+        raise ValueError("fixed entities {} and edge_type {} must be two vectors of one length".format(
+            tuple(fixed.shape), tuple(types.shape)))
+    b = int(fixed.numel())
+    if cand.dtype != torch.int64:
+        raise TypeError("indices must be int64 (torch.long), got {}".format(cand.dtype))
+    if cand.dim() != 2 or cand.shape[0] != b:
+        raise ValueError("candidates must have shape [{}, K], got {}".format(b, tuple(cand.shape)))
+    k = int(cand.shape[1])
+    if (k > 1 and cand.stride(1) != 1) or (b > 1 and cand.stride(0) < k):
+        cand = cand.contiguous()
+    return m, h, KGE_SIDES[side], fixed, types, cand, b, k
+
+
+def kge_batch_forward(model, ent, rel, fixed, et, cand, side, gamma, divisor, log_sigmoid, out, raw=None):
+    """gn_kge_batch_forward_f32: out[b, k] (fp32 [B, K], contiguous) = the score of (fixed[b], et[b], cand[b, k]) for
+    `side` "tail", of (cand[b, k], et[b], fixed[b]) for "head" (with `log_sigmoid`: its log-sigmoid, the raw scores into
+    `raw`) - the bits of kge_forward on the expanded list.  Ids outside the tables: NaN (a bad fixed entity or relation:
+    the whole row) and the device's error flag (raise_if_index_errors)."""
+    m, h, sd, fixed, types, cand, b, k = _kge_batch_operands(model, ent, rel, fixed, et, cand, side)
+    need = int(load().gn_kge_batch_forward_workspace_bytes(m, rel.shape[0], h))
+    ws = torch.empty((need,), dtype=torch.uint8, device=ent.device) if need else None
+    _call("gn_kge_batch_forward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(fixed), ptr(types),
+          ptr(cand), ld(cand), b, k, sd, float(gamma), float(divisor), int(bool(log_sigmoid)), ptr(out), ptr(raw),
+          ptr(error_flag(ent.device)), ptr(ws), need, stream_ptr(ent.device))
+    return out
+
+
+def kge_batch_backward(model, ent, rel, fixed, et, cand, side, divisor, grad_out, raw, d_ent, d_rel, types_sorted=None):
+    """gn_kge_batch_backward_f32: d_ent / d_rel (overwritten) from the gradient [B, K] of kge_batch_forward's output; `raw`:
+    the raw scores when that output was the log-sigmoid.  `types_sorted` None: looked up (once per edge_type tensor and
+    version)."""
+    m, h, sd, fixed, types, cand, b, k = _kge_batch_operands(model, ent, rel, fixed, et, cand, side)
+    if types_sorted is None:
+        types_sorted = b < 2 or _non_decreasing(et)
+    need = int(load().gn_kge_batch_backward_workspace_bytes(m, ent.shape[0], rel.shape[0], h, b, k))
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=ent.device)
+    _call("gn_kge_batch_backward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(fixed), ptr(types),
+          ptr(cand), ld(cand), b, k, sd, float(divisor), ptr(grad_out), ptr(raw), ptr(d_ent), ld(d_ent), ptr(d_rel), ld(d_rel),
           GN_DM_TYPES_SORTED if types_sorted else 0, ptr(ws), need, stream_ptr(ent.device))
     return d_ent, d_rel
 

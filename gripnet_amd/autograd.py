@@ -522,6 +522,32 @@ class KgeScoreFn(torch.autograd.Function):
         return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None
 
 
+class KgeBatchScoreFn(torch.autograd.Function):
+    """The scores [B, K] of K candidate entities per positive (fixed[b], et[b]) under one of the KGE baselines, or their
+    log-sigmoid: the 'tail-batch' / 'head-batch' modes of KGEModel.forward
+    (baselines/LP_baselines/TransE_DistMult_ComplEx_RotatE.py:127-136, :150-173).  `side` "tail": the candidates are tails of
+    (fixed, et, .); "head": heads of (., et, fixed).  Saves what KgeScoreFn saves."""
+
+    @staticmethod
+    def forward(ctx, entity, relation, fixed, et, cand, side, model, gamma, divisor, log_sigmoid):
+        ent, rel = _hip.f32_rows(entity.detach()), _hip.f32_rows(relation.detach())
+        shape = (cand.shape[0], cand.shape[1])
+        out = torch.empty(shape, dtype=torch.float32, device=ent.device)
+        raw = torch.empty(shape, dtype=torch.float32, device=ent.device) if log_sigmoid else None
+        _hip.kge_batch_forward(model, ent, rel, fixed, et, cand, side, gamma, divisor, log_sigmoid, out, raw)
+        ctx.model, ctx.divisor, ctx.side = model, divisor, side
+        ctx.save_for_backward(ent, rel, fixed, et, cand, raw)  # (sigma(-s) of the log-sigmoid is applied where the upstream is read)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ent, rel, fixed, et, cand, raw = ctx.saved_tensors
+        g = g.contiguous().to(torch.float32)
+        d_ent, d_rel = torch.empty_like(ent), torch.empty_like(rel)
+        _hip.kge_batch_backward(ctx.model, ent, rel, fixed, et, cand, ctx.side, ctx.divisor, g, raw, d_ent, d_rel)
+        return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None, None
+
+
 class GatConvFn(torch.autograd.Function):
     """``act(softmax-weighted sum over the in-edges of (x W) + b)`` per head (GATConv.forward of torch_geometric 1.4 / 1.5 as
     baselines/NC_baselines/GAT.py:66-67 calls it, with the ReLU that follows).  The forward's launches are the same with and

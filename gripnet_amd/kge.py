@@ -7,15 +7,32 @@ gradients come from a sort-based segmented reduction instead of autograd's scatt
 """
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import _hip
-from .autograd import KgeScoreFn
+from .autograd import KgeBatchScoreFn, KgeScoreFn
 
 PI = 3.14159265358979323846                                    # the constant the reference divides by (:214)
 
 # model -> (entity rows hold a real and an imaginary half, relation rows do); None: the caller's flag decides
 _HALVES = {"TransE": (None, None), "DistMult": (None, None), "ComplEx": (True, True), "RotatE": (True, None)}
+
+_BATCH_SIDES = {"tail-batch": "tail", "head-batch": "head"}    # forward's batch modes -> the side the candidates stand on
+
+
+def self_adversarial_loss(positive_score, negative_score, adversarial_temperature=None):
+    """The negative-sampling loss these four models are trained with where K negatives come with every positive, on RAW
+    scores: positive_score [B], negative_score [B, K].  The negatives are averaged, or - with a temperature T - weighted by
+    ``softmax(T * negative_score, dim=1)`` taken as a constant (self-adversarial weighting).
+    ``(-logsigmoid(s_pos).mean() - neg.mean()) / 2``.  Plain torch ops: 4 bytes per score."""
+    pos = F.logsigmoid(positive_score)
+    neg = F.logsigmoid(-negative_score)
+    if adversarial_temperature is None:
+        neg = neg.mean(dim=1)
+    else:
+        neg = (F.softmax(negative_score * adversarial_temperature, dim=1).detach() * neg).sum(dim=1)
+    return (-pos.mean() - neg.mean()) / 2
 
 
 class KGEModel(nn.Module):
@@ -55,8 +72,10 @@ class KGEModel(nn.Module):
             self.__dict__["_consts"] = cached
         return cached[1]
 
-    def _score(self, sample, et, log_sigmoid):
+    def _score(self, sample, et, log_sigmoid, mode="single"):
         ent, rel = self.entity_embedding, self.relation_embedding
+        if mode != "single":
+            return self._score_batch(sample, et, log_sigmoid, mode)
         _hip.require_gpu(ent, rel, sample, et)
         gamma, divisor = self._constants()
         if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
@@ -65,15 +84,44 @@ class KGEModel(nn.Module):
         return _hip.kge_forward(self.model_name, _hip.f32_rows(ent.detach()), _hip.f32_rows(rel.detach()), sample, et, gamma,
                                 divisor, log_sigmoid, out)
 
-    def forward(self, sample, et, mode="single"):
-        """``logsigmoid(score)`` [E] of the triples (sample[0, e], et[e], sample[1, e]) (:127-187).  An id outside its table
-        gives NaN for that triple and raises IndexError at the next synchronising check (``_hip.raise_if_index_errors``,
-        ``utils.relation_metrics``), as the decoders do."""
-        return self._score(sample, et, True)
+    def _score_batch(self, sample, et, log_sigmoid, mode):
+        """[B, K]: the candidates negatives[b, :] in the place of the positive's tail ('tail-batch') or head ('head-batch')."""
+        if mode not in _BATCH_SIDES:
+            raise ValueError("mode %s not supported" % mode)
+        side = _BATCH_SIDES[mode]
+        positive, negatives = sample
+        if positive.dim() != 2 or positive.shape[0] != 2:
+            raise ValueError("positive must have shape [2, B], got {}".format(tuple(positive.shape)))
+        if negatives.dim() != 2 or negatives.shape[0] != positive.shape[1]:
+            raise ValueError("negatives must have shape [{}, K], got {}".format(positive.shape[1], tuple(negatives.shape)))
+        ent, rel = self.entity_embedding, self.relation_embedding
+        _hip.require_gpu(ent, rel, positive, negatives, et)
+        gamma, divisor = self._constants()
+        fixed = positive[0] if side == "tail" else positive[1]     # the member the candidates do not replace
+        negatives = negatives.contiguous()
+        if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
+            return KgeBatchScoreFn.apply(ent, rel, fixed, et, negatives, side, self.model_name, gamma, divisor, log_sigmoid)
+        out = torch.empty(tuple(negatives.shape), dtype=torch.float32, device=ent.device)
+        return _hip.kge_batch_forward(self.model_name, _hip.f32_rows(ent.detach()), _hip.f32_rows(rel.detach()), fixed, et,
+                                      negatives, side, gamma, divisor, log_sigmoid, out)
 
-    def score(self, sample, et):
-        """The raw scores [E] (before the log-sigmoid): for metrics and tests."""
-        return self._score(sample, et, False)
+    def forward(self, sample, et, mode="single"):
+        """``mode="single"``: ``logsigmoid(score)`` [E] of the triples (sample[0, e], et[e], sample[1, e]) (:127-187).
+        ``mode="tail-batch"`` / ``"head-batch"`` (:127-136, :150-173): `sample` is a pair ``(positive, negatives)`` -
+        positive [2, B], negatives int64 [B, K] (made contiguous if it is not), et [B] - and the result is
+        ``logsigmoid(score)`` [B, K] of (positive[0, b], et[b], negatives[b, k]) for 'tail-batch', of (negatives[b, k], et[b],
+        positive[1, b]) for 'head-batch': K corrupted tails or heads per positive in one launch, every score the same bits
+        as the 'single' mode gives for that triple.  Any other mode raises ``ValueError("mode %s not supported")``; before
+        the batch modes existed every string was accepted and ignored, and no caller in the reference, the examples or the
+        tests passes one.  An id outside its table gives NaN for that triple (a bad positive: its whole row) and raises
+        IndexError at the next synchronising check (``_hip.raise_if_index_errors``, ``utils.relation_metrics``), as the
+        decoders do."""
+        return self._score(sample, et, True, mode)
+
+    def score(self, sample, et, mode="single"):
+        """The raw scores (before the log-sigmoid), [E] or - in the batch modes - [B, K]: differentiable; for losses on raw
+        scores (``self_adversarial_loss``), metrics and tests."""
+        return self._score(sample, et, False, mode)
 
     def _eval_operands(self, *index):
         ent, rel = self.entity_embedding, self.relation_embedding

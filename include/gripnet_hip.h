@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 168 /* 0.1.62 */
+#define GN_VERSION 169 /* 0.1.63 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -657,6 +657,44 @@ GN_API gn_status gn_kge_backward_f32(int model, const float* ent, int64_t ld_ent
                               const float* grad_out, const float* raw_scores /* nullable */, float* d_ent, int64_t ld_dent,
                               float* d_rel, int64_t ld_drel, int flags, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/* The scorers on candidate blocks: the 'head-batch' / 'tail-batch' modes of KGEModel.forward (:127-136, :150-173).  A
+ * positive b is (fixed[b], edge_type[b]) with K candidate entities cand[b * ld_cand + k] (int64, ld_cand >= K) and a side
+ * (GN_KGE_SIDE_TAIL 0, GN_KGE_SIDE_HEAD 1, defined with the ranking entry points below):
+ *   tail side: fixed is the head,  out[b * K + k] = s(fixed[b], edge_type[b], cand[b, k])
+ *   head side: fixed is the tail,  out[b * K + k] = s(cand[b, k], edge_type[b], fixed[b])
+ * or its log-sigmoid; raw_out (nullable, [B, K]) receives s as well.  Tables, gamma, phase_divisor, models, hidden sizes and
+ * the workspace (gn_kge_batch_forward_workspace_bytes, 16-byte aligned) are those of gn_kge_forward_f32, and every score is
+ * bit for bit what gn_kge_forward_f32 gives for that triple in a list: the same lanes per score, column order, term
+ * arithmetic and fold.  8 bytes of ids are read per score instead of 24, and the query's rows once per 64 candidates.
+ * A fixed entity or relation outside its table makes the whole row NaN, a candidate outside makes its element NaN; either
+ * sets bit 0 of *error_flag; nothing outside a table is read.  B == 0 or K == 0: nothing is written.
+ * GN_ERR_UNSUPPORTED: B * K beyond the triple count gn_kge_forward_f32 takes. */
+GN_API size_t gn_kge_batch_forward_workspace_bytes(int model, int64_t num_relations, int64_t hidden_dim);
+GN_API gn_status gn_kge_batch_forward_f32(int model, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                                   int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                                   const int64_t* edge_type, const int64_t* cand, int64_t ld_cand, int64_t num_positives,
+                                   int64_t num_candidates, int side, float gamma, float phase_divisor, int log_sigmoid,
+                                   float* out, float* raw_out /* nullable */, int32_t* error_flag, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+/* Their backward.  grad_out [B, K] (contiguous) and raw_scores (nullable, [B, K]) as for gn_kge_backward_f32; d_ent and
+ * d_rel are overwritten.  No float atomics, no host synchronisation, the same bits in every call:
+ *   - the candidates' rows: B * K records keyed by the candidate through the list backward's segmented reduction;
+ *   - the fixed entity's and the relation's rows: per positive the K contributions are summed first (a workgroup per
+ *     positive, k ascending within one of its 256 / lanes slots, the slots folded in slot order) into one partial row per
+ *     positive and role; two segmented reductions over B records keyed by fixed[b] and edge_type[b] then add those rows;
+ *   - d_ent is the candidate pass plus the fixed-entity pass.
+ * GN_DM_TYPES_SORTED in flags promises a non-decreasing edge_type [B]: the relation pass skips its sort.  Positives and
+ * candidates with an id outside its table contribute nothing.  B == 0 or K == 0: zero gradients.  Scratch:
+ * gn_kge_batch_backward_workspace_bytes bytes, 256-byte aligned. */
+GN_API size_t gn_kge_batch_backward_workspace_bytes(int model, int64_t num_entities, int64_t num_relations, int64_t hidden_dim,
+                                             int64_t num_positives, int64_t num_candidates);
+GN_API gn_status gn_kge_batch_backward_f32(int model, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                                    int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                                    const int64_t* edge_type, const int64_t* cand, int64_t ld_cand, int64_t num_positives,
+                                    int64_t num_candidates, int side, float phase_divisor, const float* grad_out,
+                                    const float* raw_scores /* nullable */, float* d_ent, int64_t ld_dent, float* d_rel,
+                                    int64_t ld_drel, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Graph attention: GATConv of torch_geometric 1.4 / 1.5 as baselines/NC_baselines/GAT.py uses it (single `weight`, single
