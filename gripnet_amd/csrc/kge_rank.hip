@@ -36,19 +36,19 @@
 // Budget at the widest row (EW = 128, head side): registers 128 (row) + ~40; LDS 33 KB stage + 32 KB queries
 // (4 waves x 8 x 256 floats) + 8 KB bitmaps + (top-k) 4 x 8 x (k + 128) x 8 B <= 48 KB: 121 KB of the CU's 160, one
 // workgroup per CU, one wave per SIMD.  At the driver's H = 32 (RotatE: EW = 64): 16.6 + 16 + 8 + 35 KB.
-#include "kge_term.cuh"
+// The operands are the Tables of kge_rows.cuh, made ready by its make_tables as for every KGE entry point (DistArgs takes
+// their members over at the scan loops' widths: embedding the struct cost two of k_kge_dist's lines 1 - 3 %, measured).
+#include "kge_rows.cuh"
 #include "rank_engine.cuh"
 
 namespace {
-
-enum { kTailSide = 0, kHeadSide = 1 };
 
 constexpr int kDistQueries = 8;              // queries per wave
 constexpr int kDistCap = 128;                // top-k: candidate buffer per query (a stage appends up to 64)
 constexpr int kDistStage = 64;               // candidates per stage: one per lane
 
 struct DistArgs {
-    const float* ent; int64_t ld_ent; int n; int h;
+    const float* ent; int64_t ld_ent; int n; int h;                 // Tables' members at the widths the scan loops use
     const float* rel; const float* rel_im; int64_t ld_rel; int R;   // TransE: the table; RotatE: cos and sin of its phases
     const int64_t* fixed; const int64_t* truth; const int64_t* et; int64_t Q;
     const int32_t* rowptr; const int32_t* partners;                 // null: no filter
@@ -304,7 +304,7 @@ gn_status launch_dist_model(int model, int side, const DistArgs& a, hipStream_t 
 
 // ---- the inner-product models' query rows ------------------------------------------------------------------------------
 struct QueryArgs {
-    const float* ent; int64_t ld_ent; int64_t n; const float* rel; int64_t ld_rel; int64_t R; int h;
+    Tables t;
     const int64_t* fixed; const int64_t* et; int64_t Q;
     float* q;                                                        // [Q, De]
 };
@@ -314,38 +314,34 @@ template <int M, int SIDE>
 __global__ void k_kge_query(QueryArgs a) {
 #pragma clang fp contract(off)
     constexpr int P = Traits<M>::ent_parts;
-    const int64_t total = a.Q * a.h;
+    const int h = a.t.h;
+    const int64_t total = a.Q * h;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t query = i / a.h;
-        const int c = (int)(i - query * a.h);
+        const int64_t query = i / h;
+        const int c = (int)(i - query * h);
         const int64_t ff = a.fixed[query], rr = a.et[query];
         float q0 = 0.f, q1 = 0.f;
-        if ((uint64_t)ff < (uint64_t)a.n && (uint64_t)rr < (uint64_t)a.R) {
-            const float* pe = a.ent + ff * a.ld_ent;
-            const float* pr = a.rel + rr * a.ld_rel;
+        if (in_tables(a.t, ff, ff, rr)) {
+            const float* pe = a.t.ent + ff * a.t.ld_ent;
+            const float* pr = a.t.rel + rr * a.t.ld_rel;
             if constexpr (SIDE == kTailSide || M == kDistMult) {
-                const Col col = {pe[c], P == 2 ? pe[a.h + c] : 0.f, pr[c], P == 2 ? pr[a.h + c] : 0.f, 0.f, 0.f};
+                const Col col = {pe[c], P == 2 ? pe[h + c] : 0.f, pr[c], P == 2 ? pr[h + c] : 0.f, 0.f, 0.f};
                 head_part<M>(col, q0, q1);
             } else {
-                const float tr = pe[c], ti = pe[a.h + c], wr = pr[c], wi = pr[a.h + c];
+                const float tr = pe[c], ti = pe[h + c], wr = pr[c], wi = pr[h + c];
                 q0 = wr * tr + wi * ti;
                 q1 = wr * ti - wi * tr;
             }
         }
-        float* out = a.q + query * (int64_t)(P * a.h);
+        float* out = a.q + query * (int64_t)(P * h);
         out[c] = q0;
-        if constexpr (P == 2) out[a.h + c] = q1;
+        if constexpr (P == 2) out[h + c] = q1;
     }
 }
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-size_t trig_bytes(int model, int64_t r, int64_t h) { return model == kRotatE ? align16((size_t)2 * r * h * sizeof(float)) : 0; }
-
+// the [Q, De] query rows of the inner-product models (the distance models have the trig tables there instead)
 size_t query_bytes(int model, int64_t h, int64_t q) {
-    if (model == kDistMult) return align16((size_t)q * h * sizeof(float));
-    if (model == kComplEx) return align16((size_t)2 * q * h * sizeof(float));
-    return 0;
+    return model == kDistMult || model == kComplEx ? gn::seg_align_up((size_t)entity_parts(model) * q * h * sizeof(float)) : 0;
 }
 
 struct Call {
@@ -364,8 +360,7 @@ gn_status run(const Call& c) {
     GN_REQUIRE(c.n >= 0 && c.R >= 0 && c.h >= 1 && c.Q >= 0, "bad size (n=%lld, R=%lld, hidden=%lld, queries=%lld)",
                (long long)c.n, (long long)c.R, (long long)c.h, (long long)c.Q);
     GN_REQUIRE(c.n < (1ll << 31) && c.R < (1ll << 31) && c.Q < (1ll << 40), "table too large");
-    const bool two = c.model == kComplEx || c.model == kRotatE;
-    const int64_t de = two ? 2 * c.h : c.h, dr = c.model == kComplEx ? 2 * c.h : c.h;
+    const int64_t de = entity_parts(c.model) * c.h, dr = relation_parts(c.model) * c.h;
     if (de > kMaxFeatures)
         return gn::fail(GN_ERR_UNSUPPORTED, "the ranking kernels take entity rows of at most %d floats (got %lld)", kMaxFeatures, (long long)de);
     GN_REQUIRE(c.ld_ent >= de && c.ld_rel >= dr, "leading dimension smaller than the row length");
@@ -377,9 +372,11 @@ gn_status run(const Call& c) {
     GN_REQUIRE(c.n > 0 && c.R > 0, "queries given but the entity or relation table is empty");
     const size_t need = trig_bytes(c.model, c.R, c.h) + query_bytes(c.model, c.h, c.Q);
     GN_REQUIRE(need == 0 || (c.ws && c.ws_bytes >= need && gn::aligned16(c.ws)), "workspace too small: need %zu bytes (16-byte aligned)", need);
+    Tables t;
+    GN_OK_OR_RETURN(make_tables(t, c.model, c.ent, c.ld_ent, c.n, c.rel, c.ld_rel, c.R, c.h, c.divisor, c.ws, c.ws_bytes, c.st));
 
     if (c.model == kDistMult || c.model == kComplEx) {
-        QueryArgs qa = {c.ent, c.ld_ent, c.n, c.rel, c.ld_rel, c.R, (int)c.h, c.fixed, c.et, c.Q, static_cast<float*>(c.ws)};
+        QueryArgs qa = {t, c.fixed, c.et, c.Q, static_cast<float*>(c.ws)};
         const int grid = gn::stream_grid(c.Q * c.h, 256);
         if (c.model == kDistMult) k_kge_query<kDistMult, kTailSide><<<grid, 256, 0, c.st>>>(qa);
         else if (c.side == kTailSide) k_kge_query<kComplEx, kTailSide><<<grid, 256, 0, c.st>>>(qa);
@@ -394,16 +391,8 @@ gn_status run(const Call& c) {
     }
 
     DistArgs a = {};
-    a.ent = c.ent; a.ld_ent = c.ld_ent; a.n = (int)c.n; a.h = (int)c.h;
-    a.rel = c.rel; a.rel_im = c.rel; a.ld_rel = c.ld_rel; a.R = (int)c.R;
-    if (c.model == kRotatE) {
-        GN_REQUIRE(c.divisor != 0.f, "RotatE: the phase divisor is zero");
-        float* cos_t = static_cast<float*>(c.ws);
-        float* sin_t = cos_t + c.R * c.h;
-        k_kge_trig<<<gn::stream_grid(c.R * c.h, 256), 256, 0, c.st>>>(c.rel, c.ld_rel, c.R, (int)c.h, c.divisor, cos_t, sin_t);
-        GN_LAUNCH_CHECK();
-        a.rel = cos_t; a.rel_im = sin_t; a.ld_rel = c.h;
-    }
+    a.ent = t.ent; a.ld_ent = t.ld_ent; a.n = (int)t.n; a.h = t.h;
+    a.rel = t.rel; a.rel_im = t.rel_im; a.ld_rel = t.ld_rel; a.R = (int)t.r;
     a.fixed = c.fixed; a.truth = c.truth; a.et = c.et; a.Q = c.Q;
     if (c.known) { a.rowptr = c.known->rowptr.p; a.partners = c.known->partners.p; }
     a.gamma = c.gamma; a.greater = c.greater; a.ties = c.ties; a.scores = c.scores; a.ids = c.ids; a.k = c.k; a.err = c.err;

@@ -1,7 +1,12 @@
-// What the KGE scorers' triple-list kernels (kge.hip) and candidate-block kernels (kge_batch.hip) share beyond the column
-// arithmetic of kge_term.cuh: the tables as the kernels read them, a triple's columns, the derivative of a column's term per
-// role, the backward's record and its contribution to seg_reduce.cuh, the reduce launch rule and the operand checks.  One
-// definition each, so that a score or a gradient of one triple is the same bits whichever entry point it came through.
+// What the KGE entry points (kge.hip: triple lists, kge_batch.hip: candidate blocks, kge_rank.hip: ranking) share beyond the
+// column arithmetic of kge_term.cuh, one definition each, so that a score or a gradient of one triple is the same bits
+// whichever entry point it came through:
+//   * Tables and make_tables: the operands as the kernels read them, with the refusals of a RotatE call;
+//   * load_entity / load_relation / load_cols: the float4-or-scalar row loaders;
+//   * wave_scores and store_score: the forward kernels' wave loop (lane groups, xor fold, transposition) and epilogue;
+//   * dscore, Rec, KgeTerm: the derivative of a column's term per role, the backward's record and its contribution to
+//     seg_reduce.cuh; k_kge_recs: the one record builder, over a source per entry point;
+//   * BwdFrame and backward_frame: what both backward entry points check and hold; launch_seg_reduce: the column-block rule.
 #pragma once
 
 #include "common.h"
@@ -65,7 +70,44 @@ struct Tables {
     int h;
 };
 
-// the VEC columns [k, k + VEC) of a triple's three rows
+// the VEC columns [k, k + VEC) of an entity row, real and imaginary member
+template <int M, int VEC>
+__device__ __forceinline__ void load_entity(const Tables& t, int row, int k, float (&re)[VEC], float (&im)[VEC]) {
+    const float* p = t.ent + (int64_t)row * t.ld_ent + k;
+    constexpr bool two = Traits<M>::ent_parts == 2;
+    if constexpr (VEC == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(p);
+        float4 ai = a;
+        if constexpr (two) ai = *reinterpret_cast<const float4*>(p + t.h);
+        re[0] = a.x; re[1] = a.y; re[2] = a.z; re[3] = a.w;
+        im[0] = ai.x; im[1] = ai.y; im[2] = ai.z; im[3] = ai.w;
+    } else {
+        re[0] = p[0];
+        im[0] = two ? p[t.h] : 0.f;
+    }
+}
+
+// the same columns of a relation's operand (RotatE: cos, sin)
+template <int M, int VEC>
+__device__ __forceinline__ void load_relation(const Tables& t, int row, int k, float (&re)[VEC], float (&im)[VEC]) {
+    const float* p = t.rel + (int64_t)row * t.ld_rel + k;
+    const float* pi = t.rel_im + (int64_t)row * t.ld_rel + k;
+    constexpr bool two = Traits<M>::ent_parts == 2;
+    if constexpr (VEC == 4) {
+        const float4 w = *reinterpret_cast<const float4*>(p);
+        float4 wi = w;
+        if constexpr (two) wi = *reinterpret_cast<const float4*>(pi);
+        re[0] = w.x; re[1] = w.y; re[2] = w.z; re[3] = w.w;
+        im[0] = wi.x; im[1] = wi.y; im[2] = wi.z; im[3] = wi.w;
+    } else {
+        re[0] = p[0];
+        im[0] = two ? pi[0] : 0.f;
+    }
+}
+
+// The same columns of a triple's three rows.  Not two load_entity calls and a load_relation call: that form issues the
+// loads row by row, this one the three real pieces before the three imaginary ones, and the record reductions, which at a
+// record or two per row wait for exactly these loads, measured 0.4 - 0.8 % slower with it (profiles/r23_kge_once.md).
 template <int M, int VEC>
 __device__ __forceinline__ void load_cols(const Tables& t, int hh, int tt, int rr, int k, Col (&c)[VEC]) {
     const float* ph = t.ent + (int64_t)hh * t.ld_ent + k;
@@ -92,12 +134,56 @@ __device__ __forceinline__ void load_cols(const Tables& t, int hh, int tt, int r
     }
 }
 
+// every id inside its table (a query, which has one entity, passes it twice)
+__device__ __forceinline__ bool in_tables(const Tables& t, int64_t head, int64_t tail, int64_t rel) {
+    return (uint64_t)head < (uint64_t)t.n && (uint64_t)tail < (uint64_t)t.n && (uint64_t)rel < (uint64_t)t.r;
+}
+
 __device__ __forceinline__ float log_sigmoid(float s) { return fminf(s, 0.f) - log1pf(expf(-fabsf(s))); }
 
 // d logsigmoid(s) / d s = sigma(-s), without an overflow of exp
 __device__ __forceinline__ float sigmoid_neg(float s) {
     const float ex = expf(-fabsf(s));
     return s > 0.f ? ex / (1.0f + ex) : 1.0f / (1.0f + ex);
+}
+
+// ds of score `at`'s upstream: grad_out, times sigma(-s) when the forward returned the log-sigmoid (raw holds s then)
+__device__ __forceinline__ float upstream(const float* __restrict__ grad_out, const float* __restrict__ raw, int64_t at) {
+    const float g = grad_out[at];
+    return raw ? g * sigmoid_neg(raw[at]) : g;
+}
+
+// ---- forward: the wave loop ----------------------------------------------------------------------------------------------
+// A wave scores cnt <= 64 triples, `group` lanes (a power of two, 1..16) per score, 64 / group scores per trip.  partial(idx)
+// is lane j's share of score idx's column sum, j = lane % group: every lane calls it in every trip (it may shuffle the ids a
+// lane read) and a slot past cnt returns 0.  The group's shares are folded by xor in a fixed order and lane l keeps the sum
+// of score l (trip l / slots, slot l % slots), so the scores leave in one coalesced store.  The list kernel and the block
+// kernel run THIS loop: a triple's score is the same bits from either.
+template <typename Partial>
+__device__ __forceinline__ float wave_scores(int lane, int group, int cnt, Partial&& partial) {
+    const int slots = 64 / group, slot = lane / group;
+    float result = 0.f;
+    for (int it = 0; it * slots < cnt; ++it) {
+        float acc = partial(it * slots + slot);
+        for (int off = 1; off < group; off <<= 1) acc += __shfl_xor(acc, off);
+        const float got = __shfl(acc, (lane % slots) * group);
+        if (lane / slots == it) result = got;
+    }
+    return result;
+}
+
+// The epilogue of score `at`: the model's finish; NaN and bit 0 of the error word for an id outside its table; the raw score
+// for the backward; the log-sigmoid or the score itself.
+template <int M>
+__device__ __forceinline__ void store_score(float sum, bool ok, int64_t at, float gamma, int log_sigmoid_out, float* out,
+                                            float* raw, int32_t* err) {
+    float result = finish<M>(sum, gamma);
+    if (!ok) {
+        result = __builtin_nanf("");
+        if (err) atomicOr(err, 1);
+    }
+    if (raw) raw[at] = result;
+    out[at] = log_sigmoid_out ? log_sigmoid(result) : result;
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
@@ -109,7 +195,7 @@ constexpr uint32_t kSkip = 0xffffffffu;
 template <int M, int ROLE>
 struct KgeTerm {
     using Rec = ::Rec;
-    static constexpr int P = ROLE == kRelation ? (M == kComplEx ? 2 : 1) : Traits<M>::ent_parts;
+    static constexpr int P = ROLE == kRelation ? Traits<M>::rel_parts : Traits<M>::ent_parts;
     static constexpr bool kFused = true;
     Tables t; float divisor;
     static __device__ __forceinline__ bool skip(const Rec& r) { return r.h == kSkip; }
@@ -127,6 +213,22 @@ struct KgeTerm {
     }
 };
 
+// The records of a pass.  A source yields element e's record - src.get(e, t, rec): false for an id outside its table - and
+// the record is keyed by its member for `role`; an invalid element becomes a skip record whose key sorts past the last
+// row and is never read.  keys == null: the records stay in list order (a relation pass over sorted relation ids).
+template <typename Src>
+__global__ void k_kge_recs(Src src, int role, int64_t count, Tables t, uint32_t num_keys, uint32_t* __restrict__ keys,
+                           Rec* __restrict__ recs) {
+    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < count; e += (int64_t)gridDim.x * blockDim.x) {
+        Rec rec;
+        uint32_t key = num_keys;
+        if (src.get(e, t, rec)) key = role == kHead ? rec.h : (role == kTail ? rec.t : rec.r);
+        else rec = {kSkip, 0u, 0u, 0.f};
+        if (keys) keys[e] = key;
+        recs[e] = rec;
+    }
+}
+
 size_t trig_bytes(int model, int64_t r, int64_t h) { return model == kRotatE ? gn::seg_align_up((size_t)2 * r * h * sizeof(float)) : 0; }
 
 // The relation operand as the kernels read it: the table itself, or (RotatE) cos / sin of its phases in `trig`.
@@ -139,6 +241,19 @@ gn_status relation_operand(int model, Tables& t, const float* rel, int64_t ld_re
     GN_LAUNCH_CHECK();
     t.rel = cos_t; t.rel_im = sin_t; t.ld_rel = t.h;
     return GN_OK;
+}
+
+// The ready tables of a call with work to do, for every entry point: RotatE needs a divisor and trig_bytes of 16-byte aligned
+// scratch for its cos / sin tables.
+gn_status make_tables(Tables& t, int model, const float* ent, int64_t ld_ent, int64_t n, const float* rel, int64_t ld_rel, int64_t r,
+                      int64_t h, float divisor, void* trig, size_t trig_size, hipStream_t st) {
+    t.ent = ent; t.ld_ent = ld_ent; t.n = n; t.r = r; t.h = (int)h;
+    if (model == kRotatE) {
+        GN_REQUIRE(divisor != 0.f, "RotatE: the phase divisor is zero");
+        GN_REQUIRE(trig && trig_size >= trig_bytes(model, r, h) && gn::aligned16(trig),
+                   "workspace too small: need %zu bytes (16-byte aligned)", trig_bytes(model, r, h));
+    }
+    return relation_operand(model, t, rel, ld_rel, divisor, static_cast<float*>(trig), st);
 }
 
 bool vector_rows(const Tables& t) {
@@ -162,8 +277,7 @@ gn_status check_shapes(int model, const float* ent, int64_t ld_ent, int64_t n, c
     if (e == 0) return GN_OK;
     GN_REQUIRE(n > 0 && r > 0, "triples given but the entity or relation table is empty");
     GN_REQUIRE(ent && rel, "operand pointer is null");
-    const int64_t de = (model == kComplEx || model == kRotatE) ? 2 * h : h, dr = model == kComplEx ? 2 * h : h;
-    GN_REQUIRE(ld_ent >= de && ld_rel >= dr, "leading dimension smaller than the row length");
+    GN_REQUIRE(ld_ent >= entity_parts(model) * h && ld_rel >= relation_parts(model) * h, "leading dimension smaller than the row length");
     return GN_OK;
 }
 
@@ -177,6 +291,59 @@ void launch_seg_reduce(const C& c, const gn::SegFrame<Rec>& f, bool vec, int lpe
     if (!vec) gn::k_seg_reduce<C, 1, 16, CHUNK><<<chunks, 256, 0, st>>>(a);
     else if (lpe == 8) gn::k_seg_reduce<C, 4, 8, CHUNK><<<chunks, 256, 0, st>>>(a);
     else gn::k_seg_reduce<C, 4, 16, CHUNK><<<chunks, 256, 0, st>>>(a);
+}
+
+// What a backward entry point holds for its passes, whatever its ids are; an entry point derives from it and adds those.
+struct BwdFrame {
+    int model; Tables t;
+    const float* grad_out; const float* raw; float divisor;     // upstream; the forward's raw scores or null; 1 unless RotatE
+    float* d_ent; int64_t ld_dent; float* d_rel; int64_t ld_drel;
+    bool types_sorted, vec; int lpe; hipStream_t st;              // vec, lpe: the column-block rule, decided here once
+};
+
+// The backward entry points' common part, after check_shapes: the gradients' checks; with `empty` (no score or no column)
+// the gradients of an empty sum, and nothing else; otherwise the pointer and workspace checks (layout() is the entry
+// point's SegLayout, RotatE's tables at its tail) and the frame.  ids: the entry point's id pointers are all there.
+template <typename Layout>
+gn_status backward_frame(BwdFrame& c, gn::SegLayout& l, int model, const float* ent, int64_t ld_ent, int64_t n, const float* rel,
+                         int64_t ld_rel, int64_t r, int64_t h, bool empty, bool ids, float divisor, const float* grad_out,
+                         const float* raw, float* d_ent, int64_t ld_dent, float* d_rel, int64_t ld_drel, int flags, void* workspace,
+                         size_t workspace_bytes, Layout&& layout, hipStream_t st) {
+    const int64_t de = entity_parts(model) * h, dr = relation_parts(model) * h;
+    GN_REQUIRE((n == 0 || h == 0 || d_ent) && (r == 0 || h == 0 || d_rel), "gradient pointer is null");
+    GN_REQUIRE(ld_dent >= de && ld_drel >= dr, "leading dimension of a gradient smaller than the row length");
+    if (empty) {
+        if (n > 0 && de > 0) GN_HIP(hipMemset2DAsync(d_ent, ld_dent * sizeof(float), 0, de * sizeof(float), n, st));
+        if (r > 0 && dr > 0) GN_HIP(hipMemset2DAsync(d_rel, ld_drel * sizeof(float), 0, dr * sizeof(float), r, st));
+        return GN_OK;
+    }
+    GN_REQUIRE(ids && grad_out, "operand pointer is null");
+    l = layout();
+    GN_REQUIRE(workspace && workspace_bytes >= l.total, "workspace too small: need %zu bytes", l.total);
+    GN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "workspace must be 256-byte aligned");
+    c.model = model;
+    GN_OK_OR_RETURN(make_tables(c.t, model, ent, ld_ent, n, rel, ld_rel, r, h, divisor, static_cast<char*>(workspace) + l.tail,
+                                trig_bytes(model, r, h), st));
+    c.grad_out = grad_out; c.raw = raw;
+    c.divisor = model == kRotatE ? divisor : 1.0f;
+    c.d_ent = d_ent; c.ld_dent = ld_dent; c.d_rel = d_rel; c.ld_drel = ld_drel;
+    c.types_sorted = (flags & GN_DM_TYPES_SORTED) != 0;
+    c.vec = vector_rows(c.t);                                     // (the gradients are stored a float at a time: any ld)
+    c.lpe = reduce_lanes(c.vec, c.t.h / (c.vec ? 4 : 1));
+    c.st = st;
+    return GN_OK;
+}
+
+// One pass of a backward: `count` records from `src` keyed by `role` - sorted, or left in list order when `sorted_types` are
+// the relation pass's own sorted ids - and reduced per row into `o` by the contribution that `launch` starts.
+template <typename Src, typename Launch>
+gn_status record_pass(const BwdFrame& c, const gn::SegWs<Rec>& w, const Src& src, int role, int64_t count,
+                      const int64_t* sorted_types, const gn::SegOut& o, Launch&& launch, int chunk = gn::kSegChunkRecs) {
+    const int64_t rows = role == kRelation ? c.t.r : c.t.n;
+    k_kge_recs<<<gn::stream_grid(count, 256), 256, 0, c.st>>>(src, role, count, c.t, (uint32_t)rows, sorted_types ? nullptr : w.keys, w.recs);
+    GN_LAUNCH_CHECK();
+    const int vecw = c.vec ? 4 : 1;
+    return gn::seg_pass(w, count, rows, sorted_types, o, c.t.h / vecw, vecw, c.lpe, launch, c.st, chunk);
 }
 
 }  // namespace

@@ -1,17 +1,43 @@
-// The per-column arithmetic of the knowledge-graph-embedding scorers, shared by the triple-list kernels (kge.hip) and the
-// ranking kernels (kge_rank.hip): one definition of what a column contributes, so that both round a term alike.
+// What every knowledge-graph-embedding kernel (kge.hip, kge_batch.hip, kge_rank.hip) starts from: the model and side ids, how
+// many parts a row has, the one place where a run-time model id or flag becomes a template argument, and the per-column
+// arithmetic - one definition of what a column contributes, so that every kernel rounds a term alike.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
 enum { kTransE = GN_KGE_TRANSE, kDistMult = GN_KGE_DISTMULT, kComplEx = GN_KGE_COMPLEX, kRotatE = GN_KGE_ROTATE };
+enum { kTailSide = GN_KGE_SIDE_TAIL, kHeadSide = GN_KGE_SIDE_HEAD };      // which end of the triple the candidates fill
 
+// parts (real, imaginary) of an entity row and of a row of the relation table (RotatE's table holds phases: one part; the
+// operand the kernels read has two, cos and sin)
 template <int M> struct Traits;
-template <> struct Traits<kTransE>   { static constexpr int ent_parts = 1; };
-template <> struct Traits<kDistMult> { static constexpr int ent_parts = 1; };
-template <> struct Traits<kComplEx>  { static constexpr int ent_parts = 2; };
-template <> struct Traits<kRotatE>   { static constexpr int ent_parts = 2; };   // (its relation operand has two parts as well: cos, sin)
+template <> struct Traits<kTransE>   { static constexpr int ent_parts = 1, rel_parts = 1; };
+template <> struct Traits<kDistMult> { static constexpr int ent_parts = 1, rel_parts = 1; };
+template <> struct Traits<kComplEx>  { static constexpr int ent_parts = 2, rel_parts = 2; };
+template <> struct Traits<kRotatE>   { static constexpr int ent_parts = 2, rel_parts = 1; };
+
+// The dispatch: f(std::integral_constant<int, model>{}) for a validated model id, f(std::true_type / std::false_type{}) for a
+// flag.  A launch site is these two around a generic lambda that names its kernel once.
+template <typename F>
+auto with_model(int model, F&& f) {
+    switch (model) {
+        case kTransE: return f(std::integral_constant<int, kTransE>{});
+        case kDistMult: return f(std::integral_constant<int, kDistMult>{});
+        case kComplEx: return f(std::integral_constant<int, kComplEx>{});
+        default: return f(std::integral_constant<int, kRotatE>{});
+    }
+}
+
+template <typename F>
+auto with_flag(bool flag, F&& f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+int entity_parts(int model) { return with_model(model, [](auto m) { return Traits<decltype(m)::value>::ent_parts; }); }
+int relation_parts(int model) { return with_model(model, [](auto m) { return Traits<decltype(m)::value>::rel_parts; }); }
 
 // One column of a triple: (hr, hi), (rr, ri), (tr, ti); the imaginary members are unused by the real models.  For RotatE
 // (rr, ri) = (cos theta, sin theta).
