@@ -42,6 +42,11 @@ struct gn_distmult_plan {
     gn::DevBuf<uint32_t> cls_mirror;  // [(batches + slack) * 64]
     gn::DevBuf<uint32_t> cls_rel;     // [(batches + slack) * 2] relation of each of the batch's four steps, 16 bits each
     gn::DevBuf<int32_t> cls_wg;       // [groups][4 + 4 walks] first rows: start, count; second rows: start, count; per walk: batches lo, hi; relations lo, count
+    // Launches of up to 256 workgroups take the rows with the kernel arguments: the four row numbers of each class (one or
+    // three) and two bits of class per workgroup (DmClassArgs)
+    int cls_by_args = 0;
+    int32_t cls_rows[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    uint32_t cls_of_wg[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -219,6 +224,11 @@ struct DmClassArgs {
     float* out; int c0; int sigmoid, first_launch, last_launch;
     int walks;                 // batch ranges per workgroup: an XCD's workgroups walk its position sub-ranges one after the other
     int dma;                   // the LDS image is a straight byte copy of z rows and D rows: filled by LDS-DMA (class_dma_piece)
+    // Grids of up to 256 workgroups (k_distmult_class): the class's rows come with the arguments (the workgroup descriptor
+    // a.wg is plan memory, L2-cold at kernel start: read first, it put a round trip in front of the table's requests, which
+    // need nothing else of it).  Larger grids (k_distmult_class_wide) read the rows from a.wg.
+    int cls_rows[3][4];        // r0s, r0c, r1s, r1c of each class
+    uint32_t cls_of_wg[16];    // two bits of class per workgroup
 };
 
 // One wave step: quad q scores the pair of slot 4 q + S.  J 16-byte chunks per lane (lane l4 of the quad holds chunks
@@ -283,18 +293,56 @@ __device__ __forceinline__ void class_dma_piece(float4* lds4, int p, int lane, c
                                          (__attribute__((address_space(3))) void*)(lds4 + (size_t)p * 64), 16, 0, 0);
 }
 
-template <int J, int J1>
-__global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
+// The same for a piece of the rows alone (bytes [0, t) of the image): needs the class's row numbers and nothing of the
+// workgroup's batch ranges
+__device__ __forceinline__ void class_dma_rows_piece(float4* lds4, int p, int lane, const char* z0, const char* z1, uint32_t t0, uint32_t t) {
+    const uint32_t o = (uint32_t)p * 1024u + (uint32_t)lane * 16u;
+    const char* src = o < t0 ? z0 + o : z1 + (o - t0);
+    if (o < t)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                         (__attribute__((address_space(3))) void*)(lds4 + (size_t)p * 64), 16, 0, 0);
+}
+
+// ARGS: the class's rows come with the kernel arguments (grids of up to 256 workgroups, k_distmult_class); else from the
+// workgroup descriptor, read first (k_distmult_class_wide).
+template <int J, int J1, bool ARGS>
+__device__ __forceinline__ void distmult_class(const DmClassArgs& a) {
     extern __shared__ float4 lds4[];
     constexpr int ROW4 = 4 * J;                               // float4 per row of the launch's columns
     constexpr int STR4 = (J & 1) ? ROW4 : ROW4 + 4;           // LDS stride: an odd number of 64-byte bank slots
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int32_t* __restrict__ g = a.wg + (size_t)blockIdx.x * (4 + 4 * a.walks);
-    const int r0s = g[0], r0c = g[1], r1s = g[2], r1c = g[3];
+    uint32_t wg_id = blockIdx.x;
+    const float* zp = a.z;
+    int dma_arg = a.dma;
+    int r0s, r0c, r1s, r1c;
+    if constexpr (ARGS) {
+        // All twelve row numbers arrive with the arguments and the class picks among them with scalar selects.
+        // Everything the first requests need goes THROUGH one empty asm statement together with the workgroup's number,
+        // which the descriptor's address is made of: the compiler fetches an argument in the block that first uses it and
+        // waits for it there, and a wait for scalar loads waits for all of them - left alone, the class's rows, a.dma and
+        // a.z were each fetched behind the descriptor's loads and waited for WITH them, a round trip to plan memory.  So:
+        // the arguments with one wait, then the descriptor's loads, which stay in flight until the batches start.  (Not
+        // volatile and without a memory clobber: a statement that may write memory in front of them turns the descriptor's
+        // loads into vector loads.)
+        int q00 = a.cls_rows[0][0], q01 = a.cls_rows[0][1], q02 = a.cls_rows[0][2], q03 = a.cls_rows[0][3];
+        int q10 = a.cls_rows[1][0], q11 = a.cls_rows[1][1], q12 = a.cls_rows[1][2], q13 = a.cls_rows[1][3];
+        int q20 = a.cls_rows[2][0], q21 = a.cls_rows[2][1], q22 = a.cls_rows[2][2], q23 = a.cls_rows[2][3];
+        uint32_t cls_word = a.cls_of_wg[(blockIdx.x >> 4) & 15u];
+        asm("" : "+s"(wg_id), "+s"(zp), "+s"(dma_arg), "+s"(cls_word)
+               : "s"(q00), "s"(q01), "s"(q02), "s"(q03), "s"(q10), "s"(q11), "s"(q12), "s"(q13), "s"(q20), "s"(q21), "s"(q22),
+                 "s"(q23), "s"(a.wg), "s"(a.walks));
+        const uint32_t cls = (cls_word >> (2u * (wg_id & 15u))) & 3u;
+        r0s = cls == 0 ? q00 : (cls == 1 ? q10 : q20);
+        r0c = cls == 0 ? q01 : (cls == 1 ? q11 : q21);
+        r1s = cls == 0 ? q02 : (cls == 1 ? q12 : q22);
+        r1c = cls == 0 ? q03 : (cls == 1 ? q13 : q23);
+    }
+    const int32_t* __restrict__ g = a.wg + (size_t)wg_id * (4 + 4 * a.walks);
     // (the first walk's range is read with the rows - one scalar load of the descriptor's first 32 bytes - and every further
     // walk's range one walk ahead: read where it is used, it put a memory round trip in front of the first batches' requests)
     int nb_lo = g[4], nb_hi = g[5], nrel_lo = g[6], nnrel = g[7];
+    if constexpr (!ARGS) { r0s = g[0]; r0c = g[1]; r1s = g[2]; r1c = g[3]; }
     const int rows = r0c + r1c;
     GN_DM_STAMP(0);
 #ifdef GN_STAMPS
@@ -311,6 +359,29 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
     const uint32_t lane_off = (uint32_t)l4 * 16u;
     float4* dfill = lds4 + (size_t)rows * STR4;
     const f32x4* __restrict__ dl = reinterpret_cast<const f32x4*>(dfill) + l4;
+    bool dma = false;
+    if constexpr (STR4 == ROW4) dma = dma_arg != 0;
+    // LDS-DMA fill with the rows from the arguments: the pieces of the two row blocks - nine tenths of the image - are
+    // requested HERE, while the descriptor is still on its way; the index words and D's pieces follow behind it (first walk
+    // below).  The workgroup starts at a piece of its own (a 16-bit hash scaled to the piece count: no division), the waves
+    // take turns.
+    const bool rows_first = ARGS && dma;
+    if constexpr (STR4 == ROW4) {
+        if (rows_first) {
+            constexpr int RB = ROW4 * 16;
+            const char* z0 = reinterpret_cast<const char*>(zp) + (int64_t)r0s * RB;
+            const char* z1 = reinterpret_cast<const char*>(zp) + (int64_t)r1s * RB;
+            const uint32_t t0 = (uint32_t)r0c * RB, t = (uint32_t)rows * RB;
+            const int nr = (int)((t + 1023u) >> 10);
+            const int rot = (int)((((wg_id * 977u) & 0xffffu) * (uint32_t)nr) >> 16);
+            for (int i = wave; i < nr; i += (int)kStep) {
+                int p = i + rot;
+                p = p < nr ? p : p - nr;
+                class_dma_rows_piece(lds4, p, lane, z0, z1, t0, t);
+            }
+            asm volatile("" ::: "memory");                                           // the rows' pieces are requested first
+        }
+    }
     // A workgroup walks its batch ranges one after the other (one per position sub-range of its XCD: the half-written
     // score lines of ONE sub-range are what the L2 has to keep); the table is filled once, the relation rows of D a
     // range's batches name are refilled per range.
@@ -327,8 +398,6 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
         uint32_t rw0 = rel[2 * b], rw1 = rel[2 * (b + kStep)];
         uint32_t o0 = own[b * 64u], o1 = own[(b + kStep) * 64u];
         uint32_t m0 = last ? mir[b * 64u] : kNoMirror, m1 = last ? mir[(b + kStep) * 64u] : kNoMirror;
-        bool dma = false;
-        if constexpr (STR4 == ROW4) dma = a.dma != 0;
         if (dma) {
             if constexpr (STR4 == ROW4) {
                 // The LDS image is a byte copy of the class's rows and of the range's relation rows of D: every 1 KB piece of
@@ -337,13 +406,13 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
                 // first (all that a pair inside the first block needs), then the second block's; inside each set the
                 // workgroup starts at its own piece and the waves take turns.
                 constexpr int RB = ROW4 * 16;
-                const char* z0 = reinterpret_cast<const char*>(a.z) + (int64_t)r0s * RB;
-                const char* z1 = reinterpret_cast<const char*>(a.z) + (int64_t)r1s * RB;
+                const char* z0 = reinterpret_cast<const char*>(zp) + (int64_t)r0s * RB;
+                const char* z1 = reinterpret_cast<const char*>(zp) + (int64_t)r1s * RB;
                 const char* d0 = reinterpret_cast<const char*>(a.d) + (int64_t)rel_lo * a.ld_d * 4;
                 const uint32_t t0 = (uint32_t)r0c * RB, t = (uint32_t)rows * RB, end = t + (uint32_t)nrel * RB;
                 const int np = (int)((end + 1023u) >> 10), pd = (int)(t >> 10);      // pieces; the first one that holds D
                 asm volatile("" ::: "memory");                                       // the index words are requested first
-                if (walk == 0) {
+                if (walk == 0 && !rows_first) {
                     const int p0 = (int)((t0 + 1023u) >> 10), pl = max(pd, p0);      // second block only: pieces [p0, pl)
                     const int ne = p0 + np - pl, nl = pl - p0;
                     const int rot_e = (int)((blockIdx.x * 977u) % (unsigned)max(ne, 1));
@@ -374,7 +443,8 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
                     GN_DM_STAMP(5);
 #endif
                 } else {
-                    __syncthreads();                              // every wave is done with the previous range's relation rows
+                    // D's pieces alone: behind the rows requested from the arguments (first walk), or for a further walk
+                    if (walk > 0) __syncthreads();                // every wave is done with the previous range's relation rows
                     for (int p = pd + wave; p < np; p += (int)kStep)
                         class_dma_piece<RB>(lds4, p, lane, z0, z1, t0, t, d0, a.ld_d * 4, t, end);
                 }
@@ -466,12 +536,23 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) {
 }
 
 template <int J, int J1>
+__global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) { distmult_class<J, J1, true>(a); }
+template <int J, int J1>
+__global__ __launch_bounds__(kThreads) void k_distmult_class_wide(DmClassArgs a) { distmult_class<J, J1, false>(a); }
+
+template <int J, int J1>
 gn_status launch_class(const gn_distmult_plan* plan, const DmClassArgs& a, int64_t n, hipStream_t st) {
-    gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(k_distmult_class<J, J1>), 160 * 1024);
+    auto launch = [&](auto kernel) {
+        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(kernel), 160 * 1024);
+        if (s != GN_OK) return s;
+        const gn::LaunchEvents ev = gn::take_launch_events();
+        if (ev.start || ev.stop) hipExtLaunchKernelGGL(kernel, dim3(plan->cls_groups), dim3(kThreads), 160 * 1024, st, ev.start, ev.stop, 0, a);
+        else kernel<<<plan->cls_groups, kThreads, 160 * 1024, st>>>(a);
+        return GN_OK;
+    };
+    // (the class table of the arguments covers 256 workgroups: a larger grid reads its rows from the descriptors)
+    const gn_status s = plan->cls_by_args ? launch(k_distmult_class<J, J1>) : launch(k_distmult_class_wide<J, J1>);
     if (s != GN_OK) return s;
-    const gn::LaunchEvents ev = gn::take_launch_events();
-    if (ev.start || ev.stop) hipExtLaunchKernelGGL((k_distmult_class<J, J1>), dim3(plan->cls_groups), dim3(kThreads), 160 * 1024, st, ev.start, ev.stop, 0, a);
-    else k_distmult_class<J, J1><<<plan->cls_groups, kThreads, 160 * 1024, st>>>(a);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }
@@ -524,6 +605,11 @@ gn_status build_distmult_plan(const V& hu, const V& hv, const V& hr, int64_t E,
             GN_LAP("decoder: allocations + upload (sync)");
             GN_LAP(nullptr);
             p->cls_features = (int)num_features; p->cls_groups = cl.groups; p->cls_batches = cl.batches; p->cls_walks = cl.walks;
+            p->cls_by_args = cl.groups <= 256 && (int)cl.wg_cls.size() == cl.groups;
+            if (p->cls_by_args) {
+                memcpy(p->cls_rows, cl.cls_rows, sizeof(p->cls_rows));
+                for (int w = 0; w < cl.groups; ++w) p->cls_of_wg[w >> 4] |= (uint32_t)(cl.wg_cls[(size_t)w] & 3u) << (2 * (w & 15));
+            }
             p->cls_ok = 1;
             *out = p.release();
             return GN_OK;
@@ -625,6 +711,8 @@ static gn_status plan_forward_cols(const gn_distmult_plan* plan, const float* z,
             c.first_launch = col_lo == 0; c.last_launch = col_hi == num_features; c.walks = plan->cls_walks;
             // (odd J: no padding between the LDS rows; z and d are 16-byte aligned and ld_d a multiple of four floats here)
             c.dma = (J & 1) && ld_z == f && col_lo == 0;
+            memcpy(c.cls_rows, plan->cls_rows, sizeof(c.cls_rows));
+            memcpy(c.cls_of_wg, plan->cls_of_wg, sizeof(c.cls_of_wg));
             hipStream_t st = gn::as_stream(stream);
             switch (J * 8 + J1) {
                 case 5 * 8 + 3: return launch_class<5, 3>(plan, c, n, st);

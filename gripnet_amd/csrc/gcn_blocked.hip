@@ -146,6 +146,7 @@ struct ColArgs {
     const float* dis; const float* bias;
     float* out; int64_t ld_out;
     int n, rows_pad, groups, ranges, relu;
+    int per_x, group_shift;              // ranges per XCD, ceil(ranges / 8); log2(groups): groups is a power of two
     gn_side_copy side;
     float* next_table;                   // k_col_gather_next: the next layer's table, [groups][rows_pad][CW] (see col_gather)
 };
@@ -190,42 +191,56 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
     const int q = lane >> 2, j = lane & 3;
     // Workgroups go to the eight XCDs round-robin and every XCD has its own L2: the column groups of one range sit on
     // one XCD (its id stream is fetched into one L2), and each XCD sees every column group.
-    const int wg = blockIdx.x, per_x = (a.ranges + 7) / 8;
+    // (per_x = ceil(ranges / 8) and log2(groups) come with the arguments: the generic division by `groups` stood, with a
+    // second fetch of arguments behind it, in front of the first request.  A workgroup without a range - ranges no multiple
+    // of eight - takes the same path with nothing to fill, gather or write: an early way out for it split the argument
+    // loads over two blocks, and every workgroup waited for them twice.)
+    const int wg = blockIdx.x;
     const int x = wg & 7, k = wg >> 3;
-    const int range = x * per_x + k / a.groups, cg = k % a.groups;
+    const int range = x * a.per_x + (k >> a.group_shift), cg = k & (a.groups - 1);
     const bool live = range < a.ranges;
 #ifdef GN_STAMPS
     const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
 #endif
     // ---- this wave's tiles [c0, c1): read with scalar loads BEFORE the first vector-memory instruction (behind the
     //      DMA loads the compiler would make them vector loads, and those return in issue order: behind the table) ----
-    const int32_t* __restrict__ cell = a.cell + ((size_t)(live ? range : 0) * kColWaves + wave) * kWaveInts;
+    //      (a workgroup without a range reads the record behind the last range's: no tiles, no iterations)
+    const int my_range = live ? range : a.ranges;
+    const int32_t* __restrict__ cell = a.cell + ((size_t)my_range * kColWaves + wave) * kWaveInts;
     const int c0 = cell[0], c1 = cell[1];
     int it = cell[2];
     const int it_last = cell[3];
     const int e0 = cell[4], e1 = cell[5], e2 = cell[6], e3 = cell[7], e4 = cell[8];   // last iteration of the wave's first five tiles
-    const int range_c0 = a.cell[(size_t)(live ? range : 0) * kColWaves * kWaveInts];  // first tile of the range: wave 0's c0
+    const int range_c0 = a.cell[(size_t)my_range * kColWaves * kWaveInts];            // first tile of the range: wave 0's c0
+    // (the table's address is pinned in the entry block - behind the record's loads, which an asm statement in front of them
+    // would turn into vector loads: left to the compiler it was fetched from the arguments where the DMA loop starts, and the
+    // wait for it there also waited for the record - a round trip to plan memory in front of the first request.  Here it
+    // arrives with the other arguments, behind their one wait.)
+    const float* table = a.table;
+    asm volatile("" : "+s"(table));
     // ---- this column group of every node -> LDS, 1 KB per wave instruction (rows_pad * CW * 4 is a multiple of 1 KB;
     //      row n of the table is zero: padded id slots name it) ----
-    if (live) {
-        const int total = a.rows_pad * CW / 4;                            // float4 pieces
-        const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(a.table + (size_t)cg * a.rows_pad * CW);
+    {
+        const int total = live ? a.rows_pad * CW / 4 : 0;                 // float4 pieces
+        const f32x4* __restrict__ src = reinterpret_cast<const f32x4*>(table + (size_t)cg * a.rows_pad * CW);
         for (int i = wave * 64; i < total; i += kColThreads)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + i + lane),
                                              (__attribute__((address_space(3))) void*)(lds4 + i), 16, 0, 0);
     }
-    do {
-    if (!live) break;
     asm volatile("" ::: "memory");                                         // what follows is requested behind the DMA loads
     int tile_end = e0;
     // sixteen iterations of ids are requested before anything is consumed (a wave has ~13 on PoSE): the stream comes
-    // from HBM once per range, and a loop that asks for it three iterations ahead pays that latency again and again
+    // from HBM once per range, and a loop that asks for it three iterations ahead pays that latency again and again.
+    // A wave with fewer asks for its LAST iteration again instead of what lies behind it (a wave-uniform index: the loads
+    // stay unconditional; the repeat is served by the L1): ids nobody reads took a fifth of the stream's share of the fill,
+    // which runs at the rate the L2 feeds one compute unit.
     const u32x2* __restrict__ sp = a.ids + (size_t)it * 64 + lane;
+    const int it_have = max(it_last - it, 1) - 1;                          // the last iteration the wave has (0: also for none)
     u32x2 wa[8], wb[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) wa[k] = sp[64 * k];
+    for (int k = 0; k < 8; ++k) wa[k] = sp[64 * min(k, it_have)];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) wb[k] = sp[512 + 64 * k];
+    for (int k = 0; k < 8; ++k) wb[k] = sp[64 * min(8 + k, it_have)];
     sp += 1024;
     // direct stores: destination row and scale of this quad in the wave's first four tiles (more tiles: read when they
     // come up).  The staged loop needs neither: its write-out reads them for all the wave's tiles at once.
@@ -351,7 +366,6 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
         o[0] = st0; o[1] = st1; o[2] = __builtin_amdgcn_s_memrealtime(); o[3] = st2;
     }
 #endif
-    } while (0);
     // concat slot: streamed by the whole grid, here last
     gn::side_copy_stream(a.side, blockIdx.x * (int64_t)blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
 }
@@ -428,7 +442,11 @@ gn_status blocked_gather(const gn_graph_plan* plan, int64_t fout, const float* b
     a.ids = reinterpret_cast<const u32x2*>(plan->blk_ids.p); a.dis = plan->blk_dis.p; a.bias = bias;
     a.out = out; a.ld_out = ld_out; a.n = (int)plan->rows; a.rows_pad = plan->blk_rows;
     a.groups = (int)(fout / cw); a.ranges = plan->blk_cells; a.relu = relu; a.side = side; a.next_table = next_table;
+    GN_REQUIRE(a.groups >= 1 && (a.groups & (a.groups - 1)) == 0, "the LDS-staged gather deals its workgroups by shifts: %d column groups are no power of two", a.groups);
     const int per_x = (a.ranges + 7) / 8;
+    a.per_x = per_x;
+    a.group_shift = 0;
+    while ((1 << a.group_shift) < a.groups) ++a.group_shift;
     const int grid = 8 * per_x * a.groups;
     const bool staged = blocked_staged(plan);
     const size_t lds = (size_t)plan->blk_rows * cw * sizeof(float) + (staged ? stage_bytes(plan) : 0);
@@ -559,6 +577,9 @@ extern "C" gn_status gn_graph_plan_build_blocked(gn_graph_plan* plan, int64_t co
     GN_HIP(plan->blk_tile_rows.upload(bl.tile_rows, st));
     GN_HIP(plan->blk_tile_dis.upload(bl.tile_dis, st));
     GN_HIP(plan->blk_ids.upload(bl.ids.data(), bl.ids.size() / 2, st));           // (four 16-bit ids of a lane as two words)
+    // behind the last range's record an EMPTY one (no tiles, no iterations): what the workgroups of a grid of 8 ceil(R / 8)
+    // ranges beyond R walk - the gather has no separate way out for them
+    bl.cell.insert(bl.cell.end(), (size_t)kColWaves * kWaveInts, 0);
     GN_HIP(plan->blk_cell.upload(bl.cell, st));
     GN_HIP(plan->blk_table.alloc((size_t)rows_pad * cols));
     // rows beyond the last node stay zero for the life of the plan (padded id slots name row N): k_col_transform writes
@@ -591,7 +612,7 @@ extern "C" int gn_graph_plan_blocked_gather_kernel(const gn_graph_plan* plan) {
 // tests: the schedule the gather walks, [ranges][16 waves][12] (first tile, end tile, first iteration, end iteration, ...)
 extern "C" int64_t gn_graph_plan_blocked_waves(const gn_graph_plan* plan, int32_t* host_out, int64_t capacity) {
     if (!plan || !plan->blk_ok) return 0;
-    const int64_t count = (int64_t)plan->blk_cell.n;
+    const int64_t count = (int64_t)plan->blk_cells * kColWaves * kWaveInts;    // (without the empty record behind the last range)
     if (host_out) {
         if (capacity < count) return -1;
         if (hipMemcpy(host_out, plan->blk_cell.p, (size_t)count * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) return -1;

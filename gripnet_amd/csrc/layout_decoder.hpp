@@ -294,6 +294,10 @@ struct ClassLayout {
     gn::RawVec<uint32_t> packed, own, mirror;
     std::vector<uint32_t> rel32;
     std::vector<int32_t> wg;
+    // The same rows once per CLASS (a plan has one or three), and every workgroup's class: what a launch of up to 256
+    // workgroups hands over with the kernel arguments, so that the kernel requests its rows without waiting for wg[]
+    int32_t cls_rows[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    std::vector<uint8_t> wg_cls;        // [groups]
 };
 
 // How build_class_layout cuts the node table and the list.  The table: one block, or three of which a class holds two (its
@@ -674,13 +678,17 @@ inline bool describe_workgroups(const ClassShape& sh, const std::vector<int64_t>
     if (G < 1) return false;
     const int dstride = 4 + 4 * walks;
     L.wg.assign((size_t)G * dstride, 0);
+    L.wg_cls.assign((size_t)G, 0);
     for (int x = 0; x < parts; ++x)
         for (size_t l = 0; l < part_wgs[x].size(); ++l) {
             const Wg& w = part_wgs[x][l];
             const int c = w.cls;
-            int32_t* d = L.wg.data() + (parts == 8 ? (size_t)(8 * l + x) : l) * dstride;
+            const size_t at = parts == 8 ? (size_t)(8 * l + x) : l;
+            int32_t* d = L.wg.data() + at * dstride;
             if (sh.nblocks == 1) { d[0] = 0; d[1] = (int32_t)sh.n; d[2] = 0; d[3] = 0; }
             else { d[0] = (int32_t)sh.bstart(c); d[1] = (int32_t)sh.bsize(c); d[2] = (int32_t)sh.bstart((c + 1) % 3); d[3] = (int32_t)sh.bsize((c + 1) % 3); }
+            L.wg_cls[at] = (uint8_t)c;
+            for (int k = 0; k < 4; ++k) L.cls_rows[c][k] = d[k];
             for (int wk = 0; wk < walks; ++wk) {
                 const int g = sh.group_of(x, wk, c);
                 const int64_t nb = grp_batch0[g + 1] - grp_batch0[g];

@@ -349,12 +349,39 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
     const unsigned long long st0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-    // ---- prologue: this wave's window on its stream, the att table ----
+    // ---- prologue: the att table, this wave's window on its stream ----
+    // Order of the REQUESTS (everything is waited for once, in front of the barrier):
+    //   1. the per-wave plan words and the workgroup's destination rows, as scalar loads: plan memory is L2-cold at kernel
+    //      start, and nothing below needs them before step 3;
+    //   2. the att table by LDS-DMA (it needs none of them: behind a wait for them the bulk of the fill started a memory round
+    //      trip late);
+    //   3. what the plan words name: the stream window and the first descriptor pages (the wait for step 1 is here);
+    //   4. what goes through registers and therefore waits for its own loads (which return behind everything requested so far):
+    //      the table's tail rows or the padded table, the zero rows, the side copy.
+    // (Read behind the DMA loads, the destination rows were a vector load with a full wait behind it: the descriptor pages
+    // were requested only once the table had landed.)
     const uint32_t wave_id = (uint32_t)(g * kWaves + wave);
     const uint32_t first_block = a.wave_first[wave_id], n_units = a.wave_units[wave_id];
+    const uint32_t desc_first = a.wave_desc[wave_id];
+    int32_t my_dst[4];
+    {
+        const int32_t* __restrict__ wd = a.wg_dst + (size_t)g * 4;
+#pragma unroll
+        for (int d = 0; d < 4; ++d) my_dst[d] = wd[d];
+    }
+    asm volatile("" ::: "memory");                                             // 1 stays in front of 2
+    if (a.att_dma) {
+        // rows of 32 bases are the LDS rows: 1 KB per wave instruction straight into LDS
+        const int pieces = a.R / 8;
+        const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(a.att);
+        for (int i = wave; i < pieces; i += kWaves)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)i * 64 + lane),
+                                             (__attribute__((address_space(3))) void*)(uintptr_t)(lds0 + (uint32_t)i * 1024u), 16, 0, 0);
+    }
+    asm volatile("" ::: "memory");                                             // 2 stays in front of 3
     // byte offset of this wave's descriptors inside a.desc: uniform, 32 bits (a lane adds its own 4 bytes; the base stays
     // the kernel argument, so that the loads take the scalar-base form and no lane holds a 64-bit address)
-    const uint32_t desc_b = __builtin_amdgcn_readfirstlane(a.wave_desc[wave_id] * 128u);
+    const uint32_t desc_b = __builtin_amdgcn_readfirstlane(desc_first * 128u);
     const unsigned char* __restrict__ descp = reinterpret_cast<const unsigned char*>(a.desc);
     const unsigned char* __restrict__ xp = a.xp;
     const uint32_t lane4 = (uint32_t)lane * 4u;
@@ -378,14 +405,13 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)q * 32),
                                              (__attribute__((address_space(3))) void*)(uintptr_t)(w.ring_base + q * 512u), 16, 0, 0);
     }
+    // unit descriptors of this wave, 32 dwords each (block counts, the chunk's 32 source ids): lane L holds dword L of the
+    // current page of two units, and of the page after it
+    uint32_t descv = n_units ? *reinterpret_cast<const uint32_t*>(descp + (desc_b + lane4)) : 0u;
+    uint32_t descn = n_units > 2 ? *reinterpret_cast<const uint32_t*>(descp + (desc_b + 256u + lane4)) : 0u;
+    asm volatile("" ::: "memory");                                             // 3 stays in front of 4
     if (a.att_dma) {
-        // rows of 32 bases are the LDS rows: 1 KB per wave instruction straight into LDS
-        const int pieces = a.R / 8;
-        const u32x4* __restrict__ src = reinterpret_cast<const u32x4*>(a.att);
-        for (int i = wave; i < pieces; i += kWaves)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + (size_t)i * 64 + lane),
-                                             (__attribute__((address_space(3))) void*)(uintptr_t)(lds0 + (uint32_t)i * 1024u), 16, 0, 0);
-        for (int e = pieces * 256 + tid; e < a.R * 32; e += kThreads)
+        for (int e = (a.R / 8) * 256 + tid; e < a.R * 32; e += kThreads)       // the rows behind the last whole piece
             reinterpret_cast<float*>(lds)[e] = a.att[e];
     } else {
         for (int e = tid; e < a.R * 32; e += kThreads) {
@@ -393,13 +419,7 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
             reinterpret_cast<float*>(lds)[e] = b < a.B ? a.att[(size_t)r * a.B + b] : 0.f;
         }
     }
-    // the workgroup's destination rows (read here, not in front of the epilogue's loads: one round trip less behind the loop)
-    int32_t my_dst[4];
-    {
-        const int32_t* __restrict__ wd = a.wg_dst + (size_t)g * 4;
-#pragma unroll
-        for (int d = 0; d < 4; ++d) my_dst[d] = wd[d];
-    }
+    // the workgroup's destination rows (requested in step 1, not in front of the epilogue's loads: one round trip less behind the loop)
     int nd = 0;
 #pragma unroll
     for (int d = 0; d < kMaxD; ++d) nd += my_dst[d] >= 0 ? 1 : 0;
@@ -413,10 +433,6 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
             a.side.dst[i * a.side.ld_dst + cc] = a.side.mode ? fabsf(v) : v;
         }
     }
-    // unit descriptors of this wave, 32 dwords each (block counts, the chunk's 32 source ids): lane L holds dword L of the
-    // current page of two units, and of the page after it
-    uint32_t descv = n_units ? *reinterpret_cast<const uint32_t*>(descp + (desc_b + lane4)) : 0u;
-    uint32_t descn = n_units > 2 ? *reinterpret_cast<const uint32_t*>(descp + (desc_b + 256u + lane4)) : 0u;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #ifdef GN_STAMPS
@@ -586,6 +602,9 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
 #pragma unroll
     for (int d = 0; d < kMaxD; ++d) sum[d] = (f32x4)(0.f);
     {
+        // (Tried in round 24: the twelve offsets k computed once, between the shares' store and the barrier, so that this
+        // loop is LDS reads and FMAs only - the contraction's stamp 1.7 -> 1.5 us, the stage in front of it 2.2 -> 2.7 us:
+        // the offsets' divisions landed in front of a barrier the whole workgroup waits at.  Dropped, profiles/r24_kernel_heads.md.)
         int base = sl / FIN, feat = sl - base * FIN;                           // of row j * slices + sl, advanced by slices per step
         const int dbase = slices / FIN, dfeat = slices - dbase * FIN;
 #pragma unroll

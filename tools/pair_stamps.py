@@ -40,6 +40,8 @@ def main():
     print("entry spread {:.1f} us; prologue done at {:.1f} mean {:.1f} max; loop done at {:.1f} mean {:.1f} max; exit {:.1f} mean {:.1f} max".format(
         us(b[:, 0].max() - t0), us(b[:, 1].mean() - t0), us(b[:, 1].max() - t0), us(b[:, 2].mean() - t0), us(b[:, 2].max() - t0),
         us(b[:, 3].mean() - t0), us(b[:, 3].max() - t0)))
+    pro = us(b[:, 1] - b[:, 0])
+    print("prologue per wave (entry -> barrier passed): mean {:.2f} p90 {:.2f} max {:.2f} us".format(pro.mean(), np.percentile(pro, 90), pro.max()))
     loop = us(b[:, 2] - b[:, 1])
     units = (buf[buf[:, 0] > 0][:, 7] >> np.uint64(32)).astype(np.float64)
     blocks = (buf[buf[:, 0] > 0][:, 7] & np.uint64(0xffffffff)).astype(np.float64)
