@@ -112,6 +112,73 @@ def case_a(model, side, seed=5):
     return c
 
 
+D_RELATION_COUNTS = ((1, 31), (2, 2), (4, 31), (5, 32), (7, 70), (8, 1), (10, 33), (11, 30))
+D_ENTITY_COUNTS = ((3, 31), (4, 2), (5, 31), (9, 32), (20, 70)) + tuple((e, 1) for e in range(30, 64)) + ((80, 30),)
+D_HIDDEN = (8, 36, 72, 35)
+"""One column block on 8 lanes; 9 units on 16 lanes; 18 units - a second column block of the reductions and a second trip of
+the query kernel's column loop; the scalar path with three column blocks."""
+
+
+def _repeat(counts):
+    return torch.cat([torch.full((c,), i, dtype=torch.long) for i, c in counts])
+
+
+def case_d(model, side, H, shuffled, seed=31):
+    """Rows of the passes over the B positives (chunks of ROW_CHUNK = 32 records) that lie in more than one chunk: n = 90,
+    R = 12, K = 5, B = 230 = 7 * 32 + 6, gamma as case_c argues (12 at H % 4 == 0, 1 on the scalar path).  In key order the
+    relations D_RELATION_COUNTS hold the positions
+      1: 0-30    2: 31-32    4: 33-63    5: 64-95    7: 96-165    8: 166    10: 167-199    11: 200-229
+    so relation 2 is a two-record row across a cut (the chunk's second slot, then the next chunk's first), 4 ends on a cut, 5
+    is exactly one aligned chunk (final, never a partial), 7 begins on a cut and spans three chunks with chunk 4 wholly inside
+    it, chunk 5 holds the end of 7, the one-record row 8 and the start of 10, chunk 6 the end of 10 and the start of 11, the
+    last chunk holds six records, and the relations 0, 3, 6 and 9 are empty.  The fixed entities D_ENTITY_COUNTS cut the
+    same way up to position 165 (3, 4, 5, 9, 20), then come 34 entities of one positive each and entity 80 on 200-229; they
+    are dealt to the positives in a random order, so the entity pass sorts a real permutation and adds its straddling rows
+    onto the candidate pass's sums (the candidates are uniform over the entities 0..88: the rows 3, 9 and 20 of d_ent get
+    both).  Entity 89 appears nowhere.
+    `shuffled`: the positives (with their candidates and upstream rows) in a random order, as a training batch has them;
+    otherwise THAT block reordered by et.sort(stable=True) - what a stable sort by relation makes of it.  The upstream
+    `up` [B, K] belongs to the positives and moves with them."""
+    n, R, K, B = 90, 12, 5, 230
+    gamma = 12.0 if H % 4 == 0 else 1.0
+    gen = torch.Generator().manual_seed(seed)
+    ent, rel = kc.tables(model, n, R, H, gamma, gen)
+    et = _repeat(D_RELATION_COUNTS)
+    fixed = _repeat(D_ENTITY_COUNTS)
+    assert et.numel() == B and fixed.numel() == B
+    fixed = fixed[torch.randperm(B, generator=gen)]
+    other = torch.randint(0, n - 1, (B,), generator=gen)           # the member that the candidates replace: never read
+    negatives = torch.randint(0, n - 1, (B, K), generator=gen)
+    up = torch.linspace(-1.0, 1.0, B * K).view(B, K)
+    order = torch.randperm(B, generator=gen)
+    if not shuffled:
+        order = order[et[order].sort(stable=True).indices]
+    et, fixed, other, negatives, up = et[order], fixed[order], other[order], negatives[order].contiguous(), up[order].contiguous()
+    positive = torch.stack([fixed, other]) if side == "tail" else torch.stack([other, fixed])
+    return _case(model, side, n, R, H, gamma, ent, rel, positive, et, negatives, up=up, unused_entity=n - 1,
+                 empty_relations=(0, 3, 6, 9))
+
+
+def case_e(model, side):
+    """More positives than the query kernel's grid of 16 384 workgroups: B = 16 385, K = 2, H = 4, n = 500, R = 9.  A
+    relation owns about 1 820 positives: the combine adds the partials of some 58 chunks of ROW_CHUNK records."""
+    return random_case(model, side, 500, 9, 4, 16385, 2, seed=41)
+
+
+def straddling_rows(keys, chunk=None):
+    """{key: (first, last + 1)} of the rows of `keys` in key order whose records lie in more than one chunk of `chunk`
+    records (ROW_CHUNK by default): the rows that leave the reduction as chunk partials and are added by the combine."""
+    chunk = ROW_CHUNK if chunk is None else chunk
+    counts = torch.bincount(keys)
+    ends = torch.cumsum(counts, 0)
+    out = {}
+    for key, (count, end) in enumerate(zip(counts.tolist(), ends.tolist())):
+        begin = end - count
+        if count > 0 and begin // chunk != (end - 1) // chunk:
+            out[key] = (begin, end)
+    return out
+
+
 def with_bad_ids(c):
     """A copy of the case's block with a negative and a too large id in `fixed`, in `et` and in `negatives`:
     (positive, et, negatives, bad rows, bad elements).  (Not sorted any more: the relation pass sorts.)"""

@@ -1,5 +1,6 @@
 """The candidate-block modes of KGEModel without a GPU: the expansion that defines their reference, the loss on raw scores
-against its formula in float64, and the refusals of the module (an unknown mode, candidates of the wrong shape)."""
+against its formula in float64, the refusals of the module (an unknown mode, candidates of the wrong shape), and what the
+gradient cases of tests/test_gpu_kge_batch.py are built to hold (rows across the chunks of the passes over the positives)."""
 import math
 
 import pytest
@@ -7,6 +8,7 @@ import torch
 
 import gripnet_amd
 import kge_batch_cases as kb
+import kge_cases as kc
 from gripnet_amd.kge import self_adversarial_loss
 
 
@@ -34,6 +36,121 @@ def test_case_a_holds_what_it_promises():
     assert bool((c.et[1:] >= c.et[:-1]).all()) and set(c.et.tolist()) == {1, 2, 3, 4, 5}
     h = kb.case_a("RotatE", "head")
     assert int((h.sample[0] == 0).sum()) == 2049 and int((h.sample[1] == 1).sum()) == 3 * h.K
+
+
+def _kinds(keys, rows, chunk=kb.ROW_CHUNK):
+    """Which kinds of rows the passes over the positives meet when the records are in the order of `keys`."""
+    counts = torch.bincount(keys, minlength=rows).tolist()
+    straddlers = kb.straddling_rows(keys, chunk)
+    kinds = set()
+    touched = {}
+    for key, (begin, end) in straddlers.items():
+        kinds.add("straddler from inside a chunk" if begin % chunk else "straddler from a cut")
+        first, last = begin // chunk, (end - 1) // chunk
+        if last - first >= 2:
+            kinds.add("whole interior chunk")
+        for c in range(first, last + 1):
+            touched.setdefault(c, set()).add(key)
+    if any(len(rows_of) == 2 for rows_of in touched.values()):
+        kinds.add("chunk with two straddlers")
+    assert all(len(rows_of) <= 2 for rows_of in touched.values())   # (a chunk has one row that came in and one that goes on)
+    begin = 0
+    for key, count in enumerate(counts):
+        if count == chunk and begin % chunk == 0:
+            kinds.add("aligned one-chunk row")
+        if count == 1:
+            kinds.add("one-record row")
+        if count == 0:
+            kinds.add("empty row")
+        begin += count
+    if keys.numel() % chunk:
+        kinds.add("short last chunk")
+    return kinds, straddlers
+
+
+@pytest.mark.parametrize("side", kb.SIDES)
+def test_case_d_has_rows_across_chunks_of_every_kind(side):
+    """Pins what kge_batch_cases.case_d is there for, so that an edit of the builder cannot lose it: in the order of the
+    relation pass and in the order of the entity pass, rows of every kind the chunked reduction tells apart.  Case A, the
+    only other gradient case with more positives than a chunk, has no such row in the relation pass and at most one
+    two-record row in the entity pass: the reason for case D."""
+    everything = {"straddler from inside a chunk", "straddler from a cut", "whole interior chunk", "chunk with two straddlers",
+                  "aligned one-chunk row", "one-record row", "empty row", "short last chunk"}
+    for shuffled in (False, True):
+        c = kb.case_d("TransE", side, 8, shuffled)
+        assert (c.n, c.R, c.K, c.B) == (90, 12, 5, 230) and c.B == 7 * kb.ROW_CHUNK + 6
+        assert torch.bincount(c.et, minlength=c.R).tolist() == [0, 31, 2, 0, 31, 32, 0, 70, 1, 0, 33, 30]
+        fixed = kb.fixed_of(c.positive, side)
+        kinds, straddlers = _kinds(c.et, c.R)
+        assert kinds == everything
+        assert straddlers == {2: (31, 33), 7: (96, 166), 10: (167, 200), 11: (200, 230)}
+        assert all(int(torch.bincount(c.et, minlength=c.R)[r]) == 0 for r in c.empty_relations)
+        # the entity pass: the same cuts up to position 165, then single records and entity 80 across the last cut; no
+        # chunk of it holds two straddlers (the counts leave entity 20's last chunk to rows of one record)
+        kinds, straddlers = _kinds(fixed, c.n)
+        assert kinds == everything - {"chunk with two straddlers"}
+        assert straddlers == {4: (31, 33), 20: (96, 166), 80: (200, 230)}
+        # rows of d_ent that get a candidate-pass sum and a straddling row-pass sum
+        assert all(bool((c.negatives == e).any()) for e in (3, 4, 9, 20, 80))
+        assert not bool((c.negatives == c.unused_entity).any()) and not bool((c.positive == c.unused_entity).any())
+        # a real permutation for the entity pass's sort, and (shuffled) for the relation pass's
+        assert not bool((fixed[1:] >= fixed[:-1]).all())
+        assert bool((c.et[1:] >= c.et[:-1]).all()) == (not shuffled)
+    # the two orders are one block: the sorted one is the stable sort of the shuffled one
+    s, o = kb.case_d("RotatE", side, 35, True), kb.case_d("RotatE", side, 35, False)
+    order = s.et.sort(stable=True).indices
+    assert int((order != torch.arange(s.B)).sum()) > s.B // 2
+    assert torch.equal(s.et[order], o.et) and torch.equal(s.positive[:, order], o.positive)
+    assert torch.equal(s.negatives[order], o.negatives) and torch.equal(s.up[order], o.up)
+    assert s.gamma == 1.0 and kb.case_d("RotatE", side, 72, True).gamma == 12.0
+    # case A: no relation's row straddles, and no entity's - but for ComplEx's draw of the fixed entities, which puts the two
+    # records of entity 46 on either side of position 32: a two-chunk row from inside a chunk, the one kind case A ever has
+    across = {"straddler from inside a chunk", "straddler from a cut", "whole interior chunk", "chunk with two straddlers"}
+    for model in kc.MODELS:
+        a = kb.case_a(model, side)
+        assert a.B > kb.ROW_CHUNK and kb.straddling_rows(a.et) == {}
+        kinds, straddlers = _kinds(kb.fixed_of(a.positive, side), a.n)
+        assert straddlers == ({46: (31, 33)} if model == "ComplEx" else {})
+        assert kinds & across <= {"straddler from inside a chunk"}
+
+
+def test_case_e_is_beyond_one_grid_of_the_query_kernel():
+    for side in kb.SIDES:
+        c = kb.case_e("DistMult", side)
+        assert c.B == 256 * 64 + 1 and c.K == 2 and c.H == 4
+        busiest = int(torch.bincount(c.et).max())
+        assert 1750 <= busiest <= 1950                              # about B / R = 1 820: some 58 chunks in the combine
+        assert len(kb.straddling_rows(c.et)) == c.R
+        # K below CHUNK / ROW_CHUNK: the chunks of the passes over the positives size the workspace's partials
+        assert c.K < kc.CHUNK // kb.ROW_CHUNK and c.B > kb.ROW_CHUNK
+
+
+@pytest.mark.parametrize("side", kb.SIDES)
+def test_the_bounds_take_the_depth_of_the_busiest_row(side, monkeypatch):
+    """The GPU tests' c_g counts the additions of the longest path: query_reduction_depth must be asked for the busiest
+    relation and the busiest fixed entity of the case at hand - 70 positives in case D, about 1 820 in case E."""
+    import test_gpu_kge_batch as gpu_tests                          # (its helpers run on the CPU; its tests need the GPU)
+    asked = []
+    depth = kb.query_reduction_depth
+
+    def recording(K, B_per_row, lanes):
+        asked.append((K, B_per_row, lanes))
+        return depth(K, B_per_row, lanes)
+
+    monkeypatch.setattr(kb, "query_reduction_depth", recording)
+    for H, lanes, by_hand in ((8, 8, 1 + 32 + 1 + 32 + 3 + 1), (72, 16, 1 + 16 + 2 + 16 + 3 + 1)):
+        c = kb.case_d("DistMult", side, H, True)
+        del asked[:]
+        gpu_tests._gradient_bounds(c, c.sample, c.et_list, c.up.reshape(-1), True)
+        assert asked == [(5, 70, lanes), (5, 70, lanes)]            # (the busiest fixed entity, the busiest relation)
+        assert depth(5, 70, lanes) == by_hand
+    c = kb.case_e("DistMult", side)
+    busiest_rel = int(torch.bincount(c.et).max())
+    busiest_fixed = int(torch.bincount(kb.fixed_of(c.positive, side)).max())
+    del asked[:]
+    gpu_tests._gradient_bounds(c, c.sample, c.et_list, torch.linspace(-1.0, 1.0, c.E), True)
+    assert asked == [(2, busiest_fixed, 8), (2, busiest_rel, 8)]
+    assert depth(2, busiest_rel, 8) == 1 + 32 + 1 + 32 + -(-busiest_rel // 32) + 1
 
 
 def _log_sigmoid(x):
