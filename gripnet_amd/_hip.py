@@ -1016,13 +1016,23 @@ class RgcnPlan(Handle):
             _recorder.keep.append(ei)
         return dw
 
-    def _workspace(self, x, fin, fout, bases, flags=0):
+    def _choice(self, x, fin, fout, bases, flags):
+        """(kernel code, workspace bytes) of a forward with these shapes and flags: on `x` (its alignment picks the kernel),
+        or, without one (a null x), on an aligned input - what gn_rgcn_forward_path and gn_rgcn_workspace_bytes answer."""
         need = C.c_size_t(0)
-        load().gn_rgcn_forward_choice(self._h, x.data_ptr(), ld(x), fin, fout, bases, flags, C.byref(need))   # (x: its alignment picks the kernel)
-        need = int(need.value)
+        at = (None, 0) if x is None else (x.data_ptr(), ld(x))
+        code = int(load().gn_rgcn_forward_choice(self._h, at[0], at[1], fin, fout, bases, flags, C.byref(need)))
+        return code, int(need.value)
+
+    def _scratch(self, need):
+        """The plan's scratch buffer, grown to `need` bytes."""
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
-        return self._ws, need
+        return self._ws
+
+    def _workspace(self, x, fin, fout, bases, flags=0):
+        need = self._choice(x, fin, fout, bases, flags)[1]
+        return self._scratch(need), need
 
     @staticmethod
     def mode_flags(fast=False, path="auto"):
@@ -1031,10 +1041,7 @@ class RgcnPlan(Handle):
 
     def path(self, fin, fout, bases, fast=False, path="auto", x=None):
         """Name of the kernel a forward with these shapes and flags takes (on `x` when given, else on an aligned input)."""
-        if x is not None:
-            code = int(load().gn_rgcn_forward_choice(self._h, x.data_ptr(), ld(x), fin, fout, bases, self.mode_flags(fast, path), None))
-        else:
-            code = int(load().gn_rgcn_forward_path(self._h, fin, fout, bases, self.mode_flags(fast, path)))
+        code = self._choice(x, fin, fout, bases, self.mode_flags(fast, path))[0]
         return RGCN_PATH_NAMES.get(code, "?")
 
     def weighted_supported(self, fin, fout, bases) -> bool:
@@ -1055,10 +1062,8 @@ class RgcnPlan(Handle):
         fin, fout, bases = x.shape[1], basis.shape[2], basis.shape[0]
         self.build_positions()
         need = int(load().gn_rgcn_weighted_workspace_bytes(self._h, fin, fout, bases))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=self.device)
         _call("gn_rgcn_forward_weighted_f32", self._h, ptr(x), ld(x), fin, ptr(basis), ptr(att), bases, ptr(root), ptr(bias), fout,
-              int(bool(relu)), GN_RGCN_PARTIAL if partial else GN_RGCN_SUM, ptr(edge_weight), ptr(out), ld(out), ptr(self._ws), need,
+              int(bool(relu)), GN_RGCN_PARTIAL if partial else GN_RGCN_SUM, ptr(edge_weight), ptr(out), ld(out), ptr(self._scratch(need)), need,
               stream_ptr(x.device))
         return out
 

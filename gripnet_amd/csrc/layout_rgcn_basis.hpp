@@ -11,6 +11,10 @@ namespace gn_layout {
 
 constexpr int kRelDwItemEdges = 512;  // rgcn_basis.hip: edges of one work item of the general relational weight gradient
 constexpr int kBasisHeavyEdges = 512; // rgcn_basis.hip: destination rows with more incoming edges are walked by a whole workgroup
+constexpr int kBasisTiles = 16, kBasisTilesSum = 32;   // accumulator tiles (16 bases x 16 features) of a row: the mean's kernels; the sum's and the weighted ones (64 bases x 128 features)
+constexpr int64_t kSlabBytes = 256ll << 20;            // rows of U in flight between the gather and the dense product (round 6: 64 MB cut the all-nodes
+                                                       // baseline's first layer - 19,726 rows of 4.3 KB - into two slabs: two gather launches that each
+                                                       // drew every work item of all rows, two products)
 
 // ---- relational layer of any size (rgcn_basis.hip): the rows' degree order and the weight gradient's work items ---------------------
 // Rows by in-degree, largest first (a counting sort; ties by row id), and the number of rows a whole workgroup walks.

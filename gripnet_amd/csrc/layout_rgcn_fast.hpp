@@ -12,6 +12,8 @@
 
 namespace gn_layout {
 
+constexpr int kFastFout = 32;                            // out_features of the layer this kernel is built for,
+constexpr int kFastMaxFin = 64;                          // in_features: 16, 32, 48 or 64 (the finalisation alone: any up to 64)
 constexpr int kFastGroups = 256;                         // persistent workgroups = CUs of an MI355X
 constexpr int kFastChunk = 4096;                         // packed words per work item = LDS edge buffer (16 KB)
 constexpr int kFastItemEdges = kFastChunk - 3 * 128;     // edges per work item: every one of the 128 slot lists is padded to 4 words

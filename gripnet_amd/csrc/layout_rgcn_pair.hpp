@@ -12,8 +12,14 @@
 namespace gn_layout {
 
 // ---- relational layer, destination-major kernel (rgcn_pair.hip) -----------------------------------------------------------
-constexpr int kPairWaves = 16;             // waves of a workgroup
-constexpr int kPairRowBytes = 128;         // LDS stride of an att row
+constexpr int kPairWaves = 16;             // waves of a workgroup: four per SIMD, 128 registers each, one destination row per wave
+constexpr int kPairThreads = kPairWaves * 64;
+constexpr int kPairLdsBytes = 160 * 1024;  // the workgroup's LDS: the compute unit's
+constexpr int kPairRowBytes = 128;         // LDS stride of an att row (32 bases; fewer: zero padded)
+// what the kernel is instantiated for (rgcn_route.hpp holds the rule)
+constexpr int kPairMaxFin = 64, kPairMaxFout = 64, kPairMaxBases = kPairRowBytes / 4;
+constexpr int kPairMaxTiles = 6;           // (fin / 16) * ceil(bases / 16): accumulator tiles of a lane
+constexpr int kPairRegRows = 16, kPairRegRowsWide = 12;   // rows of basis a thread holds in registers in the epilogue; at fin 48 and 64
 constexpr int kPairMaxD = 3;               // destination rows per workgroup
 constexpr int kPairSectionCap = 64;        // blocks of a section inside one unit
 constexpr int kPairSlackBlocks = 192;      // readable blocks behind the last wave's stream (the window reads ahead)

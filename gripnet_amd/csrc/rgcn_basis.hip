@@ -14,7 +14,7 @@
 // the root term, the bias and the activation.  Workspace: the slab (<= 256 MB) + the stacked weights, independent of
 // R and N; the edges come from the plan's destination-major list (key = relation * N + source), 4 bytes per edge.
 #include "common.h"
-#include "layout_rgcn_basis.hpp"
+#include "rgcn_route.hpp"
 
 namespace {
 
@@ -28,10 +28,7 @@ __device__ __forceinline__ f32x4 basis_mfma(float a, float b, f32x4 c) { return 
 
 constexpr int kBasisThreads = 512, kBasisWaves = kBasisThreads / 64;   // eight waves: a destination row per wave at a time, or a heavy row per workgroup
 constexpr int kHeavyEdges = gn_layout::kBasisHeavyEdges;               // rows with more incoming edges are walked by a whole workgroup
-constexpr int kBasisTiles = 16, kBasisTilesSum = 32;                   // accumulator tiles (16 bases x 16 features) of a row: the mean's kernels; the sum's and the weighted ones (64 bases x 128 features)
-constexpr int64_t kSlabBytes = 256ll << 20;        // rows of U in flight between the gather and the dense product (round 6: 64 MB cut the all-nodes
-                                                   // baseline's first layer - 19,726 rows of 4.3 KB - into two slabs: two gather launches that each
-                                                   // drew every work item of all rows, two products)
+using gn_layout::kBasisTilesSum;                                       // accumulator tiles the kernels are instantiated up to (rgcn_route.hpp holds the rule)
 
 struct BasisArgs {
     const float* x; int64_t ld_x; int fin;
@@ -328,32 +325,7 @@ __global__ void k_basis_weights(const float* __restrict__ basis, const float* __
         w[t] = t < nb ? basis[t] : (t < nb + nr ? root[t - nb] : 0.f);
 }
 
-struct BasisLayout {
-    int kp;
-    int64_t slab_rows, slabs;
-    size_t w_off, q_off, o_off, u_off, total;     // o_off: (several slabs) [slabs] heavy counts, then [N] the slabs' own orders
-};
-
-BasisLayout basis_layout(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
-    BasisLayout l;
-    l.kp = (int)(gn::ceil_div((bases + 1) * fin, 32) * 32);
-    int64_t slab_bytes = kSlabBytes;
-    if (const char* e = getenv("GN_RGCN_SLAB_MB")) {                       // test hook: small slabs (the same bits: a slab is a range of rows)
-        const long mb = atol(e);
-        if (mb >= 1 && mb <= 4096) slab_bytes = (int64_t)mb << 20;
-    }
-    l.slab_rows = std::min<int64_t>(std::max<int64_t>(plan->num_nodes, 1), std::max<int64_t>(256, slab_bytes / ((int64_t)l.kp * 4)));
-    l.slab_rows = std::max<int64_t>(l.slab_rows, gn::ceil_div(std::max<int64_t>(plan->num_nodes, 1), 256));   // at most 256 slabs (one work counter each)
-    l.slabs = gn::ceil_div(std::max<int64_t>(plan->num_nodes, 1), l.slab_rows);
-    l.w_off = 0;
-    l.q_off = ((size_t)l.kp * fout * sizeof(float) + 255) & ~size_t(255);
-    l.o_off = l.q_off + (((size_t)l.slabs * sizeof(unsigned int) + 255) & ~size_t(255));
-    l.u_off = l.o_off + (l.slabs > 1 ? ((((size_t)l.slabs + (size_t)plan->num_nodes) * sizeof(int32_t) + 255) & ~size_t(255)) : 0);
-    l.total = l.u_off + (size_t)l.slab_rows * l.kp * sizeof(float);
-    return l;
-}
-
-// (up to kBasisTiles accumulator tiles for the mean, kBasisTilesSum for the sum and the weighted calls: gn_rgcn_basis_applicable)
+// (up to kBasisTiles accumulator tiles for the mean, kBasisTilesSum for the sum and the weighted calls: rgcn_route.hpp)
 template <int BT, bool WT>
 gn_status launch_bt(int nt, const BasisArgs& a, int grid, hipStream_t st) {
 #define GN_BASIS_CASE(N) case N: if constexpr (BT * N <= kBasisTilesSum) { k_rgcn_basis<BT, N, WT><<<grid, kBasisThreads, 0, st>>>(a); break; } else return gn::fail(GN_ERR_UNSUPPORTED, "unsupported shape")
@@ -510,17 +482,6 @@ gn_status launch_dw(int nt, const RelDwArgs& a, int grid, hipStream_t st) {
     return GN_OK;
 }
 
-// ---- called from rgcn.hip ----
-bool gn_rgcn_basis_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases, bool sum) {
-    if (!plan || !plan->row_order.p || fin < 1 || fin > 128 || bases < 1 || bases > 64 || fout < 1) return false;
-    const int64_t bt = gn::ceil_div(bases, 16), nt = gn::ceil_div(fin, 16);
-    return bt * nt <= (sum ? kBasisTilesSum : kBasisTiles);
-}
-
-size_t gn_rgcn_basis_workspace_bytes(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
-    return basis_layout(plan, fin, fout, bases).total;
-}
-
 extern "C" {
 
 size_t gn_rgcn_weight_grad_workspace_bytes(const gn_rgcn_plan* plan, int64_t fin, int64_t fout) {
@@ -596,15 +557,14 @@ gn_status gn_rgcn_weight_grad_weighted_f32(const gn_rgcn_plan* plan, const int64
 
 }  // extern "C"
 
+// ---- called from rgcn.hip ----
 gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* basis,
                                 const float* att, int64_t bases, const float* root, const float* bias, int64_t fout, int relu,
-                                int partial, int fast_arith, float* out, int64_t ld_out, const gn_side_copy& side, void* ws,
-                                size_t ws_bytes, hipStream_t st, int sum, const float* ew) {
+                                int partial, int sum, const float* ew, float* out, int64_t ld_out, const gn_side_copy& side, void* ws,
+                                const gn::route::RelRoute& l, hipStream_t st) {
     // sum (GN_RGCN_SUM): the slab's rows leave undivided and the product adds x root (where there is a root), the bias and the
     // activation as for the mean; ew: the weighted instantiation (its position list has been built: rgcn.hip checks)
     const bool with_root = !partial && root != nullptr;
-    const BasisLayout l = basis_layout(plan, fin, fout, bases);
-    GN_REQUIRE(ws && ws_bytes >= l.total, "workspace too small: the basis-space path needs %zu bytes, got %zu", l.total, ws_bytes);
     const int64_t N = plan->num_nodes;
     float* W = reinterpret_cast<float*>(static_cast<char*>(ws) + l.w_off);
     float* U = reinterpret_cast<float*>(static_cast<char*>(ws) + l.u_off);
@@ -625,13 +585,12 @@ gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_
         GN_LAUNCH_CHECK();
     }
     a.scale = (partial || sum) ? 0 : 1; a.with_x = with_root ? 1 : 0;
-    a.pos = ew ? plan->pos.p : nullptr; a.ew = ew;
+    a.pos = l.wt ? plan->pos.p : nullptr; a.ew = l.wt ? ew : nullptr;
     a.vec = (fin % 16 == 0) && (ld_x % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     // (measured and dropped: the att table staged in LDS - a fifth of the gathered bytes - made the layer 8 % SLOWER: the
     // fill costs more than the L2-resident 64-byte rows; what bounds the kernel is the rate of row gathers from L2 / the
     // Infinity Cache, 6-7 TB/s of 128- and 256-byte pieces of x)
     a.fast_addr = a.vec && (uint64_t)N * (uint64_t)ld_x * 4 < (1ull << 32) && (uint64_t)plan->num_relations * (uint64_t)bases * 4 < (1ull << 32);
-    const int bt = (int)gn::ceil_div(bases, 16), nt = (int)gn::ceil_div(fin, 16);
     // four waves per SIMD on every compute unit where the registers allow (<= 128): two workgroups of eight waves
     const int grid = (int)std::min<int64_t>((int64_t)gn::compute_units() * 2, std::max<int64_t>(plan->heavy_rows, gn::ceil_div(N, kBasisWaves)));
     for (int64_t r0 = 0; r0 < N; r0 += l.slab_rows) {
@@ -641,15 +600,15 @@ gn_status gn_rgcn_basis_forward(const gn_rgcn_plan* plan, const float* x, int64_
         if (l.slabs > 1) { a.order = slab_order + r0; a.n_rows = (int)(r1 - r0); a.slab_heavy = slab_heavy + r0 / l.slab_rows; }
         a.side = r0 == 0 ? side : gn_side_copy{nullptr, 0, nullptr, 0, 0, 0, 0};
         gn_status s;
-        switch (bt) {
-            case 1: s = ew ? launch_bt<1, true>(nt, a, grid, st) : launch_bt<1, false>(nt, a, grid, st); break;
-            case 2: s = ew ? launch_bt<2, true>(nt, a, grid, st) : launch_bt<2, false>(nt, a, grid, st); break;
-            case 3: s = ew ? launch_bt<3, true>(nt, a, grid, st) : launch_bt<3, false>(nt, a, grid, st); break;
-            default: s = ew ? launch_bt<4, true>(nt, a, grid, st) : launch_bt<4, false>(nt, a, grid, st); break;
+        switch (l.bt) {
+            case 1: s = l.wt ? launch_bt<1, true>(l.nt, a, grid, st) : launch_bt<1, false>(l.nt, a, grid, st); break;
+            case 2: s = l.wt ? launch_bt<2, true>(l.nt, a, grid, st) : launch_bt<2, false>(l.nt, a, grid, st); break;
+            case 3: s = l.wt ? launch_bt<3, true>(l.nt, a, grid, st) : launch_bt<3, false>(l.nt, a, grid, st); break;
+            default: s = l.wt ? launch_bt<4, true>(l.nt, a, grid, st) : launch_bt<4, false>(l.nt, a, grid, st); break;
         }
         if (s != GN_OK) return s;
         s = gn_gemm_f32(U, l.kp, 0, nullptr, 0, W, fout, 0, out + r0 * ld_out, ld_out, 0, r1 - r0, fout, l.kp, 1,
-                        partial ? nullptr : bias, ((relu && !partial) ? GN_GEMM_RELU : 0) | (fast_arith ? GN_GEMM_ARITH_FAST : 0) | GN_GEMM_SPLIT_KERNEL, st);
+                        partial ? nullptr : bias, ((relu && !partial) ? GN_GEMM_RELU : 0) | (l.terms == 2 ? GN_GEMM_ARITH_FAST : 0) | GN_GEMM_SPLIT_KERNEL, st);
         if (s != GN_OK) return s;
     }
     return GN_OK;

@@ -24,7 +24,7 @@
 // L2-resident.  The matrix-core time of (1), 2 N_tile x in x out flops per item at the fp32 MFMA
 // rate (256 flop/clk/CU), is the larger cost below ~10^4 edges per relation.
 #include "common.h"
-#include "layout_rgcn_fast.hpp"
+#include "rgcn_route.hpp"
 #include "plan_device.cuh"
 
 #include <algorithm>
@@ -35,7 +35,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int kFout = 32;                  // out_features of the layer this path is built for
+constexpr int kFout = gn_layout::kFastFout; // out_features of the layer this path is built for
 constexpr int kLpr = kFout / 4;            // float4 per full feature row (slab layout, finalisation)
 constexpr int kNB = 128;                   // destination slots per item = edges in flight per workgroup
 constexpr int kChunk = gn_layout::kFastChunk;     // packed words per work item = LDS edge buffer (16 KB)
@@ -735,11 +735,6 @@ gn_status gn_rgcn_build_fast_segments(gn_rgcn_plan* plan, const int64_t* src, co
 
 // Multi-GPU finalisation: the all-reduced [n, 32] sum is one "slab"; mean / root / bias / activation and the
 // concat slot in a single launch (the general path needs a GEMM launch for the root term first).
-bool gn_rgcn_fast_finalize_applicable(int64_t fin, int64_t fout, int64_t ld_summed, const void* summed) {
-    return !gn::fast_paths_disabled() && fout == kFout && fin >= 1 && fin <= 64 && ld_summed == kFout &&
-           (reinterpret_cast<uintptr_t>(summed) & 15) == 0;
-}
-
 gn_status gn_rgcn_fast_finalize(const gn_rgcn_plan* plan, const float* summed, const float* x, int64_t ld_x, int64_t fin,
                                 const float* root, const float* bias, int relu, float* out, int64_t ld_out,
                                 const gn_side_copy& side, hipStream_t st) {
@@ -750,16 +745,6 @@ gn_status gn_rgcn_fast_finalize(const gn_rgcn_plan* plan, const float* summed, c
     k_rgcn_slab_finalize<<<(int)plan->num_nodes, 256, 0, st>>>(f);
     GN_LAUNCH_CHECK();
     return GN_OK;
-}
-
-bool gn_rgcn_fast_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
-    if (!plan->fast_ok || gn::fast_paths_disabled()) return false;
-    return fout == kFout && (fin == 16 || fin == 32 || fin == 48 || fin == 64) && bases >= 1;
-}
-
-size_t gn_rgcn_fast_workspace_bytes(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
-    const size_t w = ((size_t)plan->num_relations * fin * fout * sizeof(float) + 255) & ~size_t(255);
-    return w + (size_t)plan->fast_groups * plan->num_nodes * fout * sizeof(float);
 }
 
 static gn_status gn_rgcn_fast_weights(const gn_rgcn_plan* plan, int64_t fin, const float* basis, const float* att,
@@ -778,17 +763,11 @@ static gn_status gn_rgcn_fast_weights(const gn_rgcn_plan* plan, int64_t fin, con
 gn_status gn_rgcn_fast_forward(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin,
                                const float* basis, const float* att, int64_t bases, const float* root,
                                const float* bias, int64_t fout, int relu, int partial, float* out,
-                               int64_t ld_out, const gn_side_copy& side, void* ws, size_t ws_bytes, hipStream_t st) {
-    GN_REQUIRE(ld_x % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "x must be 16-byte aligned with ld_x %% 4 == 0");
-    const int64_t N = plan->num_nodes, R = plan->num_relations;
-    GN_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 15) == 0, "workspace must be 16-byte aligned");
+                               int64_t ld_out, const gn_side_copy& side, void* ws, const gn::route::RelRoute& route, hipStream_t st) {
+    const int64_t N = plan->num_nodes;          // (x in 16-byte rows: the route's rule)
     float* Wt = static_cast<float*>(ws);
-    const size_t w_bytes = ((size_t)R * fin * fout * sizeof(float) + 255) & ~size_t(255);
-    float* slabs = reinterpret_cast<float*>(static_cast<char*>(ws) + w_bytes);
-    {
-        gn_status ws_status = gn_rgcn_fast_weights(plan, fin, basis, att, bases, fout, ws, st);
-        if (ws_status != GN_OK) return ws_status;
-    }
+    float* slabs = reinterpret_cast<float*>(static_cast<char*>(ws) + route.lds_w_bytes);
+    GN_OK_OR_RETURN(gn_rgcn_fast_weights(plan, fin, basis, att, bases, fout, ws, st));
     FastArgs a;
     a.x = x; a.ld_x = ld_x; a.n = (int)N; a.wt = Wt; a.packed = plan->packed.p; a.slot_off = plan->seg_begin.p;
     a.work = reinterpret_cast<const WorkDesc*>(plan->wg_items.p); a.wg_begin = plan->wg_begin.p;

@@ -20,7 +20,7 @@
 // hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi in fp32 accumulators, dropping terms below 2^-24 of |p||x| - the same
 // order as fp32's own rounding.  GN_RGCN_ARITH_FAST keeps two terms and three products (<= 2^-16 per product).
 #include "common.h"
-#include "layout_rgcn_pair.hpp"
+#include "rgcn_route.hpp"
 #include "plan_device.cuh"
 
 #include <numeric>
@@ -34,7 +34,7 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kWaves = gn_layout::kPairWaves, kThreads = kWaves * 64;   // four waves per SIMD: 128 registers each, one destination row per wave
+constexpr int kWaves = gn_layout::kPairWaves, kThreads = gn_layout::kPairThreads;   // four waves per SIMD: 128 registers each, one destination row per wave
 constexpr int kRowBytes = gn_layout::kPairRowBytes;             // LDS stride of an att row (32 bases; fewer: zero padded)
 constexpr int kRingBlocks = 32;            // per-wave window on its stream: 32 blocks of 64 bytes, refilled a quarter (512 B) at a time
 constexpr int kRingBytes = kRingBlocks * 64;
@@ -42,7 +42,7 @@ constexpr int kMaxD = gn_layout::kPairMaxD;                   // destination row
 constexpr int kMaxChunks = 255;            // chunks of 32 sources
 constexpr int kSectionCap = gn_layout::kPairSectionCap;            // (<= 255: a descriptor holds a section's blocks in eight bits)
                                            // pair becomes several units (running sums stay short: fp32 chains of <= 64)
-constexpr int kLdsBytes = 160 * 1024;
+constexpr int kLdsBytes = gn_layout::kPairLdsBytes;
 constexpr int kSlackBlocks = gn_layout::kPairSlackBlocks;          // readable blocks behind the last wave's stream (the window reads ahead)
 
 struct PairArgs {
@@ -717,24 +717,21 @@ using gn::Scratch;   // scoped device scratch (common.h)
 
 bool pair_disabled() { return gn::fast_paths_disabled(); }     // (a kernel is chosen by flag, GN_RGCN_PATH_*; GN_DISABLE_FAST=1 turns every fast path off)
 
-template <int NT, int BT, int TERMS>
-gn_status launch_pair(const gn_rgcn_plan* plan, const PairArgs& a, hipStream_t st) {
-    static int stamp = 0;
-    if (a.xp) {
-        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(k_rgcn_pair<NT, BT, TERMS, true>), kLdsBytes);
-        if (s != GN_OK) return s;
-        const gn::LaunchEvents ev = gn::take_launch_events();
-        if (ev.start || ev.stop) hipExtLaunchKernelGGL((k_rgcn_pair<NT, BT, TERMS, true>), dim3(plan->pair_groups), dim3(kThreads), kLdsBytes, st, ev.start, ev.stop, 0, a, stamp++);
-        else k_rgcn_pair<NT, BT, TERMS, true><<<plan->pair_groups, kThreads, kLdsBytes, st>>>(a, stamp++);
-    } else {
-        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(k_rgcn_pair<NT, BT, TERMS, false>), kLdsBytes);
-        if (s != GN_OK) return s;
-        const gn::LaunchEvents ev = gn::take_launch_events();
-        if (ev.start || ev.stop) hipExtLaunchKernelGGL((k_rgcn_pair<NT, BT, TERMS, false>), dim3(plan->pair_groups), dim3(kThreads), kLdsBytes, st, ev.start, ev.stop, 0, a, stamp++);
-        else k_rgcn_pair<NT, BT, TERMS, false><<<plan->pair_groups, kThreads, kLdsBytes, st>>>(a, stamp++);
-    }
+template <int NT, int BT, int TERMS, bool XP>
+gn_status launch_pair(const gn_rgcn_plan* plan, const PairArgs& a, int stamp, hipStream_t st) {
+    gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(k_rgcn_pair<NT, BT, TERMS, XP>), kLdsBytes);
+    if (s != GN_OK) return s;
+    const gn::LaunchEvents ev = gn::take_launch_events();
+    if (ev.start || ev.stop) hipExtLaunchKernelGGL((k_rgcn_pair<NT, BT, TERMS, XP>), dim3(plan->pair_groups), dim3(kThreads), kLdsBytes, st, ev.start, ev.stop, 0, a, stamp);
+    else k_rgcn_pair<NT, BT, TERMS, XP><<<plan->pair_groups, kThreads, kLdsBytes, st>>>(a, stamp);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+template <int NT, int BT, int TERMS>
+gn_status launch_pair(const gn_rgcn_plan* plan, const PairArgs& a, hipStream_t st) {
+    static int stamp = 0;                  // (GN_STAMPS: the launches of these widths alternate between the two stamp sets)
+    return a.xp ? launch_pair<NT, BT, TERMS, true>(plan, a, stamp++, st) : launch_pair<NT, BT, TERMS, false>(plan, a, stamp++, st);
 }
 
 template <int TERMS>
@@ -845,23 +842,10 @@ extern "C" GN_API int gn_debug_read_pair_stamps(unsigned long long* out) {   // 
 }
 #endif
 
-bool gn_rgcn_pair_applicable(const gn_rgcn_plan* plan, int64_t fin, int64_t fout, int64_t bases) {
-    if (!plan || !plan->pair_ok || pair_disabled()) return false;
-    if (fin % 16 != 0 || fin < 16 || fin > 64 || bases < 1 || bases > 32 || fout % 4 != 0 || fout < 4 || fout > 64) return false;
-    const int64_t nt = fin / 16, bt = (bases + 15) / 16;
-    // the waves' shares of U in LDS: 8 waves x 3 rows x (16 bt x fin) floats, plus the slices' sums behind wave 0's
-    const int64_t kp = (16 * bt + 4) * fin;                                    // (four pad floats per feature, see the kernel)
-    const int64_t part = (int64_t)(kWaves + kMaxD) * kp * 4;                   // the waves' shares, the rows' sums
-    const int64_t red = (int64_t)kThreads * kMaxD * 16 + (int64_t)kThreads * 16;   // the slices' sums (padded) reuse the shares' space
-    const int64_t slices = kThreads / (fout / 4), per = (bases * fin + slices - 1) / slices;
-    const int64_t need = (int64_t)kWaves * kp >= (int64_t)kThreads * kMaxD * 4 + kThreads * 4 ? std::max(part, red) : part + red;   // (narrow layers: behind the sums)
-    return need <= kLdsBytes && nt * bt <= 6 && per <= (nt <= 2 ? 16 : 12);   // (rows of basis a thread holds in registers)
-}
-
 gn_status gn_rgcn_pair_forward(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t fin, const float* basis,
                                const float* att, int64_t bases, const float* root, const float* bias, int64_t fout,
-                               int relu, int partial, int fast_arith, float* out, int64_t ld_out, const gn_side_copy& side,
-                               const void* x_planes, hipStream_t st, int basis_transposed) {
+                               int relu, int partial, float* out, int64_t ld_out, const gn_side_copy& side, const void* x_planes,
+                               const gn::route::RelRoute& route, int basis_transposed, hipStream_t st) {
     PairArgs a;
     a.basis_t = basis_transposed ? 1 : 0;
     a.xp = static_cast<const unsigned char*>(x_planes);
@@ -876,6 +860,5 @@ gn_status gn_rgcn_pair_forward(const gn_rgcn_plan* plan, const float* x, int64_t
     a.chunks = plan->pair_chunks; a.relu = relu; a.partial = partial;
     a.att_dma = bases == 32 && (reinterpret_cast<uintptr_t>(att) & 15) == 0;
     a.side = side;
-    const int nt = (int)(fin / 16), bt = (int)((bases + 15) / 16);
-    return fast_arith ? dispatch_pair<2>(plan, a, nt, bt, st) : dispatch_pair<3>(plan, a, nt, bt, st);
+    return route.terms == 2 ? dispatch_pair<2>(plan, a, route.nt, route.bt, st) : dispatch_pair<3>(plan, a, route.nt, route.bt, st);
 }

@@ -368,8 +368,10 @@ GN_API size_t gn_host_scratch_release(void);
  * LDS-accumulator kernel reads aligned rows only: a column slice of a concat at an odd offset takes the general kernel). */
 GN_API size_t gn_rgcn_workspace_bytes(const gn_rgcn_plan* plan, int64_t in_features, int64_t out_features,
                                int64_t num_bases, int flags);
-/* The kernel (GN_RGCN_PATH_*) a gn_rgcn_forward_f32 call on this x takes, and (workspace_bytes, nullable) the scratch it needs;
- * -1 for a null plan or non-positive sizes. */
+/* The kernel (GN_RGCN_PATH_*) a gn_rgcn_forward_f32 call on this x takes (x == NULL: on an aligned one, as the two queries
+ * without x answer), and (workspace_bytes, nullable) the scratch it needs; -1 for a null plan or non-positive sizes.  The
+ * queries answer for a 16-byte aligned `basis` and never refuse; the rules they and the forward share, first one that holds:
+ * the table at the top of gripnet_amd/csrc/rgcn_route.hpp. */
 GN_API int gn_rgcn_forward_choice(const gn_rgcn_plan* plan, const float* x, int64_t ld_x, int64_t in_features,
                                   int64_t out_features, int64_t num_bases, int flags, size_t* workspace_bytes);
 

@@ -3,6 +3,7 @@
 Bar (BASELINE.json north_star): index outputs bit-exact; fp32 outputs within 1e-4 abs of the
 reference.  Most checks are held to a tighter 2e-5 so that regressions show early.
 """
+import ctypes
 import numpy as np
 import os
 
@@ -1198,6 +1199,53 @@ def test_forced_general_path_gets_its_own_workspace(gpu):
                                          conv.root.data_ptr(), None, fout, 1, 16, out.data_ptr(), fout,
                                          None, None, None, 0, _hip.stream_ptr(gpu))
         assert status == _hip.GN_ERR_INVALID_ARG and b"flags" in lib.gn_last_error()
+
+
+@needs_fast_paths
+def test_every_kernel_runs_in_exactly_the_routes_workspace(gpu):
+    """The smallest plan all four kernels take (40 nodes, 3 relations of 100 edges, 16 -> 32 on 2 bases), each kernel forced in
+    turn, on an aligned x and on a view 4 bytes past alignment: the queries answer the line tests/test_rgcn_route.py holds
+    for these facts, a forward handed exactly that many bytes equals the table kernel's result, and one handed a byte fewer
+    is refused."""
+    from test_rgcn_route import route_line
+    n, R, fin, fout, bases = 40, 3, 16, 32, 2
+    g = torch.Generator().manual_seed(11)
+    ei = torch.randint(0, n, (2, 100 * R), generator=g).to(gpu)
+    ranges = torch.tensor([[100 * r, 100 * r + 100] for r in range(R)])
+    plan = _hip.RgcnPlan(ei, ranges, n)
+    x, basis, att, root = (torch.randn(s, generator=g).to(gpu) for s in ((n, fin), (bases, fin, fout), (R, bases), (fin, fout)))
+    flat = torch.empty(n * fin + 1, device=gpu)
+    shifted = flat[1:].view(n, fin).copy_(x)
+    assert x.data_ptr() % 16 == 0 and shifted.data_ptr() % 16 == 4
+    lib = _hip.load()
+
+    def forward(xin, path, ws_bytes):
+        out = torch.full((n, fout), float("nan"), device=gpu)
+        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=gpu)
+        status = lib.gn_rgcn_forward_f32(plan._h, xin.data_ptr(), fin, fin, basis.data_ptr(), att.data_ptr(), bases, root.data_ptr(),
+                                         None, fout, 1, plan.mode_flags(path=path), out.data_ptr(), fout, None, None,
+                                         ws.data_ptr(), ws_bytes, _hip.stream_ptr(gpu))
+        return status, out
+
+    want = None
+    for xin, x_at in ((x, ""), (shifted, " x_at=4")):
+        for path in ("table", "auto", "pair", "lds", "general"):
+            line = route_line("forward nodes=40 rels=3 edges=300 groups=3 fin=16 bases=2 force={}{}".format(_hip.RGCN_PATHS[path], x_at))
+            kernel = line.split()[0]
+            need = int(line.split("ws=")[1].split()[0])
+            assert plan.path(fin, fout, bases, path=path, x=xin) == kernel, (path, x_at, line)
+            choice = ctypes.c_size_t(0)
+            lib.gn_rgcn_forward_choice(plan._h, xin.data_ptr(), fin, fin, fout, bases, plan.mode_flags(path=path), ctypes.byref(choice))
+            assert int(choice.value) == need, (path, x_at, line)
+            if not x_at:                                   # the query without x: an aligned one
+                assert int(lib.gn_rgcn_workspace_bytes(plan._h, fin, fout, bases, plan.mode_flags(path=path))) == need, (path, line)
+            status, out = forward(xin, path, need)
+            assert status == 0, (path, x_at, lib.gn_last_error())
+            want = out if want is None else want           # (the table kernel on the aligned x comes first)
+            close(out, want)
+            if need > 0:
+                status, _ = forward(xin, path, need - 1)
+                assert status == _hip.GN_ERR_INVALID_ARG and b"workspace too small" in lib.gn_last_error(), (path, x_at)
 
 
 # ---- bf16 storage of the gathered table (SURVEY.md 8f row 4) -----------------------------------
