@@ -15,8 +15,9 @@
 #ifndef GN_AGG_U
 #define GN_AGG_U 2
 #endif
+// (the 16-lanes-per-neighbour transform kernels: all sixteen groups of four, a whole padded row of 64 in one request round)
 #ifndef GN_AGG_U_WIDE
-#define GN_AGG_U_WIDE 8
+#define GN_AGG_U_WIDE 16
 #endif
 // Row gathers in flight per lane of k_aggregate_group
 #ifndef GN_AGG_GROUP_U

@@ -283,6 +283,17 @@ __device__ __forceinline__ float tail_bcast(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xf, 0xf, true));
 }
 
+// `token` as it is, in a vector register, behind sixteen gathered rows: one empty statement that reads all of them, so every
+// one of their loads is issued in front of it and every use of what it returns stands behind it.
+__device__ __forceinline__ int rows_landed(int token, const f32x4 (&t)[16]) {
+    asm volatile("" : "+v"(token)
+                 : "v"(t[0]), "v"(t[1]), "v"(t[2]), "v"(t[3]), "v"(t[4]), "v"(t[5]), "v"(t[6]), "v"(t[7]), "v"(t[8]), "v"(t[9]),
+                   "v"(t[10]), "v"(t[11]), "v"(t[12]), "v"(t[13]), "v"(t[14]), "v"(t[15]));
+    return token;
+}
+template <int N>
+__device__ __forceinline__ int rows_landed(int token, const f32x4 (&)[N]) { return token; }   // (the narrow instantiations never ask)
+
 // SPLIT (64 input features): the gathered row is kept in two tables (AggSplit) - lane j of a neighbour's group takes its 16
 // bytes from the head table where 4 j < head_cols, from the tail table otherwise: the same loads, lines, sums and bits as over
 // the materialised concatenation, which then has no reader.
@@ -293,6 +304,7 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
     static_assert(KPL % 4 == 0, "K slice per lane must cover whole float4 groups");
     static_assert(!TAIL || LPE == 16, "the deferred tail transform is the last quad of a 16-lane group");
     static_assert(!SPLIT || !TAIL, "a split source has no deferred tail transform");
+    static_assert(!SPLIT || LPE == 16, "a split source is 64 columns: sixteen lanes a neighbour");
     const int lane = threadIdx.x & 63;
     const int slot = lane / LPE, j = lane % LPE;
     const int c = lane % FOUT, kq = lane / FOUT;
@@ -350,22 +362,44 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
             const float v = a.ell_col ? v0 : (mine < end ? (a.coef ? a.coef[mine] : 1.0f) : 0.f);
             const int cnt = min(kWave, end - base);
             // U groups of S neighbour rows are requested before the first one is consumed (see k_aggregate); wide rows
-            // (16 lanes each: the external layer, a few hundred destination rows of ~30 edges, latency-bound) ask for
-            // eight groups = 32 rows at once
+            // (16 lanes each: the external layer, a few hundred destination rows of 14..47 edges, one wave per SIMD,
+            // latency-bound) ask for all sixteen groups = 64 rows at once: a quarter of pose0-syn's rows have more than 32
+            // neighbours and paid a second dependent round trip at eight groups.  Slot `slot` adds its rows in the order
+            // idx = (it0 + it) * S + slot whatever U is: the bits do not depend on it.
             constexpr int IT = kWave / S, UW = LPE >= 16 ? GN_AGG_U_WIDE : GN_AGG_U, U = IT < UW ? IT : UW;
             for (int it0 = 0; it0 * S < cnt; it0 += U) {
-                float4 t[U];
+                f32x4 t[U];
                 float vv[U];
 #pragma unroll
                 for (int it = 0; it < U; ++it) {
                     const int idx = (it0 + it) * S + slot;
-                    const uint32_t cc = (uint32_t)__shfl((int)cl, idx);
+                    uint32_t cc = (uint32_t)__shfl((int)cl, idx);
                     vv[it] = __shfl(v, idx);
-                    t[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (SPLIT) {
-                        if (idx < cnt) t[it] = *reinterpret_cast<const float4*>(src + (uint64_t)cc * src_ld);
+                    if constexpr (LPE >= 16) {
+                        // Every load of the batch is issued, whatever the row's length: a slot beyond the row's end reads
+                        // row 0 (a row with a neighbour has a table with a row) and what it read is dropped below.  Under
+                        // `if (idx < cnt)` the compiler waits for each load inside its own branch (s_waitcnt vmcnt(0) behind
+                        // every global_load of the batch): a round trip per group of four neighbours, eight in a row of 29.
+                        cc &= (uint32_t)((idx - cnt) >> 31);                       // idx < cnt: all ones
+                        if constexpr (SPLIT) t[it] = *reinterpret_cast<const f32x4*>(src + (uint64_t)cc * src_ld);
+                        else t[it] = *reinterpret_cast<const f32x4*>(a.table + (int64_t)cc * a.ld_table + 4 * j);
                     } else {
-                        if (idx < cnt) t[it] = *reinterpret_cast<const float4*>(a.table + (int64_t)cc * a.ld_table + 4 * j);
+                        t[it] = (f32x4)(0.f);
+                        if (idx < cnt) t[it] = *reinterpret_cast<const f32x4*>(a.table + (int64_t)cc * a.ld_table + 4 * j);
+                    }
+                }
+                int cnt_behind = cnt;                                              // (the row's length for what follows the loads)
+                if constexpr (LPE >= 16) {
+                    // A slot without a row becomes +0 through a bit mask whose operand - the row's length - comes out of
+                    // rows_landed: no use of a loaded row can stand in front of the last request.  (Left to itself the
+                    // compiler turned the mask back into a select, consumed the first rows in front of the last requests
+                    // to save registers - one wave per SIMD has them - and made those a second and third trip.)
+                    cnt_behind = rows_landed(cnt, t);
+#pragma unroll
+                    for (int it = 0; it < U; ++it) {
+                        const uint32_t keep = (uint32_t)(((it0 + it) * S + slot - cnt_behind) >> 31);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) t[it][k] = __uint_as_float(__float_as_uint(t[it][k]) & keep);
                     }
                 }
                 if constexpr (TAIL) {
@@ -386,13 +420,22 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
                             for (int cc = 0; cc < 4; ++cc) h[cc] = fmaxf(h[cc], 0.f);
                         }
                         // (a slot beyond the row's end stays zero: relu(b2) is not)
-                        if (j >= 12 && (it0 + it) * S + slot < cnt) t[it] = make_float4(h[0], h[1], h[2], h[3]);
+                        if (j >= 12 && (it0 + it) * S + slot < cnt_behind) t[it] = h;
                     }
                 }
 #pragma unroll
                 for (int it = 0; it < U; ++it) {
-                    acc[0] += vv[it] * t[it].x; acc[1] += vv[it] * t[it].y; acc[2] += vv[it] * t[it].z; acc[3] += vv[it] * t[it].w;
+                    // The roundings of `acc[k] += vv * t[k]` as this loop has always been compiled, written out: features 0 and
+                    // 1 of a lane fused, 2 and 3 as a rounded product and a sum (the compiler's choice with contraction left
+                    // to it; it chose otherwise once the loads moved, and every output of the layer changed in its last bit).
+#pragma clang fp contract(off)
+                    acc[0] = __builtin_fmaf(vv[it], t[it].x, acc[0]);
+                    acc[1] = __builtin_fmaf(vv[it], t[it].y, acc[1]);
+                    const float pz = vv[it] * t[it].z, pw = vv[it] * t[it].w;
+                    acc[2] = acc[2] + pz;
+                    acc[3] = acc[3] + pw;
                 }
+                if constexpr (U == IT) break;                                      // (one trip, said so: it0 is the constant 0, not sixteen scalars)
             }
         }
 #pragma unroll

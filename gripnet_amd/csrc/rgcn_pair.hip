@@ -604,7 +604,12 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
     {
         // (Tried in round 24: the twelve offsets k computed once, between the shares' store and the barrier, so that this
         // loop is LDS reads and FMAs only - the contraction's stamp 1.7 -> 1.5 us, the stage in front of it 2.2 -> 2.7 us:
-        // the offsets' divisions landed in front of a barrier the whole workgroup waits at.  Dropped, profiles/r24_kernel_heads.md.)
+        // the offsets' divisions landed in front of a barrier the whole workgroup waits at.  Dropped, profiles/r24_kernel_heads.md.
+        // Tried in round 26: the offsets from a table of 16-bit entries in the LDS behind the stream windows, filled in the prologue
+        // - the contraction 1.7 -> 1.6 us, the prologue 1.76 -> 2.08 us per wave; the shares' sum with both items of a wave in one
+        // round of reads and the final fold with sixteen slices at once - the workgroup's exit 6.7 us behind its slowest wave, as
+        // with this code (shares summed at 3.4, contraction done at 5.0 against 5.1).  All three dropped, none of it is in the source:
+        // there is one contraction loop and no table.  profiles/r26_epilogue_and_rows.md.)
         int base = sl / FIN, feat = sl - base * FIN;                           // of row j * slices + sl, advanced by slices per step
         const int dbase = slices / FIN, dfeat = slices - dbase * FIN;
 #pragma unroll
