@@ -66,7 +66,7 @@ __device__ __forceinline__ void finish_row(const AggArgs& a, int row, int fcol, 
         float val = MEAN && a.rowdiv ? acc[t] / div : acc[t];
         if (MEAN && a.addend) val += a.addend[(int64_t)row * a.ld_addend + fcol + t];
         if (a.bias) val += a.bias[fcol + t];
-        if (a.relu) val = fmaxf(val, 0.f);
+        if (a.relu) val = gn::relu_keep_nan(val);
         acc[t] = val;
     }
     float* dst = a.out + (int64_t)row * a.ld_out + fcol;
@@ -417,7 +417,7 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
                         }
                         if (tail.relu) {
 #pragma unroll
-                            for (int cc = 0; cc < 4; ++cc) h[cc] = fmaxf(h[cc], 0.f);
+                            for (int cc = 0; cc < 4; ++cc) h[cc] = gn::relu_keep_nan(h[cc]);
                         }
                         // (a slot beyond the row's end stays zero: relu(b2) is not)
                         if (j >= 12 && (it0 + it) * S + slot < cnt_behind) t[it] = h;
@@ -451,7 +451,7 @@ __device__ __forceinline__ void aggregate_transform(const AggArgs& a, const floa
         for (int off = FOUT; off < kWave; off <<= 1) part += __shfl_xor(part, off);
         if (kq == 0) {
             float val = part + bias;
-            if (a.relu) val = fmaxf(val, 0.f);
+            if (a.relu) val = gn::relu_keep_nan(val);
             a.out[(int64_t)row * a.ld_out + c] = val;
             if (a.split.planes) write_split(a.split, row, a.split.col_main + c, val);
         }
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(256) void k_aggregate_transform_q(AggArgs a, const 
         part = agg_dpp_add<0x4E>(part);                          // quad_perm [2,3,0,1]
         if (j == 0) {
             float val = part + bias;
-            if (a.relu) val = fmaxf(val, 0.f);
+            if (a.relu) val = gn::relu_keep_nan(val);
             a.out[(int64_t)row * a.ld_out + q] = val;
         }
     }
@@ -657,7 +657,7 @@ __global__ __launch_bounds__(1024) void k_aggregate_mfma(AggArgs a, const float*
                 const int orow = rb * RPI + 16 * mt + 4 * kg + i;
                 if (orow < a.rows) {
                     float val = d[i] + bias;
-                    if (a.relu) val = fmaxf(val, 0.f);
+                    if (a.relu) val = gn::relu_keep_nan(val);
                     a.out[(int64_t)orow * a.ld_out + col] = val;
                 }
             }

@@ -63,6 +63,12 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 
+// The ReLU of every epilogue: NaN stays NaN (torch.relu's contract; fmaxf alone returns 0 for it, and a diverged model
+// then looks finite).  Every other value, -0 and the infinities included, keeps the bits fmaxf(v, 0) gives it: v for a NaN,
+// fmaxf(v, 0) otherwise is IEEE 754-2019's `maximum`, one v_maximum3_f32 on gfx950 where fmaxf was one v_max_f32 (written as
+// `v != v ? v : fmaxf(v, 0.f)` it is a compare and a select more per stored element).
+__device__ __forceinline__ float relu_keep_nan(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
 // Compute units of the current device (persistent kernels launch one workgroup each); 256 if the query fails.
 inline int compute_units() {
     static int cached[16] = {0};

@@ -279,7 +279,7 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
         } else if (j == 0 && row >= 0) {                                                                       \
             vec_t r = scale_bias<CW>(acc, d, bias);                                                            \
             if (a.relu) {                                                                                      \
-                _Pragma("unroll") for (int c = 0; c < CW; ++c) r[c] = fmaxf(r[c], 0.f);                        \
+                _Pragma("unroll") for (int c = 0; c < CW; ++c) r[c] = gn::relu_keep_nan(r[c]);                        \
             }                                                                                                  \
             *reinterpret_cast<vec_t*>(a.out + (int64_t)row * a.ld_out + CW * cg) = r;                          \
             if constexpr (NEXT)                                                                                \
@@ -348,7 +348,7 @@ __device__ __forceinline__ void col_gather(const ColArgs& a, int stamp_set) {
             vec_t ra = scale_bias<CW>(va, da, wbias), rb = scale_bias<CW>(vb, db, wbias);
             if (a.relu) {
 #pragma unroll
-                for (int c = 0; c < CW; ++c) { ra[c] = fmaxf(ra[c], 0.f); rb[c] = fmaxf(rb[c], 0.f); }
+                for (int c = 0; c < CW; ++c) { ra[c] = gn::relu_keep_nan(ra[c]); rb[c] = gn::relu_keep_nan(rb[c]); }
             }
             if (rowa >= 0) {
                 *reinterpret_cast<vec_t*>(a.out + (int64_t)rowa * a.ld_out + CW * cg) = ra;

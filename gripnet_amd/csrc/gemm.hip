@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void k_gemm_f32(GemmArgs g) {
                 float v = acc[t][i] + bias;
                 if (g.accumulate) v += C[(int64_t)row * g.ldc + col];
                 if (g.addend) v += g.addend[(int64_t)row * g.ld_add + col];
-                if (g.relu) v = fmaxf(v, 0.f);
+                if (g.relu) v = gn::relu_keep_nan(v);
                 C[(int64_t)row * g.ldc + col] = v;
             }
         }
@@ -214,7 +214,7 @@ __device__ __forceinline__ void gemm_deep_body(const GemmArgs& g, int bx, int by
             float* c = g.c + (int64_t)row * g.ldc + col;
             if (g.accumulate) v += *c;
             if (g.addend) v += g.addend[(int64_t)row * g.ld_add + col];
-            if (g.relu) v = fmaxf(v, 0.f);
+            if (g.relu) v = gn::relu_keep_nan(v);
             *c = v;
         }
     }
@@ -300,7 +300,7 @@ __device__ __forceinline__ void gemm_lds_body(const GemmArgs& g, int row_tiles, 
                     float v = acc[t][i] + bias;
                     if (g.accumulate) v += g.c[(int64_t)row * g.ldc + col];
                     if (g.addend) v += g.addend[(int64_t)row * g.ld_add + col];
-                    if (g.relu) v = fmaxf(v, 0.f);
+                    if (g.relu) v = gn::relu_keep_nan(v);
                     g.c[(int64_t)row * g.ldc + col] = v;
                 }
             }
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_gemm_split_lds(GemmArgs g, in
                     typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));   // (gn_cast_bf16's rounding: nearest even, once)
                     typedef float f32x2 __attribute__((ext_vector_type(2)));
                     typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-                    if (g.relu) v = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                    if (g.relu) v = (f32x4){gn::relu_keep_nan(v[0]), gn::relu_keep_nan(v[1]), gn::relu_keep_nan(v[2]), gn::relu_keep_nan(v[3])};
                     const f32x2 lo2 = {v[0], v[1]}, hi2 = {v[2], v[3]};
                     const u32x2 pk = {__builtin_bit_cast(uint32_t, __builtin_convertvector(lo2, bf16x2)),
                                       __builtin_bit_cast(uint32_t, __builtin_convertvector(hi2, bf16x2))};
@@ -460,7 +460,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_gemm_split_lds(GemmArgs g, in
                 float* cp = g.c + (int64_t)row * g.ldc + col;
                 if (g.accumulate) v += *reinterpret_cast<const f32x4*>(cp);
                 if (g.addend) v += *reinterpret_cast<const f32x4*>(g.addend + (int64_t)row * g.ld_add + col);
-                if (g.relu) v = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                if (g.relu) v = (f32x4){gn::relu_keep_nan(v[0]), gn::relu_keep_nan(v[1]), gn::relu_keep_nan(v[2]), gn::relu_keep_nan(v[3])};
                 *reinterpret_cast<f32x4*>(cp) = v;
             }
             return;
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_gemm_split_lds(GemmArgs g, in
                     float v = acc[t][i] + bias;
                     if (g.accumulate) v += g.c[(int64_t)row * g.ldc + col];
                     if (g.addend) v += g.addend[(int64_t)row * g.ld_add + col];
-                    if (g.relu) v = fmaxf(v, 0.f);
+                    if (g.relu) v = gn::relu_keep_nan(v);
                     g.c[(int64_t)row * g.ldc + col] = v;
                 }
             }
@@ -571,7 +571,7 @@ __global__ void k_merge(float* __restrict__ dst, int64_t ld_dst, const float* __
             case 0: *d = s; break;
             case 1: *d = fabsf(s); break;
             case 2: *d = (*d + fabsf(s)) / 2.0f; break;
-            case 3: *d = (*d + fmaxf(s, 0.f)) / 2.0f; break;
+            case 3: *d = (*d + gn::relu_keep_nan(s)) / 2.0f; break;
             case 4: *d = (*d + s + src2[i * ld_src2 + c]) / 3.0f; break;
             case 5: *d = src2[i * ld_src2 + c] > 0.f ? s : 0.f; break;
             case 6: {

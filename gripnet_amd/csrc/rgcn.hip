@@ -132,7 +132,7 @@ __global__ void k_rgcn_finalize(const float* __restrict__ summed, int64_t ld_s, 
         const int64_t i = t / cols;
         const int c = (int)(t - i * cols);
         float v = summed[i * ld_s + c] / fmaxf(indeg[i], 1.0f) + out[i * ld_o + c];   // out holds x.root + bias
-        if (relu) v = fmaxf(v, 0.f);
+        if (relu) v = gn::relu_keep_nan(v);
         out[i * ld_o + c] = v;
     }
 }

@@ -210,9 +210,12 @@ __global__ __launch_bounds__(32 * COLS) __attribute__((amdgpu_waves_per_eu(4, 4)
                 const int grow = d.tile * a.ts + lrow;
                 const bool valid = lrow < a.ts && grow < a.n;
                 const float* __restrict__ xr = x + (int64_t)(valid ? grow : 0) * a.ld_x + 4 * q;
-                const float keep = valid ? 1.0f : 0.0f;
+                // (a row beyond the tile reads row 0 and is dropped by a select: times 0.0 a NaN in row 0 stayed one)
 #pragma unroll
-                for (int kc = 0; kc < KC; ++kc) afrag[r][kc] = *reinterpret_cast<const f32x4*>(xr + 16 * kc) * keep;
+                for (int kc = 0; kc < KC; ++kc) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(xr + 16 * kc);
+                    afrag[r][kc] = valid ? v : (f32x4){0.f, 0.f, 0.f, 0.f};
+                }
             }
         }
         uint32_t e[EREGS];
@@ -273,10 +276,13 @@ __global__ __launch_bounds__(32 * COLS) __attribute__((amdgpu_waves_per_eu(4, 4)
         f32x4* arow = acc4 + j;
         auto src_of = [](uint32_t w) { return __builtin_amdgcn_ubfe(w, 0, 16) * LPR; };
         auto dst_of = [](uint32_t w) { return __builtin_amdgcn_ubfe(w, 16, 15) * LPR; };
-        // sum_k = sum_{k-1} * keep_{k-1} + H[src_k], keep = 0 after the last edge of a run: the run sum restarts
-        // inside the FMA instead of with a reset under a branch (x * 1 + y and x * 0 + y are exact).
-        f32x4 sum = (f32x4){0.f, 0.f, 0.f, 0.f};
-        float keep = 0.f;
+        // sum_k = (keep_{k-1} ? sum_{k-1} : 0) + H[src_k], keep false after the last edge of a run: the run sum restarts by a
+        // select, not under a branch.  (It restarted inside an FMA, sum * 0 + H: exact on finite sums, but a NaN or an infinity
+        // in the finished run - a source row that holds one - times 0 is NaN, and the NEXT destination of the slot, which
+        // never read that row, got it.  +0 + H and 1 * sum + H round as the FMA did: finite results keep their bits.)
+        const f32x4 zero4 = (f32x4){0.f, 0.f, 0.f, 0.f};
+        f32x4 sum = zero4;
+        bool keep = false;
         uint4 W = ebuf4[min(g4, kChunk / 4)];
         while (__any(g4 < g4end)) {
             const uint4 Wn = ebuf4[min(g4 + 1, kChunk / 4)];          // next group, in flight during the adds
@@ -293,16 +299,16 @@ __global__ __launch_bounds__(32 * COLS) __attribute__((amdgpu_waves_per_eu(4, 4)
                 if (e1) a1 = arow[i1];
                 if (e2) a2 = arow[i2];
                 if (e3) a3 = arow[i3];
-                const f32x4 s0 = sum * keep + r0;
+                const f32x4 s0 = (keep ? sum : zero4) + r0;
                 if (e0) arow[i0] = a0 + s0;
-                const f32x4 s1 = s0 * (e0 ? 0.f : 1.f) + r1;
+                const f32x4 s1 = (e0 ? zero4 : s0) + r1;
                 if (e1) arow[i1] = a1 + s1;
-                const f32x4 s2 = s1 * (e1 ? 0.f : 1.f) + r2;
+                const f32x4 s2 = (e1 ? zero4 : s1) + r2;
                 if (e2) arow[i2] = a2 + s2;
-                const f32x4 s3 = s2 * (e2 ? 0.f : 1.f) + r3;
+                const f32x4 s3 = (e2 ? zero4 : s2) + r3;
                 if (e3) arow[i3] = a3 + s3;
                 sum = s3;
-                keep = e3 ? 0.f : 1.f;
+                keep = !e3;
             }
             W = Wn;
             ++g4;
@@ -482,7 +488,7 @@ __global__ __launch_bounds__(256) void k_rgcn_slab_finalize(FinArgs a) {
             for (int k = 1; k < 8; ++k) r += xpart[k][c];
             v += r;
             if (a.bias) v += a.bias[c];
-            if (a.relu) v = fmaxf(v, 0.f);
+            if (a.relu) v = gn::relu_keep_nan(v);
         }
         a.out[(int64_t)i * a.ld_out + c] = v;
     }

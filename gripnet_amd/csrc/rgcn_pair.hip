@@ -681,7 +681,7 @@ __global__ __launch_bounds__(kThreads) void k_rgcn_pair(PairArgs a, int stamp_se
         if (lv && fin_part == 0) {
             if (!a.partial) {
                 s = s / div + t + bias_v;
-                if (a.relu) s = fmaxf(s, 0.f);
+                if (a.relu) s = gn::relu_keep_nan(s);
             }
             a.out[(int64_t)pi * a.ld_out + po] = s;
         }
