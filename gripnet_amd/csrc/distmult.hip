@@ -5,7 +5,7 @@
 // triple per lane), then the wave walks its 64 edges four at a time: 16 lanes cover one edge's
 // three feature rows with 16-byte loads (z and D stay L2 / Infinity-Cache resident), fold the
 // 16 partial products with cross-lane shuffles, and the 64 results leave in one coalesced store.
-#include "common.h"
+#include "decoder_host.hpp"
 
 namespace {
 
@@ -82,32 +82,32 @@ __global__ __launch_bounds__(256) void k_distmult(DmArgs a) {
 
 }  // namespace
 
-// distmult_fast.hip
-bool gn_distmult_fast_applicable(int64_t n, int64_t f, int64_t ld_z, int64_t ld_d, const void* z, const void* d);
-gn_status gn_distmult_fast_forward(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
-                                   const int64_t* v, const int64_t* et, const float* d, int64_t ld_d, int64_t r,
-                                   int64_t e, int sigmoid, float* out, int32_t* err, hipStream_t st);
+using gn::route::DecoderKernel;
+using gn::route::DecoderKind;
+using gn::route::DecoderRoute;
+
+template <int VEC>
+static gn_status launch_general(const DecoderRoute& rt, const DmArgs& a, hipStream_t st) {
+    k_distmult<VEC><<<rt.grid, rt.block, 0, st>>>(a);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
 
 extern "C" gn_status gn_distmult_forward_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
                                              const int64_t* v, const int64_t* et, const float* d, int64_t ld_d,
                                              int64_t r, int64_t e, int apply_sigmoid, float* out, int32_t* err,
                                              void* stream) {
-    GN_REQUIRE(n >= 0 && f >= 0 && r >= 0 && e >= 0, "negative size");
-    GN_REQUIRE(f < (1ll << 31) && n < (1ll << 31) && r < (1ll << 31), "table too large");
-    if (e == 0) return GN_OK;
-    GN_REQUIRE(n > 0 && r > 0, "edges given but the node or relation table is empty");
-    GN_REQUIRE(z && u && v && et && d && out, "operand pointer is null");
-    GN_REQUIRE(ld_z >= f && ld_d >= f, "leading dimension smaller than the row length");
+    bool empty;
+    GN_OK_OR_RETURN(gn_dm::require_edge_call(n, f, r, e, ld_z, ld_d, true, z && u && v && et && d && out, &empty));
+    if (empty) return GN_OK;
     hipStream_t st = gn::as_stream(stream);
-    if (gn_distmult_fast_applicable(n, f, ld_z, ld_d, z, d))
-        return gn_distmult_fast_forward(z, ld_z, n, f, u, v, et, d, ld_d, r, e, apply_sigmoid, out, err, st);
+    const DecoderRoute rt = gn::route::decoder_route(gn_dm::decoder_call(DecoderKind::raw, n, f, r, e, z, ld_z, d, ld_d));
     DmArgs a;
     a.z = z; a.ld_z = ld_z; a.n = n; a.features = (int)f; a.u = u; a.v = v; a.et = et;
     a.d = d; a.ld_d = ld_d; a.r = r; a.e = e; a.sigmoid = apply_sigmoid; a.out = out; a.err = err;
-    const bool vec = (f % 4 == 0) && (ld_z % 4 == 0) && (ld_d % 4 == 0) &&
-                     ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
-    const int grid = gn::stream_grid(gn::ceil_div(e, 64) * 64, 256);
-    if (vec) k_distmult<4><<<grid, 256, 0, st>>>(a); else k_distmult<1><<<grid, 256, 0, st>>>(a);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
+    switch (rt.kernel) {
+        case DecoderKernel::lds_raw: return gn_dm::launch_lds_raw(rt, z, ld_z, n, f, u, v, et, d, ld_d, r, e, apply_sigmoid, out, err, st);
+        case DecoderKernel::general_vec: return launch_general<4>(rt, a, st);
+        default: return launch_general<1>(rt, a, st);                 // general_scalar: a raw call is never refused
+    }
 }

@@ -12,7 +12,7 @@
 // ds_read_b128 (16 edges in flight per wave step), the relation row D[r] stays in registers
 // while r does not change (type-sorted positives), and the quad's partial products are folded
 // with two DPP adds.
-#include "distmult_quad.cuh"
+#include "decoder_host.hpp"
 
 namespace {
 
@@ -25,7 +25,7 @@ struct DmFastArgs {
     const float* d; int64_t ld_d; int r;
     int64_t e; int64_t edges_per_wg; int sigmoid; float* out; int32_t* err;
     int n_phases; int c0[kMaxPhases]; int width[kMaxPhases];
-    int stride4;           // LDS row stride in float4, the same in every phase (see gn_distmult_fast_forward)
+    int stride4;           // LDS row stride in float4, the same in every phase (lds_stride4, decoder_route.hpp)
     // Raw int64 triples, several column phases: the first phase leaves every edge's triple in LDS behind the table, narrowed to
     // `stage_bytes` (4: u | v << 10 | r << 20 for n <= 1023, r <= 4096; 8: u | v << 16, r; 0: no staging), and the later phases
     // read it there - 24 bytes per edge cross from HBM once instead of once per phase (pose0-syn: 155 MB moved for 56 MB of
@@ -169,67 +169,20 @@ __global__ __launch_bounds__(kThreads) void k_distmult_lds(DmFastArgs a) {
 
 }  // namespace
 
-bool gn_distmult_fast_applicable(int64_t n, int64_t f, int64_t ld_z, int64_t ld_d, const void* z, const void* d);
-static gn_status distmult_lds_launch(DmFastArgs& a, int64_t n, int64_t f, int64_t e, bool packed, hipStream_t st);
+using gn::route::DecoderKernel;
+using gn::route::DecoderKind;
+using gn::route::DecoderRoute;
 
-bool gn_distmult_fast_applicable(int64_t n, int64_t f, int64_t ld_z, int64_t ld_d, const void* z, const void* d) {
-    if (gn::fast_paths_disabled()) return false;
-    if (n < 1 || n > 65535 || f < 4 || f % 4 != 0 || ld_z % 4 != 0 || ld_d % 4 != 0) return false;
-    if (((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d)) & 15) != 0) return false;
-    int c0[kMaxPhases], w[kMaxPhases];
-    const int phases = plan_phases(n, f, c0, w);
-    return phases >= 1 && phases <= 4;   // beyond that the general (L2-gather) kernel is the better choice
-}
-
-static gn_status distmult_lds_launch(DmFastArgs& a, int64_t n, int64_t f, int64_t e, bool packed, hipStream_t st) {
-    a.n_phases = plan_phases(n, f, a.c0, a.width);
-    int max_w = 0;
-    for (int k = 0; k < a.n_phases; ++k) max_w = std::max(max_w, a.width[k]);
-    const int stride4 = lds_stride4(n, max_w);
-    a.stride4 = stride4;
-    size_t lds_bytes = (size_t)n * stride4 * 16;
-    // one workgroup per CU; every workgroup's range is a multiple of 64 edges
-    int64_t groups = std::min<int64_t>(256, gn::ceil_div(e, 64 * (kThreads / 64)));
-    if (groups < 1) groups = 1;
-    a.edges_per_wg = gn::ceil_div(gn::ceil_div(e, groups), 64) * 64;
-    groups = gn::ceil_div(e, a.edges_per_wg);
-    // the triples of the raw int64 list staged in LDS behind the table (see DmFastArgs): where a tile of a useful size fits, and
-    // the table fills of the extra tiles (every workgroup reads the whole phase table again: ~3 us each at this size) cost less
-    // than the passes over the list they save (24 bytes per edge and phase at ~5 TB/s)
-    a.stage_bytes = 0; a.tile_edges = 0; a.stage_off = (int)lds_bytes;
-    if (!packed && a.n_phases > 1) {
-        const int sb = (n <= 1023 && a.r <= 4096) ? 4 : 8;
-        const int64_t room = (int64_t)160 * 1024 - (int64_t)lds_bytes;
-        const int64_t tile = room / sb / 64 * 64;
-        if (tile >= 1024) {
-            const int64_t tiles = gn::ceil_div(a.edges_per_wg, tile);
-            const double fill_us = (double)lds_bytes * (double)groups / 1.0e7, pass_us = (double)e * 24.0 / 5.0e6;
-            if ((double)(tiles - 1) * a.n_phases * fill_us < (double)(a.n_phases - 1) * pass_us) {
-                a.stage_bytes = sb;
-                a.tile_edges = std::min<int64_t>(tile, a.edges_per_wg);
-                lds_bytes += (size_t)a.tile_edges * sb;
-            }
-        }
-    }
-    if (packed) {
-        { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_distmult_lds<true>), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
-        k_distmult_lds<true><<<(unsigned)groups, kThreads, lds_bytes, st>>>(a);
-    } else {
-        { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_distmult_lds<false>), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
-        k_distmult_lds<false><<<(unsigned)groups, kThreads, lds_bytes, st>>>(a);
-    }
+// k_distmult_lds<PACKED> as the route lays it out: column phases, row stride, the workgroups' ranges and the staging
+template <bool PACKED>
+static gn_status launch_lds(const DecoderRoute& rt, DmFastArgs& a, hipStream_t st) {
+    a.n_phases = rt.n_phases; a.stride4 = rt.stride4; a.edges_per_wg = rt.edges_per_wg;
+    for (int k = 0; k < rt.n_phases; ++k) { a.c0[k] = rt.c0[k]; a.width[k] = rt.width[k]; }
+    a.stage_bytes = rt.stage_bytes; a.tile_edges = rt.tile_edges; a.stage_off = rt.stage_off;
+    GN_OK_OR_RETURN(gn::allow_large_lds(reinterpret_cast<const void*>(k_distmult_lds<PACKED>), (int)gn::route::kLdsCu));
+    k_distmult_lds<PACKED><<<rt.grid, rt.block, rt.lds_bytes, st>>>(a);
     GN_LAUNCH_CHECK();
     return GN_OK;
-}
-
-gn_status gn_distmult_fast_forward(const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
-                                   const int64_t* v, const int64_t* et, const float* d, int64_t ld_d, int64_t r,
-                                   int64_t e, int sigmoid, float* out, int32_t* err, hipStream_t st) {
-    GN_REQUIRE(r >= 1, "no relations");
-    DmFastArgs a;
-    a.z = z; a.ld_z = ld_z; a.n = (int)n; a.features = (int)f; a.u = u; a.v = v; a.et = et; a.packed = nullptr; a.rel16 = nullptr;
-    a.d = d; a.ld_d = ld_d; a.r = (int)r; a.e = e; a.sigmoid = sigmoid; a.out = out; a.err = err;
-    return distmult_lds_launch(a, n, f, e, false, st);
 }
 
 // The same decoder on PACKED triples: u | v << 16 (uint32) and the relation (uint16) of every edge - six bytes per edge
@@ -239,17 +192,25 @@ gn_status gn_distmult_fast_forward(const float* z, int64_t ld_z, int64_t n, int6
 extern "C" gn_status gn_distmult_packed_forward_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const uint32_t* packed_uv,
                                                     const uint16_t* relation, const float* d, int64_t ld_d, int64_t r,
                                                     int64_t e, int apply_sigmoid, float* out, int32_t* err, void* stream) {
-    GN_REQUIRE(n >= 0 && f >= 0 && r >= 0 && e >= 0, "negative size");
-    if (e == 0) return GN_OK;
-    GN_REQUIRE(n > 0 && r > 0, "edges given but the node or relation table is empty");
-    GN_REQUIRE(z && packed_uv && relation && d && out, "operand pointer is null");
-    GN_REQUIRE(ld_z >= f && ld_d >= f, "leading dimension smaller than the row length");
-    if (n > 65535 || r > 65535 || !gn_distmult_fast_applicable(n, f, ld_z, ld_d, z, d))
-        return gn::fail(GN_ERR_UNSUPPORTED, "the packed decoder needs node and relation ids of 16 bits and a node table that fits the LDS "
-                                            "in four column phases: use gn_distmult_forward_f32");
+    bool empty;
+    GN_OK_OR_RETURN(require_edge_call(n, f, r, e, ld_z, ld_d, false, z && packed_uv && relation && d && out, &empty));
+    if (empty) return GN_OK;
+    const DecoderRoute rt = gn::route::decoder_route(decoder_call(DecoderKind::packed, n, f, r, e, z, ld_z, d, ld_d));
+    if (rt.kernel != DecoderKernel::lds_packed)
+        return gn::fail(rt.status, "the packed decoder needs node and relation ids of 16 bits and a node table that fits the LDS "
+                                   "in four column phases: use gn_distmult_forward_f32");
     DmFastArgs a;
     a.z = z; a.ld_z = ld_z; a.n = (int)n; a.features = (int)f; a.u = nullptr; a.v = nullptr; a.et = nullptr;
     a.packed = packed_uv; a.rel16 = relation;
     a.d = d; a.ld_d = ld_d; a.r = (int)r; a.e = e; a.sigmoid = apply_sigmoid; a.out = out; a.err = err;
-    return distmult_lds_launch(a, n, f, e, true, gn::as_stream(stream));
+    return launch_lds<true>(rt, a, gn::as_stream(stream));
+}
+
+gn_status gn_dm::launch_lds_raw(const DecoderRoute& rt, const float* z, int64_t ld_z, int64_t n, int64_t f, const int64_t* u,
+                                const int64_t* v, const int64_t* et, const float* d, int64_t ld_d, int64_t r, int64_t e, int sigmoid,
+                                float* out, int32_t* err, hipStream_t st) {
+    DmFastArgs a;
+    a.z = z; a.ld_z = ld_z; a.n = (int)n; a.features = (int)f; a.u = u; a.v = v; a.et = et; a.packed = nullptr; a.rel16 = nullptr;
+    a.d = d; a.ld_d = ld_d; a.r = (int)r; a.e = e; a.sigmoid = sigmoid; a.out = out; a.err = err;
+    return launch_lds<false>(rt, a, st);
 }

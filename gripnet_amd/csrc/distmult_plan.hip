@@ -16,7 +16,7 @@
 //   - VALU: no int64 arithmetic, no range checks (validated once, at plan time), the batch's relation is a
 //     scalar.
 // Same column phases and quad-per-edge arithmetic as the plan-less kernel: results are bitwise the same.
-#include "distmult_quad.cuh"
+#include "decoder_host.hpp"
 #include "layout_decoder.hpp"
 
 #include <algorithm>
@@ -56,6 +56,8 @@ using namespace gn_dm;
 constexpr int kNodeBits = 13;
 constexpr uint32_t kNodeMask = (1u << kNodeBits) - 1;
 using gn_layout::kNoMirror;
+using gn::route::DecoderKernel;
+using gn::route::DecoderRoute;
 
 struct DmPlanArgs {
     const float* z; int64_t ld_z; int n;
@@ -540,18 +542,19 @@ __global__ __launch_bounds__(kThreads) void k_distmult_class(DmClassArgs a) { di
 template <int J, int J1>
 __global__ __launch_bounds__(kThreads) void k_distmult_class_wide(DmClassArgs a) { distmult_class<J, J1, false>(a); }
 
+// k_distmult_class<J, J1>, or its _wide form, on the route's grid: the one place that opts in to the LDS and launches
 template <int J, int J1>
-gn_status launch_class(const gn_distmult_plan* plan, const DmClassArgs& a, int64_t n, hipStream_t st) {
+gn_status launch_class(const DecoderRoute& rt, const DmClassArgs& a, hipStream_t st) {
     auto launch = [&](auto kernel) {
-        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(kernel), 160 * 1024);
+        gn_status s = gn::allow_large_lds(reinterpret_cast<const void*>(kernel), (int)gn::route::kLdsCu);
         if (s != GN_OK) return s;
         const gn::LaunchEvents ev = gn::take_launch_events();
-        if (ev.start || ev.stop) hipExtLaunchKernelGGL(kernel, dim3(plan->cls_groups), dim3(kThreads), 160 * 1024, st, ev.start, ev.stop, 0, a);
-        else kernel<<<plan->cls_groups, kThreads, 160 * 1024, st>>>(a);
+        if (ev.start || ev.stop) hipExtLaunchKernelGGL(kernel, dim3(rt.grid), dim3(rt.block), rt.lds_bytes, st, ev.start, ev.stop, 0, a);
+        else kernel<<<rt.grid, rt.block, rt.lds_bytes, st>>>(a);
         return GN_OK;
     };
     // (the class table of the arguments covers 256 workgroups: a larger grid reads its rows from the descriptors)
-    const gn_status s = plan->cls_by_args ? launch(k_distmult_class<J, J1>) : launch(k_distmult_class_wide<J, J1>);
+    const gn_status s = rt.kernel == DecoderKernel::cls ? launch(k_distmult_class<J, J1>) : launch(k_distmult_class_wide<J, J1>);
     if (s != GN_OK) return s;
     GN_LAUNCH_CHECK();
     return GN_OK;
@@ -687,79 +690,76 @@ int64_t gn_distmult_plan_edges(const gn_distmult_plan* plan) { return plan ? pla
 
 }  // extern "C"
 
+namespace {
+
+// What a planned call brings besides its plan and its route
+struct PlanOperands {
+    const float* z; int64_t ld_z; const float* d; int64_t ld_d; int sigmoid; float* out; hipStream_t st;
+};
+
+gn_status launch_class_route(const gn_distmult_plan* plan, const DecoderRoute& rt, const PlanOperands& o) {
+    DmClassArgs c;
+    c.z = o.z; c.ld_z = o.ld_z; c.d = o.d; c.ld_d = o.ld_d;
+    c.packed = plan->cls_packed.p; c.own = plan->cls_own.p; c.mirror = plan->cls_mirror.p; c.rel = plan->cls_rel.p;
+    c.wg = plan->cls_wg.p; c.out = o.out; c.c0 = rt.c0[0]; c.sigmoid = o.sigmoid;
+    c.first_launch = rt.first_launch; c.last_launch = rt.last_launch; c.walks = plan->cls_walks;
+    c.dma = rt.dma;
+    memcpy(c.cls_rows, plan->cls_rows, sizeof(c.cls_rows));
+    memcpy(c.cls_of_wg, plan->cls_of_wg, sizeof(c.cls_of_wg));
+    switch (rt.J * 8 + rt.J1) {                                               // the instantiations the route knows (decoder_class_covers)
+        case 5 * 8 + 3: return launch_class<5, 3>(rt, c, o.st);
+        case 5 * 8 + 4: return launch_class<5, 4>(rt, c, o.st);
+        case 4 * 8 + 4: return launch_class<4, 4>(rt, c, o.st);
+        case 3 * 8 + 3: return launch_class<3, 3>(rt, c, o.st);
+        case 2 * 8 + 2: return launch_class<2, 2>(rt, c, o.st);
+        default: return launch_class<1, 1>(rt, c, o.st);
+    }
+}
+
+gn_status launch_phase(const gn_distmult_plan* plan, const DecoderRoute& rt, const PlanOperands& o) {
+    DmPlanArgs a;
+    a.z = o.z; a.ld_z = o.ld_z; a.n = (int)plan->num_nodes; a.packed = plan->packed.p; a.batch_rel = plan->batch_rel.p; a.rel16 = plan->rel16.p; a.own = plan->own.p; a.mirror = plan->mirror.p;
+    a.d = o.d; a.ld_d = o.ld_d; a.e = plan->num_edges; a.batches = plan->batches; a.sigmoid = o.sigmoid; a.out = o.out;
+    a.n_phases = rt.n_phases; a.stride4 = rt.stride4;
+    for (int k = 0; k < rt.n_phases; ++k) { a.c0[k] = rt.c0[k]; a.width[k] = rt.width[k]; }
+    a.batches_per_wg = rt.batches_per_wg; a.keep_n = rt.keep_n; a.all_kept = rt.all_kept;
+    a.first_launch = rt.first_launch; a.last_launch = rt.last_launch;
+    GN_OK_OR_RETURN(gn::allow_large_lds(reinterpret_cast<const void*>(k_distmult_plan), (int)gn::route::kLdsCu));
+    k_distmult_plan<<<rt.grid, rt.block, rt.lds_bytes, o.st>>>(a);
+    GN_LAUNCH_CHECK();
+    return GN_OK;
+}
+
 // Columns [col_lo, col_hi) of the feature dimension in one launch; the launch with col_lo = 0 starts the sums, the one
 // with col_hi = num_features finishes them.
-static gn_status plan_forward_cols(const gn_distmult_plan* plan, const float* z, int64_t ld_z, int64_t num_features, int64_t col_lo,
-                                   int64_t col_hi, const float* d, int64_t ld_d, int apply_sigmoid, float* out, void* stream) {
+gn_status plan_forward_cols(const gn_distmult_plan* plan, const float* z, int64_t ld_z, int64_t num_features, int64_t col_lo,
+                            int64_t col_hi, const float* d, int64_t ld_d, int apply_sigmoid, float* out, void* stream) {
     GN_REQUIRE(plan != nullptr, "plan is null");
     if (plan->num_edges == 0) return GN_OK;
     GN_REQUIRE(z && d && out, "operand pointer is null");
     GN_REQUIRE(num_features > 0 && ld_z >= col_hi && ld_d >= num_features, "feature count / leading dimension mismatch");
     GN_REQUIRE(0 <= col_lo && col_lo < col_hi && col_hi <= num_features && col_lo % 4 == 0, "column range outside the features");
-    const int64_t n = plan->num_nodes, f = col_hi - col_lo;
-    if (plan->cls_ok && f % 16 == 0 && f <= plan->cls_features && ld_z % 4 == 0 && ld_d % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d)) & 15) == 0 && !gn::fast_paths_disabled()) {
-        // the sum keeps the column parts of the phase kernels (plan_phases), so the bits do not depend on the kernel
-        int pc0[kMaxPhases], pw[kMaxPhases];
-        const int parts = plan_phases(n, f, pc0, pw);
-        const int J = (int)(f / 16), J1 = parts >= 1 ? pw[0] / 16 : 0;
-        if ((parts == 1 || (parts == 2 && pw[0] % 16 == 0)) && J1 >= 1) {
-            DmClassArgs c;
-            c.z = z; c.ld_z = ld_z; c.d = d; c.ld_d = ld_d;
-            c.packed = plan->cls_packed.p; c.own = plan->cls_own.p; c.mirror = plan->cls_mirror.p; c.rel = plan->cls_rel.p;
-            c.wg = plan->cls_wg.p; c.out = out; c.c0 = (int)col_lo; c.sigmoid = apply_sigmoid;
-            c.first_launch = col_lo == 0; c.last_launch = col_hi == num_features; c.walks = plan->cls_walks;
-            // (odd J: no padding between the LDS rows; z and d are 16-byte aligned and ld_d a multiple of four floats here)
-            c.dma = (J & 1) && ld_z == f && col_lo == 0;
-            memcpy(c.cls_rows, plan->cls_rows, sizeof(c.cls_rows));
-            memcpy(c.cls_of_wg, plan->cls_of_wg, sizeof(c.cls_of_wg));
-            hipStream_t st = gn::as_stream(stream);
-            switch (J * 8 + J1) {
-                case 5 * 8 + 3: return launch_class<5, 3>(plan, c, n, st);
-                case 5 * 8 + 4: return launch_class<5, 4>(plan, c, n, st);
-                case 4 * 8 + 4: return launch_class<4, 4>(plan, c, n, st);
-                case 3 * 8 + 3: return launch_class<3, 3>(plan, c, n, st);
-                case 2 * 8 + 2: return launch_class<2, 2>(plan, c, n, st);
-                case 1 * 8 + 1: return launch_class<1, 1>(plan, c, n, st);
-                default: break;                                               // other widths: the column-phase kernel
-            }
-        }
+    gn::route::DecoderCall c = decoder_call(gn::route::DecoderKind::planned, plan->num_nodes, col_hi - col_lo, plan->num_relations,
+                                            plan->num_edges, z, ld_z, d, ld_d);
+    c.col_lo = col_lo; c.col_hi = col_hi; c.num_features = num_features;
+    c.cls_ok = plan->cls_ok != 0; c.cls_features = plan->cls_features; c.cls_groups = plan->cls_groups;
+    c.cls_by_args = plan->cls_by_args != 0; c.batches = plan->batches;
+    const DecoderRoute rt = gn::route::decoder_route(c);
+    const PlanOperands o = {z, ld_z, d, ld_d, apply_sigmoid, out, gn::as_stream(stream)};
+    switch (rt.kernel) {
+        case DecoderKernel::cls:
+        case DecoderKernel::cls_wide: return launch_class_route(plan, rt, o);
+        case DecoderKernel::phase: return launch_phase(plan, rt, o);
+        default: break;
     }
-    if (plan->cls_ok && plan->batches == 0)
-        return gn::fail(GN_ERR_UNSUPPORTED, "the plan holds the row-class encoding only (built for %d features): no kernel of it covers columns [%lld, %lld): "
-                                            "use gn_distmult_forward_f32", plan->cls_features, (long long)col_lo, (long long)col_hi);
-    DmPlanArgs a;
-    a.n_phases = (f % 4 == 0 && ld_z % 4 == 0 && ld_d % 4 == 0 &&
-                  ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(d)) & 15) == 0)
-                     ? plan_phases(n, f, a.c0, a.width) : 0;
-    if (gn::fast_paths_disabled() || a.n_phases < 1 || a.n_phases > 4)
-        return gn::fail(GN_ERR_UNSUPPORTED, "the planned decoder needs a node table that fits the LDS in at most four column "
-                                            "phases (n = %lld, features = %lld): use gn_distmult_forward_f32", (long long)n, (long long)f);
-    for (int k = 0; k < a.n_phases; ++k) a.c0[k] += (int)col_lo;
-    a.first_launch = col_lo == 0;
-    a.last_launch = col_hi == num_features;
-    a.z = z; a.ld_z = ld_z; a.n = (int)n; a.packed = plan->packed.p; a.batch_rel = plan->batch_rel.p; a.rel16 = plan->rel16.p; a.own = plan->own.p; a.mirror = plan->mirror.p;
-    a.d = d; a.ld_d = ld_d; a.e = plan->num_edges; a.batches = plan->batches; a.sigmoid = apply_sigmoid; a.out = out;
-    int max_w = 0;
-    for (int k = 0; k < a.n_phases; ++k) max_w = std::max(max_w, a.width[k]);
-    a.stride4 = lds_stride4(n, max_w);
-    const size_t table_bytes = (size_t)n * a.stride4 * 16;
-    int64_t groups = std::min<int64_t>(256, gn::ceil_div(plan->batches, kThreads / 64));
-    if (groups < 1) groups = 1;
-    a.batches_per_wg = gn::ceil_div(plan->batches, groups);
-    groups = gn::ceil_div(plan->batches, a.batches_per_wg);
-    // partial sums between phases: as many batches per wave as the LDS left over by the table holds (4 KB each per workgroup)
-    const int64_t per_wave = gn::ceil_div(plan->batches, groups * (kThreads / 64));
-    const int64_t room = ((int64_t)160 * 1024 - 1024 - (int64_t)table_bytes) / ((kThreads / 64) * 256);
-    a.keep_n = a.n_phases > 1 ? (int)std::max<int64_t>(0, std::min(per_wave, room)) : 0;
-    // (a launch that takes sums from, or leaves them to, another launch needs the edge positions in those phases too)
-    a.all_kept = a.n_phases > 1 && a.keep_n >= per_wave && a.first_launch && a.last_launch;
-    const size_t lds_bytes = table_bytes + (size_t)a.keep_n * (kThreads / 64) * 256;
-    { gn_status lds_status = gn::allow_large_lds(reinterpret_cast<const void*>(k_distmult_plan), 160 * 1024); if (lds_status != GN_OK) return lds_status; }
-    k_distmult_plan<<<(unsigned)groups, kThreads, lds_bytes, gn::as_stream(stream)>>>(a);
-    GN_LAUNCH_CHECK();
-    return GN_OK;
+    if (rt.why == gn::route::DecoderRefusal::class_only)
+        return gn::fail(rt.status, "the plan holds the row-class encoding only (built for %d features): no kernel of it covers columns [%lld, %lld): "
+                                   "use gn_distmult_forward_f32", plan->cls_features, (long long)col_lo, (long long)col_hi);
+    return gn::fail(rt.status, "the planned decoder needs a node table that fits the LDS in at most four column "
+                               "phases (n = %lld, features = %lld): use gn_distmult_forward_f32", (long long)c.n, (long long)c.f);
 }
+
+}  // namespace
 
 extern "C" {
 

@@ -1,19 +1,19 @@
-// Pieces shared by the LDS-resident DistMult kernels (distmult_fast.hip: raw int64 triples every call;
-// distmult_plan.hip: a cached, re-encoded static edge list): DPP helpers, the quad-per-edge step, the column
-// phases and the LDS row stride.
+// Device pieces shared by the LDS-resident DistMult kernels (distmult_fast.hip: raw int64 triples every call;
+// distmult_plan.hip: a cached, re-encoded static edge list): DPP helpers, the table fill and the quad-per-edge step.
+// The column phases and the LDS row stride are host arithmetic: decoder_route.hpp.
 #pragma once
 
 #include "common.h"
+#include "decoder_route.hpp"
 #include "dpp.cuh"
 
 namespace gn_dm {
 
-constexpr int kMaxPhases = 8;
+using gn::route::kMaxPhases;
 #ifndef GN_DM_THREADS
 #define GN_DM_THREADS 1024
 #endif
 constexpr int kThreads = GN_DM_THREADS;
-constexpr size_t kLdsBudget = 150 * 1024;   // of 160 KB; the rest is left to the runtime
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -111,37 +111,6 @@ __device__ __forceinline__ void quad_step(const char* __restrict__ lds, int stri
     acc = dpp_add<0xB1>(acc);            // quad_perm [1,0,3,2]
     acc = dpp_add<0x4E>(acc);            // quad_perm [2,3,0,1]
     if (l4 == S) result = acc;
-}
-
-
-// Column phases: as few as possible; each at most 64 columns (4 lanes x 4 chunks x float4) with
-// n x width x 4 B inside the LDS budget; widths are multiples of 16 columns except the last.
-inline int plan_phases(int64_t n, int64_t f, int* c0, int* width) {
-    if (n <= 0 || f <= 0 || f % 4 != 0) return 0;
-    int64_t max_w = (int64_t)(kLdsBudget / (n * 4)) / 16 * 16;
-    if (max_w > 64) max_w = 64;
-    if (max_w < 16) return 0;
-    const int64_t phases = gn::ceil_div(f, max_w);
-    if (phases > kMaxPhases) return 0;
-    int64_t c = 0;
-    int k = 0;
-    while (c < f) {
-        const int64_t w = std::min(max_w, f - c);
-        c0[k] = (int)c;
-        width[k] = (int)w;
-        c += w;
-        ++k;
-    }
-    return k;
-}
-
-// LDS rows keep one stride for all phases, an odd number of 64-byte slots where there is room: a quad reads
-// 64 contiguous bytes of a row, and with rows 128 bytes apart (a 32-column phase) the four quads of a
-// 16-lane access group would share only two of the four 64-byte bank slots.
-inline int lds_stride4(int64_t n, int max_w) {
-    int stride4 = max_w / 4;
-    if ((stride4 / 4) % 2 == 0 && (size_t)n * (stride4 + 4) * 16 <= kLdsBudget + 8 * 1024) stride4 += 4;
-    return stride4;
 }
 
 }  // namespace gn_dm

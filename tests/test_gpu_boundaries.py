@@ -16,13 +16,13 @@ Guard by guard (csrc line numbers as of ABI 159; "formula": the size is found by
   distmult_plan.hip:522    plan words, nodes <= 8192, relations <= 65535    test_decoder_at_the_plan_word_limit[8192|8193],
                                                                             test_decoder_relation_counts[65535|65536]
                            (a plan of 2401..8192 nodes is built but none of its kernels takes it: the LDS fit below binds first)
-  distmult_quad.cuh:125    node table in LDS, 16 columns of n rows <= 150 KB test_decoder_at_the_lds_table_limit (arithmetic: the
+  decoder_route.hpp:54     node table in LDS, 16 columns of n rows <= 150 KB test_decoder_at_the_lds_table_limit (arithmetic: the
                            (plan forward, plan-less fast decoder)           library exports no query; `served` checks the arithmetic)
   host_layout.hpp:583-593  class layout rows_fit / three blocks / n > 65535  test_decoder_at_the_class_layout_limits (arithmetic, as
                                                                             above: one block, three blocks, none).  n > 65535 and the
                                                                             (uint16_t) stores at :626 are unreachable: the plan refuses
                                                                             n > 8192 before the layout is built.
-  distmult_fast.hip:177,247 n <= 65535, r <= 65535                           n: unreachable (the LDS fit above, n <= 2400, binds first);
+  decoder_route.hpp:229    n <= 65535, r <= 65535                            n: unreachable (the LDS fit above, n <= 2400, binds first);
                                                                             r: behind Python's 32767, test_decoder_relation_counts
   distmult_bwd.hip:652,1215,1233  n <= 65535 / <= 65536                      the n, r <= 65535 test of the LDS path is gone: tables_fit_lds
                                                                             (:762, n + r <= 2400) binds first, and the static_assert
@@ -240,7 +240,7 @@ def run_decoder(dev, n, R, f, sigmoid, static, seed, extra=4000, packed_negative
     return names, plan, (ei_g, et_g), what
 
 
-LDS_NODES_16 = 150 * 1024 // (16 * 4)           # distmult_quad.cuh:125: sixteen columns of n rows inside kLdsBudget = 150 KB -> 2400
+LDS_NODES_16 = 150 * 1024 // (16 * 4)           # decoder_route.hpp:54: sixteen columns of n rows inside kLdsBudget = 150 KB -> 2400
 
 
 @pytest.mark.parametrize("sigmoid", [True, False])
