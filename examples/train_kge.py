@@ -21,9 +21,16 @@ filter is the training list: as given for the tail side, flipped for the head si
 
 `--negatives K` (and / or `--adversarial-temperature T`) trains the way these four models are trained in the code base the
 class comes from: an epoch is a pass over shuffled mini-batches of `--batch` positives, every positive gets K uniform
-candidate entities (torch.randint on the device) that replace its tail ('tail-batch') or its head ('head-batch'),
-alternating from batch to batch, and the loss is gripnet_amd.kge.self_adversarial_loss on the raw scores.  Without these
-flags the script does what it always did.
+candidate entities (gripnet_amd.kge.sample_candidates, drawn on the device) that replace its tail ('tail-batch') or its
+head ('head-batch'), alternating from batch to batch, and the loss is gripnet_amd.kge.negative_sampling_loss on the raw
+scores: one HIP launch forward and one backward.  `--filter-negatives` keeps the known triples of the training list out of
+the candidates (two KnownPairs: keyed (relation, head) for candidate tails, built from the flipped list for candidate
+heads); `--subsampling` weights every positive by 1 / sqrt(count(r, h) + count(r, t) + 4), as that code base does;
+`--torch-loss` keeps the earlier formulation for comparison: torch.randint candidates and
+gripnet_amd.kge.self_adversarial_loss in torch ops (no filter, no weights).  Without these flags the script does what it
+always did.
+
+    python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3 --negatives 256 --adversarial-temperature 1.0 --filter-negatives
 """
 import argparse
 import os
@@ -38,7 +45,7 @@ sys.path.insert(0, ROOT)
 
 from gripnet_amd import KGEModel                                      # reference: class KGEModel, :58-235
 from gripnet_amd import _hip
-from gripnet_amd.kge import self_adversarial_loss
+from gripnet_amd.kge import negative_sampling_loss, sample_candidates, self_adversarial_loss
 from gripnet_amd.synth import make_rgcn_pose
 from gripnet_amd.decoder import KnownPairs
 from gripnet_amd.utils import EPS, device_negative_sampler, ranking_metrics, relation_metrics, typed_negative_sampling
@@ -106,6 +113,9 @@ def main():
     ap.add_argument("--negatives", type=int, default=None, help="K uniform candidates per positive: mini-batch training")
     ap.add_argument("--adversarial-temperature", type=float, default=None, help="self-adversarial weighting of the K negatives")
     ap.add_argument("--batch", type=int, default=1024, help="positives per mini-batch (with --negatives)")
+    ap.add_argument("--filter-negatives", action="store_true", help="never draw a known training triple as a negative")
+    ap.add_argument("--subsampling", action="store_true", help="weight a positive by 1 / sqrt(count(r, h) + count(r, t) + 4)")
+    ap.add_argument("--torch-loss", action="store_true", help="torch.randint candidates and the loss in torch ops")
     args = ap.parse_args()
     torch.manual_seed(1111)
     np.random.seed(1111)
@@ -154,6 +164,20 @@ def main():
     batched = args.negatives is not None or args.adversarial_temperature is not None
     n_negatives = 256 if args.negatives is None else args.negatives
 
+    if args.torch_loss and (args.filter_negatives or args.subsampling):
+        ap.error("--torch-loss is the unfiltered, unweighted formulation")
+    sides = {"tail-batch": "tail", "head-batch": "head"}
+    known = {"tail": None, "head": None}
+    if batched and args.filter_negatives:
+        known = {"tail": KnownPairs([(data.train_idx, data.train_et)], data.n_node, data.n_edge_type),
+                 "head": KnownPairs([(data.train_idx.flip(0), data.train_et)], data.n_node, data.n_edge_type)}
+    weights = None
+    if batched and args.subsampling:                                  # one count per (relation, head) and (relation, tail)
+        head_key, tail_key = (data.train_et * data.n_node + data.train_idx[i] for i in (0, 1))
+        size = data.n_edge_type * data.n_node
+        count = torch.bincount(head_key, minlength=size)[head_key] + torch.bincount(tail_key, minlength=size)[tail_key]
+        weights = torch.rsqrt((count + 4).float())
+
     def train_batched(epoch):
         """One pass over shuffled mini-batches; the metrics are the full-list ones of `train`, after the pass."""
         model.train()
@@ -165,14 +189,21 @@ def main():
         for i, lo in enumerate(starts):
             pick = order[lo:lo + args.batch]
             positive, et = data.train_idx[:, pick].contiguous(), data.train_et[pick].contiguous()
-            candidates = torch.randint(0, data.n_node, (pick.numel(), n_negatives), generator=gen, device=device)
             mode = "tail-batch" if i % 2 == 0 else "head-batch"
             optimizer.zero_grad()
-            loss = self_adversarial_loss(model.score(positive, et), model.score((positive, candidates), et, mode=mode),
-                                         args.adversarial_temperature)
+            if args.torch_loss:
+                candidates = torch.randint(0, data.n_node, (pick.numel(), n_negatives), generator=gen, device=device)
+                loss = self_adversarial_loss(model.score(positive, et), model.score((positive, candidates), et, mode=mode),
+                                             args.adversarial_temperature)
+            else:
+                candidates = sample_candidates(positive, et, n_negatives, data.n_node, side=sides[mode], known=known[sides[mode]],
+                                               seed=(1111 + epoch) * len(starts) + i)
+                loss = negative_sampling_loss(model.score(positive, et), model.score((positive, candidates), et, mode=mode),
+                                              args.adversarial_temperature, None if weights is None else weights[pick])
             loss.backward()
             optimizer.step()
             total += loss.detach()
+        _hip.raise_if_index_errors(device)                            # (a row that knows every entity would have kept a positive)
         model.eval()
         with torch.no_grad():
             pos_score = model(data.train_idx[:, :drug_edges].contiguous(), data.train_et[:drug_edges])

@@ -29,7 +29,7 @@ RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 169                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 170                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -120,6 +120,10 @@ SIGNATURES = {
     "gn_kge_batch_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_batch_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64, _i64]),
     "gn_kge_batch_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
+    "gn_kge_ns_loss_workspace_bytes": (_sz, [_i64]),
+    "gn_kge_ns_loss_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, C.c_float, _p, _p, _p, _p, _sz, _p]),
+    "gn_kge_ns_loss_backward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, C.c_float, _p, _p, _p, _p, _p, _i64, _p]),
+    "gn_kge_candidates_sample": (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, C.c_uint64, _p, _p, _i64, _p, _p]),
     "gn_gat_logits_f32": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
     "gn_gat_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, C.c_float, _p, _int, _int, _p, _i64, _p, _p, _p, _p]),
     "gn_gat_backward_dst_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, C.c_float, _p, _i64, _int, _p, _p, _p, _p]),
@@ -1107,7 +1111,8 @@ def raise_if_index_errors(device=None):
             if bits & 4:
                 raise RuntimeError("one-shot exchange: a peer's partial sums did not arrive within the timeout")
             if bits & 2:
-                raise RuntimeError("negative sampler: a relation's positive pairs leave no pair to draw")
+                raise RuntimeError("negative sampler: a relation's positive pairs leave no pair to draw "
+                                   "(or a KGE candidate row's known partners no entity)")
             found = []
             if bits & 1:
                 found.append("DistMult decoder saw an edge endpoint or relation id outside its table (or a KGE scorer a head, tail or relation id)")
@@ -1523,6 +1528,54 @@ def kge_batch_backward(model, ent, rel, fixed, et, cand, side, divisor, grad_out
           ptr(cand), ld(cand), b, k, sd, float(divisor), ptr(grad_out), ptr(raw), ptr(d_ent), ld(d_ent), ptr(d_rel), ld(d_rel),
           GN_DM_TYPES_SORTED if types_sorted else 0, ptr(ws), need, stream_ptr(ent.device))
     return d_ent, d_rel
+
+
+def kge_ns_block(pos, neg):
+    """(B, K) of a score block of the negative-sampling loss: pos fp32 [B] contiguous, neg fp32 [B, K] with unit inner
+    stride and a row stride of at least K (what KgeNegativeSamplingLossFn hands on)."""
+    b, k = int(neg.shape[0]), int(neg.shape[1])
+    if b < 1 or k < 1:
+        raise ValueError("the loss needs at least one positive and one negative each, got {}".format(tuple(neg.shape)))
+    return b, k
+
+
+def kge_ns_loss_forward(pos, neg, weight=None, temperature=None):
+    """(loss 0-d, row_stats [B, 2], scale [1]) of gn_kge_ns_loss_forward_f32; its per-device scratch is zeroed once (the
+    kernel leaves it ready for the next launch).  `temperature` None: the negatives of a row are averaged."""
+    b, k = kge_ns_block(pos, neg)
+    dev = pos.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    stats = torch.empty((b, 2), dtype=torch.float32, device=dev)
+    scale = torch.empty((1,), dtype=torch.float32, device=dev)
+    ws = zeroed_once(dev, "kge ns loss", lambda: load().gn_kge_ns_loss_workspace_bytes(b))
+    _call("gn_kge_ns_loss_forward_f32", ptr(pos), ptr(neg), ld(neg), b, k, ptr(weight), int(temperature is not None),
+          float(temperature or 0.0), ptr(loss), ptr(stats), ptr(scale), ptr(ws), ws.numel(), stream_ptr(dev))
+    return loss, stats, scale
+
+
+def kge_ns_loss_backward(pos, neg, weight, temperature, stats, scale, g, d_pos=None, d_neg=None):
+    """(d_pos [B], d_neg [B, K]) of gn_kge_ns_loss_backward_f32 from what the forward left in `stats` and `scale`; `g`: the
+    upstream gradient, a contiguous fp32 scalar on the device, or None for 1."""
+    b, k = kge_ns_block(pos, neg)
+    d_pos = torch.empty((b,), dtype=torch.float32, device=pos.device) if d_pos is None else d_pos
+    d_neg = torch.empty((b, k), dtype=torch.float32, device=pos.device) if d_neg is None else d_neg
+    _call("gn_kge_ns_loss_backward_f32", ptr(pos), ptr(neg), ld(neg), b, k, ptr(weight), int(temperature is not None),
+          float(temperature or 0.0), ptr(stats), ptr(scale), ptr(g), ptr(d_pos), ptr(d_neg), ld(d_neg), stream_ptr(pos.device))
+    return d_pos, d_neg
+
+
+KGE_ANY_RELATION = 1 << 62                                                     # gn_kge_candidates_sample without a filter reads no relation table
+
+
+def kge_candidates_sample(fixed, et, k, nentity, known, seed, step, out):
+    """gn_kge_candidates_sample: `out` (int64 [B, k], unit inner stride) = k candidates per (fixed[b], et[b]) that are not
+    partners of `known`'s row (None: no filter).  Bad ids: a row of -1 and the device's error flag."""
+    fixed, types = i64_vec(fixed), i64_vec(et)
+    b = int(fixed.numel())
+    nrel = known.num_et if known is not None else KGE_ANY_RELATION
+    _call("gn_kge_candidates_sample", ptr(fixed), ptr(types), b, int(k), int(nentity), nrel, None if known is None else known._h,
+          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), ptr(out), ld(out), ptr(error_flag(fixed.device)), stream_ptr(fixed.device))
+    return out
 
 
 GAT_MAX_ROW = 128                                                              # GN_GAT_MAX_ROW: floats of a row (heads x channels)

@@ -548,6 +548,33 @@ class KgeBatchScoreFn(torch.autograd.Function):
         return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None, None
 
 
+class KgeNegativeSamplingLossFn(torch.autograd.Function):
+    """The negative-sampling loss of a KGE mini-batch on raw scores pos [B] and neg [B, K] (csrc/kge_loss.hip), one launch
+    forward and one backward: ``loss = f(pos, neg, weight, temperature)`` with `weight` [B] or None (subsampling weights,
+    constants) and `temperature` a float or None (self-adversarial weighting of the negatives, a constant).  Saves the two
+    score tensors themselves - fp32 with a unit inner stride, as KgeScoreFn / KgeBatchScoreFn return them, they are not
+    copied - and the forward's row figures (m_b, 1 / Z_b) and 1 / (2 W); nothing of size [B, K] but d_neg is allocated."""
+
+    @staticmethod
+    def forward(ctx, pos, neg, weight, temperature):
+        p, n = pos.detach(), neg.detach()
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            p = p.contiguous().float()
+        if n.dtype != torch.float32 or (n.shape[1] > 1 and n.stride(1) != 1) or (n.shape[0] > 1 and n.stride(0) < n.shape[1]):
+            n = n.contiguous().float()
+        w = None if weight is None else weight.detach().contiguous().float()
+        loss, stats, scale = _hip.kge_ns_loss_forward(p, n, w, temperature)
+        ctx.temperature = temperature
+        ctx.save_for_backward(p, n, w, stats, scale)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        p, n, w, stats, scale = ctx.saved_tensors
+        d_pos, d_neg = _hip.kge_ns_loss_backward(p, n, w, ctx.temperature, stats, scale, g.contiguous().float())
+        return (d_pos if ctx.needs_input_grad[0] else None), (d_neg if ctx.needs_input_grad[1] else None), None, None
+
+
 class GatConvFn(torch.autograd.Function):
     """``act(softmax-weighted sum over the in-edges of (x W) + b)`` per head (GATConv.forward of torch_geometric 1.4 / 1.5 as
     baselines/NC_baselines/GAT.py:66-67 calls it, with the ReLU that follows).  The forward's launches are the same with and

@@ -11,7 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _hip
-from .autograd import KgeBatchScoreFn, KgeScoreFn
+from .autograd import KgeBatchScoreFn, KgeNegativeSamplingLossFn, KgeScoreFn
 
 PI = 3.14159265358979323846                                    # the constant the reference divides by (:214)
 
@@ -33,6 +33,83 @@ def self_adversarial_loss(positive_score, negative_score, adversarial_temperatur
     else:
         neg = (F.softmax(negative_score * adversarial_temperature, dim=1).detach() * neg).sum(dim=1)
     return (-pos.mean() - neg.mean()) / 2
+
+
+def _loss_block(positive_score, negative_score, adversarial_temperature, subsampling_weight):
+    """The shape checks of ``negative_sampling_loss``; the temperature as a float or None."""
+    if positive_score.dim() != 1 or positive_score.shape[0] < 1:
+        raise ValueError("positive_score must have shape [B] with B >= 1, got {}".format(tuple(positive_score.shape)))
+    b = positive_score.shape[0]
+    if negative_score.dim() != 2 or negative_score.shape[0] != b or negative_score.shape[1] < 1:
+        raise ValueError("negative_score must have shape [{}, K] with K >= 1, got {}".format(b, tuple(negative_score.shape)))
+    if subsampling_weight is not None and tuple(subsampling_weight.shape) != (b,):
+        raise ValueError("subsampling_weight must have shape [{}], got {}".format(b, tuple(subsampling_weight.shape)))
+    if adversarial_temperature is None:
+        return None
+    number = (int, float, np.integer, np.floating)
+    if isinstance(adversarial_temperature, bool) or not isinstance(adversarial_temperature, number):
+        raise ValueError("adversarial_temperature must be a number or None, got {!r}".format(adversarial_temperature))
+    return float(adversarial_temperature)
+
+
+def negative_sampling_loss(positive_score, negative_score, adversarial_temperature=None, subsampling_weight=None):
+    """``self_adversarial_loss`` in one HIP launch forward and one backward (csrc/kge_loss.hip), with the subsampling weights
+    of the code base these models come from: on RAW scores positive_score [B] and negative_score [B, K] (what
+    ``KGEModel.score`` returns; a column view of a wider matrix is read in place), with w = subsampling_weight [B]
+    (constants; None: ones),
+
+        loss = -(sum_b w_b logsigmoid(pos_b)) / (2 sum_b w_b) - (sum_b w_b N_b) / (2 sum_b w_b)
+
+    N_b the mean over k of logsigmoid(-neg_bk) or - with a temperature T - their sum weighted by
+    ``softmax(T * neg_b)`` taken as a constant.  A 0-d tensor; the gradients reach the embeddings through the score
+    functions' own backward.  Deterministic, no host synchronisation, capturable.  B == 0 or K == 0: ValueError."""
+    temperature = _loss_block(positive_score, negative_score, adversarial_temperature, subsampling_weight)
+    _hip.require_gpu(positive_score, negative_score, subsampling_weight)
+    return KgeNegativeSamplingLossFn.apply(positive_score, negative_score, subsampling_weight, temperature)
+
+
+def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0, step=None, out=None):
+    """int64 [B, K]: K candidate entities per positive (positive[0, b], et[b], positive[1, b]) for the batch modes of
+    ``KGEModel.forward`` / ``.score``, drawn on the device (gn_kge_candidates_sample) uniformly, with replacement, from the
+    entities that are not known partners.  `side` and `known` as for ``rank`` / ``top_k``: ``side="tail"`` fixes the head
+    positive[0] and takes a KnownPairs keyed (r, head) - candidate tails t' with (h, r, t') known are never drawn;
+    ``side="head"`` fixes the tail positive[1] and takes one built from the FLIPPED lists.  ``known=None``: no filter
+    (``torch.randint``'s distribution, this sampler's stream; the relation table's size then comes from nowhere, and a
+    relation id is only held to be non-negative).  The draw is a pure function of (seed, b, k, the row's
+    partners), documented in include/gripnet_hip.h.  `step`: a one-element int64 tensor on the device; the draw is then that
+    of ``seed + step``, read on the device and NOT advanced - ``step += 1`` after the call is an op of the caller's, so a
+    captured mini-batch draws anew at every replay.  `out`: an int64 [B, K] tensor to fill (unit inner stride; a column
+    view of a wider matrix is written in place).  No host synchronisation: a positive with an id outside its table gets a
+    row of -1 (NaN scores) and a row that knows every entity keeps its last draw; both raise at the next synchronising check
+    (``_hip.raise_if_index_errors``)."""
+    if side not in _hip.KGE_SIDES:
+        raise ValueError("side must be 'tail' or 'head', got {!r}".format(side))
+    if positive.dim() != 2 or positive.shape[0] != 2:
+        raise ValueError("positive must have shape [2, B], got {}".format(tuple(positive.shape)))
+    b = positive.shape[1]
+    if et.dim() != 1 or et.shape[0] != b:
+        raise ValueError("edge_type has {} entries for {} positives".format(et.numel(), b))
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or int(K) < 1:
+        raise ValueError("K must be a positive integer, got {!r}".format(K))
+    if isinstance(nentity, bool) or not isinstance(nentity, (int, np.integer)) or not 1 <= int(nentity) < 2 ** 31:
+        raise ValueError("nentity must be an integer in [1, 2^31), got {!r}".format(nentity))
+    K, nentity = int(K), int(nentity)
+    if known is not None:
+        if not isinstance(known, _hip.KnownPairs):
+            raise TypeError("`known` must be a KnownPairs, got {}".format(type(known).__name__))
+        if known.num_nodes != nentity or known.device != positive.device:
+            raise ValueError("KnownPairs was built for {} entities on {}; the call has {} on {}".format(
+                known.num_nodes, known.device, nentity, positive.device))
+    if step is not None and (step.dtype != torch.int64 or step.numel() != 1 or step.device != positive.device):
+        raise ValueError("`step` must be a one-element int64 tensor on {}".format(positive.device))
+    if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (b, K) or out.device != positive.device or
+                            (K > 1 and out.stride(1) != 1) or (b > 1 and out.stride(0) < K)):
+        raise ValueError("`out` must be an int64 [{}, {}] tensor with a unit inner stride on {}".format(b, K, positive.device))
+    _hip.require_gpu(positive, et)
+    if out is None:
+        out = torch.empty((b, K), dtype=torch.int64, device=positive.device)
+    fixed = positive[0] if side == "tail" else positive[1]
+    return _hip.kge_candidates_sample(fixed, et, K, nentity, known, seed, step, out)
 
 
 class KGEModel(nn.Module):
@@ -122,6 +199,25 @@ class KGEModel(nn.Module):
         """The raw scores (before the log-sigmoid), [E] or - in the batch modes - [B, K]: differentiable; for losses on raw
         scores (``self_adversarial_loss``), metrics and tests."""
         return self._score(sample, et, False, mode)
+
+    def negative_sampling_loss(self, positive, et, negatives, mode="tail-batch", adversarial_temperature=None,
+                               subsampling_weight=None):
+        """The loss of one mini-batch: ``negative_sampling_loss(self.score(positive, et), self.score((positive, negatives),
+        et, mode), adversarial_temperature, subsampling_weight)`` - positive [2, B], et [B], negatives int64 [B, K]
+        (``sample_candidates``) standing for the tails ('tail-batch') or the heads ('head-batch').  The two scorers and one
+        launch for the loss; ``loss.backward()`` is the loss's one launch and the two scorers' own backward."""
+        if mode not in _BATCH_SIDES:
+            raise ValueError("mode %s not supported" % mode)
+        if positive.dim() != 2 or positive.shape[0] != 2 or positive.shape[1] < 1:
+            raise ValueError("positive must have shape [2, B] with B >= 1, got {}".format(tuple(positive.shape)))
+        if negatives.dim() != 2 or negatives.shape[0] != positive.shape[1] or negatives.shape[1] < 1:
+            raise ValueError("negatives must have shape [{}, K] with K >= 1, got {}".format(
+                positive.shape[1], tuple(negatives.shape)))
+        if subsampling_weight is not None and tuple(subsampling_weight.shape) != (positive.shape[1],):
+            raise ValueError("subsampling_weight must have shape [{}], got {}".format(
+                positive.shape[1], tuple(subsampling_weight.shape)))
+        return negative_sampling_loss(self.score(positive, et), self.score((positive, negatives), et, mode),
+                                      adversarial_temperature, subsampling_weight)
 
     def _eval_operands(self, *index):
         ent, rel = self.entity_embedding, self.relation_embedding

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 169 /* 0.1.63 */
+#define GN_VERSION 170 /* 0.1.64 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -698,6 +698,49 @@ GN_API gn_status gn_kge_batch_backward_f32(int model, const float* ent, int64_t 
                                     const float* raw_scores /* nullable */, float* d_ent, int64_t ld_dent, float* d_rel,
                                     int64_t ld_drel, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The negative-sampling loss of a KGE mini-batch on RAW scores, and its gradient: pos [B] (gn_kge_forward_f32 without the
+ * log-sigmoid), neg [B, K] with a leading dimension ld_neg >= K (gn_kge_batch_forward_f32 likewise), weight [B] (nullable: 1;
+ * the subsampling weights of the code base KGEModel comes from, constants) and, with `adversarial` != 0, a temperature T.
+ * With ls(x) = min(x, 0) - log1p(exp(-|x|)):
+ *   P_b = ls(pos_b)
+ *   N_b = (1 / K) sum_k ls(-s_bk)                                              (adversarial == 0; temperature is not read)
+ *   N_b = sum_k p_bk ls(-s_bk),   p_b = softmax_k(T s_bk), a constant          (adversarial != 0)
+ *   W   = sum_b w_b                                                            (B without weights)
+ *   loss = -(sum_b w_b P_b) / (2 W) - (sum_b w_b N_b) / (2 W)
+ *   d_pos[b]    = -g w_b sigma(-pos_b) / (2 W)
+ *   d_neg[b, k] = +g w_b p_bk sigma(s_bk) / (2 W)                              (p_bk = 1 / K when adversarial == 0)
+ * g = *upstream (a device scalar; NULL: 1).  Without weights this is the loss of TransE_DistMult_ComplEx_RotatE.py:266-286
+ * on one block, (-logsigmoid(pos).mean() - neg.mean()) / 2.
+ * Forward, one launch, every score read once: *loss, *scale = 1 / (2 W) and, per row, row_stats[2 b] = m_b = max_k fl(T s_bk)
+ * and row_stats[2 b + 1] = 1 / Z_b, Z_b = sum_k exp(T s_bk - m_b), which the backward recomputes p_bk from: the argument is
+ * the single rounding fmaf(T, s, -m_b), the exponential the library's expf (not the hardware's exp2 on x log2 e, which
+ * loses |x| units at the arguments down to -87 that a weight far below its row's maximum has).  row_stats may be NULL when
+ * adversarial == 0; given there, its second word carries 1 / K, or NaN for a row with a NaN score.  Rows of up to 32 scores
+ * share a wave in power-of-two lane groups, a longer row is one wave's, held in registers up to 1,024 scores and taken in
+ * parts of 1,024 with a running maximum beyond; 16-byte loads when neg is 16-byte aligned and ld_neg a multiple of four,
+ * 4-byte loads into the same registers otherwise (the same bits).  The sums over a row and over the rows are taken in
+ * double, each in a fixed order: rows are dealt to the waves by the grid, a workgroup's three partial sums are added in
+ * workgroup order by the last workgroup to arrive.  No float atomics, no host synchronisation, capturable.
+ * Backward, one launch: d_pos [B] and d_neg [B, K] (ld_dneg >= K) from the scores and row_stats / scale as the forward
+ * left them; nothing else of size [B, K] exists.  An element is g * (c_b * (e * sigma(s))) with c_b = w_b / (2 W Z_b) taken in
+ * double and rounded once: an upstream of 1 changes no bit, any other costs one rounding.
+ * A NaN score makes the loss NaN and its row of d_neg NaN (without row_stats: its own element); a NaN positive makes the
+ * loss and its d_pos NaN; every other gradient element keeps its bits.  A row with w_b = 0 gets exact zeros.
+ * `workspace`: gn_kge_ns_loss_workspace_bytes(B) bytes, 8-byte aligned, ZEROED ONCE by the caller (the launch leaves it
+ * ready for the next one); calls on one workspace must be stream-ordered.
+ * GN_ERR_INVALID_ARG: B < 1 or K < 1 (K < 2^31), a leading dimension below K, a null operand, a short workspace. */
+GN_API size_t gn_kge_ns_loss_workspace_bytes(int64_t num_positives);
+GN_API gn_status gn_kge_ns_loss_forward_f32(const float* pos, const float* neg, int64_t ld_neg, int64_t num_positives,
+                                     int64_t num_candidates, const float* weight /* nullable */, int adversarial,
+                                     float temperature, float* loss /* [1] */,
+                                     float* row_stats /* [B, 2]; nullable unless adversarial */, float* scale /* [1]: 1 / (2 W) */,
+                                     void* workspace, size_t workspace_bytes, void* stream);
+GN_API gn_status gn_kge_ns_loss_backward_f32(const float* pos, const float* neg, int64_t ld_neg, int64_t num_positives,
+                                      int64_t num_candidates, const float* weight /* nullable */, int adversarial,
+                                      float temperature, const float* row_stats, const float* scale,
+                                      const float* upstream /* device, nullable */, float* d_pos, float* d_neg, int64_t ld_dneg,
+                                      void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Graph attention: GATConv of torch_geometric 1.4 / 1.5 as baselines/NC_baselines/GAT.py uses it (single `weight`, single
  * `att`).  The graph is a plan of gn_gcn_plan_create: it is the layer's working list already - input loops dropped, one
@@ -831,6 +874,30 @@ GN_API gn_status gn_kge_topk_f32(int model, int side, const float* ent, int64_t 
                           const int64_t* edge_type, int64_t num_queries, int64_t k, float gamma, float phase_divisor,
                           const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids, int32_t* error_flag,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* The candidate block of a KGE mini-batch: cand[b * ld_cand + k] (int64, ld_cand >= K), K entities per positive
+ * (fixed[b], edge_type[b]) drawn uniformly, with replacement, from the entities that are NOT partners of the row
+ * (edge_type[b], fixed[b]) of `known` (nullable: no filter) - the filtered negatives of the code base KGEModel comes from,
+ * for gn_kge_batch_forward_f32.  `known` is keyed as for gn_kge_rank_f32: (relation, head) for candidate tails, built from
+ * the flipped lists for candidate heads; it must have been built for num_entities and num_relations (GN_ERR_INVALID_ARG).
+ * THE DRAW IS PART OF THIS INTERFACE.  With mix64 the splitmix64 finaliser
+ *   mix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
+ * (64-bit wrapping arithmetic), seed' = seed + *step when `step` (a device counter, 8-byte aligned, nullable) is given,
+ * n = num_entities and element (b, k):
+ *   base = mix64(seed' ^ ((uint64)(b * K + k) * 0xD6E8FEB86659FD93))
+ *   attempt a = 0, 1, ...:   h = mix64(base + a);   c = (low32(h) * n) >> 32
+ *   cand[b, k] = the first c that is not a partner of the row   (without `known`: attempt 0)
+ * Membership is a binary search in the row's sorted partners (duplicates do no harm).  After 4,096 attempts - the typed
+ * sampler's cap - the last draw is written and bit 1 of *error_flag (nullable) is set: the row knows (nearly) every
+ * entity.  A fixed entity or relation outside its table writes -1 into the whole row and sets bit 0; nothing outside the
+ * known pairs' row table is read, and the scorers turn such a row into NaN.  `step` is read, not advanced: the caller's
+ * step += 1 is an ordinary launch of its own, so a captured mini-batch draws anew at every replay.  No host
+ * synchronisation.  n < 2^31.  B == 0 or K == 0: nothing is written. */
+GN_API gn_status gn_kge_candidates_sample(const int64_t* fixed, const int64_t* edge_type, int64_t num_positives,
+                                   int64_t num_candidates, int64_t num_entities, int64_t num_relations,
+                                   const gn_known_pairs* known /* nullable */, uint64_t seed,
+                                   const uint64_t* step /* nullable, device */, int64_t* cand, int64_t ld_cand,
+                                   int32_t* error_flag, void* stream);
 
 /* Independent small products in ONE launch.  Between gn_dense_batch_begin() and gn_dense_batch_end(stream) (per host thread,
  * not nested) the calls that carry GN_GEMM_JOIN_BATCH / GN_XTG_JOIN_BATCH - those of gn_gemm_f32 that take the deep-and-narrow kernel (a single product with at most 64 rows or 32 columns
