@@ -31,6 +31,14 @@ gripnet_amd.kge.self_adversarial_loss in torch ops (no filter, no weights).  Wit
 always did.
 
     python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3 --negatives 256 --adversarial-temperature 1.0 --filter-negatives
+
+`--typed-candidates` restricts `--rank` and `--negatives K` to the entities that can fill the slot at all (the reference
+draws its evaluation negatives from the drugs only, :277-279): a drug-drug relation's heads and tails are drugs
+[0, n_drug), the gene-gene relation's are genes [n_drug, n_node), the bidirectional gene-drug relation keeps every
+entity; one table serves both sides (gripnet_amd.utils.candidate_ranges, the `candidates` argument).  The triples ranked
+are then sorted by relation, so that a workgroup's queries share a range and the scan is as short as the range.
+
+    python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3 --rank --typed-candidates
 """
 import argparse
 import os
@@ -48,7 +56,8 @@ from gripnet_amd import _hip
 from gripnet_amd.kge import negative_sampling_loss, sample_candidates, self_adversarial_loss
 from gripnet_amd.synth import make_rgcn_pose
 from gripnet_amd.decoder import KnownPairs
-from gripnet_amd.utils import EPS, device_negative_sampler, ranking_metrics, relation_metrics, typed_negative_sampling
+from gripnet_amd.utils import (EPS, candidate_ranges, device_negative_sampler, ranking_metrics, relation_metrics,
+                               typed_negative_sampling)
 
 
 class Negatives:
@@ -116,6 +125,8 @@ def main():
     ap.add_argument("--filter-negatives", action="store_true", help="never draw a known training triple as a negative")
     ap.add_argument("--subsampling", action="store_true", help="weight a positive by 1 / sqrt(count(r, h) + count(r, t) + 4)")
     ap.add_argument("--torch-loss", action="store_true", help="torch.randint candidates and the loss in torch ops")
+    ap.add_argument("--typed-candidates", action="store_true",
+                    help="--rank and --negatives take a relation's candidates from the node type that can fill the slot")
     args = ap.parse_args()
     torch.manual_seed(1111)
     np.random.seed(1111)
@@ -164,8 +175,12 @@ def main():
     batched = args.negatives is not None or args.adversarial_temperature is not None
     n_negatives = 256 if args.negatives is None else args.negatives
 
-    if args.torch_loss and (args.filter_negatives or args.subsampling):
-        ap.error("--torch-loss is the unfiltered, unweighted formulation")
+    if args.torch_loss and (args.filter_negatives or args.subsampling or args.typed_candidates):
+        ap.error("--torch-loss is the unfiltered, unweighted, untyped formulation")
+    typed = None
+    if args.typed_candidates:                                         # drug-drug relations, then gene-gene, then gene-drug (both ways)
+        R, n_drug, n_node = int(data.n_edge_type), int(data.n_drug), int(data.n_node)
+        typed = candidate_ranges(R, n_node, [(0, R - 2, 0, n_drug), (R - 2, R - 1, n_drug, n_node)], device=device)
     sides = {"tail-batch": "tail", "head-batch": "head"}
     known = {"tail": None, "head": None}
     if batched and args.filter_negatives:
@@ -197,7 +212,7 @@ def main():
                                              args.adversarial_temperature)
             else:
                 candidates = sample_candidates(positive, et, n_negatives, data.n_node, side=sides[mode], known=known[sides[mode]],
-                                               seed=(1111 + epoch) * len(starts) + i)
+                                               seed=(1111 + epoch) * len(starts) + i, candidates=typed)
                 loss = negative_sampling_loss(model.score(positive, et), model.score((positive, candidates), et, mode=mode),
                                               args.adversarial_temperature, None if weights is None else weights[pick])
             loss.backward()
@@ -224,12 +239,19 @@ def main():
                  "head": KnownPairs([(ei.flip(0), et) for ei, et in lists], data.n_node, data.n_edge_type)}   # (relation, tail)
         e = data.train_idx.shape[1]
         pick = torch.randperm(e, generator=torch.Generator().manual_seed(7))[:args.rank_sample].to(device)
+        if typed is not None:
+            pick = pick[torch.sort(data.train_et[pick], stable=True).indices]      # a workgroup's queries share a range
         sample, et = data.train_idx[:, pick].contiguous(), data.train_et[pick].contiguous()
+        against = "{} entities".format(data.n_node)
+        if typed is not None:
+            width = (typed[:, 1] - typed[:, 0])[et]
+            against = "{}..{} candidates of the relation's type, {:.0f} on average".format(
+                int(width.min()), int(width.max()), width.double().mean().item())
         for side in ("tail", "head"):
-            greater, ties = model.rank(sample, et, side=side, known=known[side])
+            greater, ties = model.rank(sample, et, side=side, known=known[side], candidates=typed)
             m = ranking_metrics(greater, ties, et, data.n_edge_type)
-            print("filtered ranking, {} side ({} triples against {} entities):   mrr:{:0.4f}   hits@1:{:0.4f}   hits@3:{:0.4f}   "
-                  "hits@10:{:0.4f}".format(side, sample.shape[1], data.n_node, m["mrr_all"].item(), m["hits@1_all"].item(),
+            print("filtered ranking, {} side ({} triples against {}):   mrr:{:0.4f}   hits@1:{:0.4f}   hits@3:{:0.4f}   "
+                  "hits@10:{:0.4f}".format(side, sample.shape[1], against, m["mrr_all"].item(), m["hits@1_all"].item(),
                                            m["hits@3_all"].item(), m["hits@10_all"].item()))
 
 

@@ -29,7 +29,7 @@ RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 170                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 171                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -124,6 +124,7 @@ SIGNATURES = {
     "gn_kge_ns_loss_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, C.c_float, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_ns_loss_backward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, C.c_float, _p, _p, _p, _p, _p, _i64, _p]),
     "gn_kge_candidates_sample": (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, C.c_uint64, _p, _p, _i64, _p, _p]),
+    "gn_kge_candidates_sample_ranged": (_int, [_p, _p, _i64, _i64, _i64, _i64, _p, C.c_uint64, _p, _p, _i64, _p, _p, _p]),
     "gn_gat_logits_f32": (_int, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
     "gn_gat_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, C.c_float, _p, _int, _int, _p, _i64, _p, _p, _p, _p]),
     "gn_gat_backward_dst_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _p, _p, _p, C.c_float, _p, _i64, _int, _p, _p, _p, _p]),
@@ -133,6 +134,8 @@ SIGNATURES = {
     "gn_kge_rank_workspace_bytes": (_sz, [_int, _i64, _i64, _i64]),
     "gn_kge_rank_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_topk_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p]),
+    "gn_kge_rank_ranged_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p, _p]),
+    "gn_kge_topk_ranged_f32": (_int, [_int, _int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _i64, _i64, C.c_float, C.c_float, _p, _p, _p, _p, _p, _sz, _p, _p]),
     "gn_negative_sampler_create": (_int, [_p, _p, _p, _i64, _i64, _i64, _p, C.POINTER(_p)]),
     "gn_negative_sampler_destroy": (None, [_p]),
     "gn_negative_sampler_sample": (_int, [_p, C.c_uint64, _p, _p, _p, _p]),
@@ -142,6 +145,8 @@ SIGNATURES = {
     "gn_known_pairs_destroy": (None, [_p]),
     "gn_distmult_rank_f32": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "gn_distmult_topk_f32": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "gn_distmult_rank_ranged_f32": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "gn_distmult_topk_ranged_f32": (_int, [_p, _i64, _i64, _i64, _p, _i64, _i64, _p, _p, _i64, _i64, _p, _p, _p, _p, _p, _p]),
     "gn_rgcn_weight_grad_workspace_bytes": (_sz, [_p, _i64, _i64]),
     "gn_rgcn_weight_grad_supported": (_int, [_p, _i64, _i64]),
     "gn_rgcn_weight_grad_f32": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _i64, _i64, _p, _p, _sz, _p]),
@@ -1567,14 +1572,32 @@ def kge_ns_loss_backward(pos, neg, weight, temperature, stats, scale, g, d_pos=N
 KGE_ANY_RELATION = 1 << 62                                                     # gn_kge_candidates_sample without a filter reads no relation table
 
 
-def kge_candidates_sample(fixed, et, k, nentity, known, seed, step, out):
-    """gn_kge_candidates_sample: `out` (int64 [B, k], unit inner stride) = k candidates per (fixed[b], et[b]) that are not
-    partners of `known`'s row (None: no filter).  Bad ids: a row of -1 and the device's error flag."""
+def candidate_table(candidates, num_relations, device):
+    """The per-relation candidate ranges of a ranged call, checked (ValueError) and contiguous: an int64 [num_relations, 2]
+    tensor on `device` (num_relations None: whatever the table has); None stays None.  The values are read on the device."""
+    if candidates is None:
+        return None
+    if not isinstance(candidates, torch.Tensor) or candidates.dtype != torch.int64 or candidates.dim() != 2 or \
+            candidates.shape[1] != 2 or (num_relations is not None and candidates.shape[0] != num_relations) or \
+            candidates.device != device:
+        raise ValueError("`candidates` must be an int64 [{}, 2] tensor on {}, got {}".format(
+            "R" if num_relations is None else num_relations, device,
+            "{} {} on {}".format(candidates.dtype, tuple(candidates.shape), candidates.device)
+            if isinstance(candidates, torch.Tensor) else type(candidates).__name__))
+    return candidates if candidates.is_contiguous() else candidates.contiguous()
+
+
+def kge_candidates_sample(fixed, et, k, nentity, known, seed, step, out, candidates=None):
+    """gn_kge_candidates_sample_ranged: `out` (int64 [B, k], unit inner stride) = k candidates per (fixed[b], et[b]) that are
+    not partners of `known`'s row (None: no filter), from the range `candidates` gives the relation (int64 [R, 2]; None: every
+    entity).  Bad ids: a row of -1 and the device's error flag."""
     fixed, types = i64_vec(fixed), i64_vec(et)
     b = int(fixed.numel())
-    nrel = known.num_et if known is not None else KGE_ANY_RELATION
-    _call("gn_kge_candidates_sample", ptr(fixed), ptr(types), b, int(k), int(nentity), nrel, None if known is None else known._h,
-          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), ptr(out), ld(out), ptr(error_flag(fixed.device)), stream_ptr(fixed.device))
+    candidates = candidate_table(candidates, None if known is None else known.num_et, fixed.device)
+    nrel = known.num_et if known is not None else KGE_ANY_RELATION if candidates is None else int(candidates.shape[0])
+    _call("gn_kge_candidates_sample_ranged", ptr(fixed), ptr(types), b, int(k), int(nentity), nrel, None if known is None else known._h,
+          int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(step), ptr(out), ld(out), ptr(error_flag(fixed.device)), stream_ptr(fixed.device),
+          ptr(candidates))
     return out
 
 
@@ -1736,31 +1759,34 @@ def _known_handle(known, z, weight):
     return known._h
 
 
-def distmult_rank(z, edge_index, edge_type, weight, known=None):
+def distmult_rank(z, edge_index, edge_type, weight, known=None, candidates=None):
     """(greater, ties) int32 [E]: per pair (u, v, r) the non-known candidates v' != v scored above / equal to (u, v, r)
-    (gn_distmult_rank_f32).  `z` rows contiguous fp32."""
+    (gn_distmult_rank_ranged_f32).  `z` rows contiguous fp32.  `candidates`: int64 [R, 2] ranges per relation, or None."""
+    candidates = candidate_table(candidates, weight.shape[0], z.device)
     ei, u, v, e = edge_rows(edge_index)
     et = i64_vec(edge_type)
     if et.numel() != e:
         raise ValueError("edge_type has {} entries for {} edges".format(et.numel(), e))
     greater = torch.empty((e,), dtype=torch.int32, device=z.device)
     ties = torch.empty((e,), dtype=torch.int32, device=z.device)
-    _call("gn_distmult_rank_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], u, v,
-          ptr(et), e, _known_handle(known, z, weight), ptr(greater), ptr(ties), ptr(error_flag(z.device)), stream_ptr(z.device))
+    _call("gn_distmult_rank_ranged_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], u, v,
+          ptr(et), e, _known_handle(known, z, weight), ptr(greater), ptr(ties), ptr(error_flag(z.device)), stream_ptr(z.device),
+          ptr(candidates))
     return greater, ties
 
 
-def distmult_topk(z, nodes, edge_type, weight, k, known=None):
-    """(scores fp32 [Q, k], partners int64 [Q, k]) of the queries (nodes[q], edge_type[q]) (gn_distmult_topk_f32)."""
+def distmult_topk(z, nodes, edge_type, weight, k, known=None, candidates=None):
+    """(scores fp32 [Q, k], partners int64 [Q, k]) of the queries (nodes[q], edge_type[q]) (gn_distmult_topk_ranged_f32)."""
+    candidates = candidate_table(candidates, weight.shape[0], z.device)
     nodes, et = i64_vec(nodes), i64_vec(edge_type)
     if nodes.dim() != 1 or et.dim() != 1 or nodes.numel() != et.numel():
         raise ValueError("nodes and edge_type must be 1-D of one length, got {} and {}".format(tuple(nodes.shape), tuple(et.shape)))
     q = int(nodes.numel())
     scores = torch.empty((q, k), dtype=torch.float32, device=z.device)
     ids = torch.empty((q, k), dtype=torch.int64, device=z.device)
-    _call("gn_distmult_topk_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], ptr(nodes),
+    _call("gn_distmult_topk_ranged_f32", ptr(z), ld(z), z.shape[0], z.shape[1], ptr(weight), ld(weight), weight.shape[0], ptr(nodes),
           ptr(et), q, int(k), _known_handle(known, z, weight), ptr(scores), ptr(ids), ptr(error_flag(z.device)),
-          stream_ptr(z.device))
+          stream_ptr(z.device), ptr(candidates))
     return scores, ids
 
 
@@ -1786,9 +1812,11 @@ def _kge_rank_operands(model, ent, rel, side, known, queries):
     return m, KGE_SIDES[side], h, _known_handle(known, ent, rel), ws, need
 
 
-def kge_rank(model, ent, rel, sample, et, gamma, divisor, side="tail", known=None):
+def kge_rank(model, ent, rel, sample, et, gamma, divisor, side="tail", known=None, candidates=None):
     """(greater, ties) int32 [E] of the triples (sample[0, e], et[e], sample[1, e]) against every candidate tail (`side`
-    "tail") or head ("head") that is not in `known` (gn_kge_rank_f32).  `ent`, `rel`: rows contiguous fp32."""
+    "tail") or head ("head") that is not in `known` (gn_kge_rank_ranged_f32).  `ent`, `rel`: rows contiguous fp32.
+    `candidates`: int64 [R, 2] ranges per relation for that side, or None."""
+    candidates = candidate_table(candidates, rel.shape[0], ent.device)
     idx, head, tail, e = edge_rows(sample)
     types = i64_vec(et)
     if types.numel() != e:
@@ -1797,14 +1825,15 @@ def kge_rank(model, ent, rel, sample, et, gamma, divisor, side="tail", known=Non
     fixed, truth = (head, tail) if sd == 0 else (tail, head)
     greater = torch.empty((e,), dtype=torch.int32, device=ent.device)
     ties = torch.empty((e,), dtype=torch.int32, device=ent.device)
-    _call("gn_kge_rank_f32", m, sd, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, fixed, truth, ptr(types), e,
+    _call("gn_kge_rank_ranged_f32", m, sd, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, fixed, truth, ptr(types), e,
           float(gamma), float(divisor), kh, ptr(greater), ptr(ties), ptr(error_flag(ent.device)), ptr(ws), need,
-          stream_ptr(ent.device))
+          stream_ptr(ent.device), ptr(candidates))
     return greater, ties
 
 
-def kge_topk(model, ent, rel, entities, et, k, gamma, divisor, side="tail", known=None):
-    """(scores fp32 [Q, k], ids int64 [Q, k]) of the queries (entities[q], et[q]) (gn_kge_topk_f32)."""
+def kge_topk(model, ent, rel, entities, et, k, gamma, divisor, side="tail", known=None, candidates=None):
+    """(scores fp32 [Q, k], ids int64 [Q, k]) of the queries (entities[q], et[q]) (gn_kge_topk_ranged_f32)."""
+    candidates = candidate_table(candidates, rel.shape[0], ent.device)
     entities, types = i64_vec(entities), i64_vec(et)
     if entities.dim() != 1 or types.dim() != 1 or entities.numel() != types.numel():
         raise ValueError("entities and edge_type must be 1-D of one length, got {} and {}".format(
@@ -1813,9 +1842,9 @@ def kge_topk(model, ent, rel, entities, et, k, gamma, divisor, side="tail", know
     m, sd, h, kh, ws, need = _kge_rank_operands(model, ent, rel, side, known, q)
     scores = torch.empty((q, k), dtype=torch.float32, device=ent.device)
     ids = torch.empty((q, k), dtype=torch.int64, device=ent.device)
-    _call("gn_kge_topk_f32", m, sd, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(entities), ptr(types), q,
+    _call("gn_kge_topk_ranged_f32", m, sd, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(entities), ptr(types), q,
           int(k), float(gamma), float(divisor), kh, ptr(scores), ptr(ids), ptr(error_flag(ent.device)), ptr(ws), need,
-          stream_ptr(ent.device))
+          stream_ptr(ent.device), ptr(candidates))
     return scores, ids
 
 

@@ -28,17 +28,23 @@
 // prefix: no atomics, the same slots every run); before a buffer can overflow, list and buffer are merged by rank counting
 // (the order is total: ids are unique), which is deterministic as well.
 //
+// Candidate ranges (the _ranged entry points).  A table [R][2] of (lo, hi) per relation admits candidate v for a query of
+// relation r iff lo_r <= v < hi_r, on top of the rules above: a query reads its row once, the workgroup scans the stages
+// that hold a column of the union of its valid queries' ranges (rounded down to a stage; the first bitmap window is built
+// from its own start) and masks per row.  A score does not depend on where the scan starts, so a ranged result is the
+// full scan's restricted to the range, bit for bit; without a table every range is (0, n).
+//
 // The engine itself is rank_engine.cuh: kge_rank.hip runs it as well, with prepared query rows as the A operand.
 #include "rank_engine.cuh"
 
 extern "C" {
 
-gn_status gn_distmult_rank_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
-                               const int64_t* u, const int64_t* v, const int64_t* et, int64_t Q, const gn_known_pairs* known,
-                               int32_t* greater, int32_t* ties, int32_t* err, void* stream) {
+gn_status gn_distmult_rank_ranged_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
+                                      const int64_t* u, const int64_t* v, const int64_t* et, int64_t Q, const gn_known_pairs* known,
+                                      int32_t* greater, int32_t* ties, int32_t* err, void* stream, const int64_t* cand_range) {
     RankArgs a;
     int S = 0;
-    const gn_status s = fill_args(a, z, ld_z, n, f, d, ld_d, R, u, et, Q, known, err, S);
+    const gn_status s = fill_args(a, z, ld_z, n, f, d, ld_d, R, u, et, Q, known, cand_range, err, S);
     if (s != GN_OK) return s;
     if (Q == 0) return GN_OK;
     GN_REQUIRE(z && d && u && v && et && greater && ties, "operand pointer is null");
@@ -47,19 +53,31 @@ gn_status gn_distmult_rank_f32(const float* z, int64_t ld_z, int64_t n, int64_t 
     return launch<false>(a, S, gn::as_stream(stream));
 }
 
-gn_status gn_distmult_topk_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
-                               const int64_t* u, const int64_t* et, int64_t Q, int64_t k, const gn_known_pairs* known,
-                               float* scores, int64_t* ids, int32_t* err, void* stream) {
+gn_status gn_distmult_rank_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
+                               const int64_t* u, const int64_t* v, const int64_t* et, int64_t Q, const gn_known_pairs* known,
+                               int32_t* greater, int32_t* ties, int32_t* err, void* stream) {
+    return gn_distmult_rank_ranged_f32(z, ld_z, n, f, d, ld_d, R, u, v, et, Q, known, greater, ties, err, stream, nullptr);
+}
+
+gn_status gn_distmult_topk_ranged_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
+                                      const int64_t* u, const int64_t* et, int64_t Q, int64_t k, const gn_known_pairs* known,
+                                      float* scores, int64_t* ids, int32_t* err, void* stream, const int64_t* cand_range) {
     GN_REQUIRE(k >= 1 && k <= kMaxK, "k must be in [1, %d], got %lld", kMaxK, (long long)k);
     RankArgs a;
     int S = 0;
-    const gn_status s = fill_args(a, z, ld_z, n, f, d, ld_d, R, u, et, Q, known, err, S);
+    const gn_status s = fill_args(a, z, ld_z, n, f, d, ld_d, R, u, et, Q, known, cand_range, err, S);
     if (s != GN_OK) return s;
     if (Q == 0) return GN_OK;
     GN_REQUIRE(z && d && u && et && scores && ids, "operand pointer is null");
     GN_REQUIRE(n > 0 && R > 0, "queries given but the node or relation table is empty");
     a.scores = scores; a.ids = ids; a.k = (int)k;
     return launch<true>(a, S, gn::as_stream(stream));
+}
+
+gn_status gn_distmult_topk_f32(const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
+                               const int64_t* u, const int64_t* et, int64_t Q, int64_t k, const gn_known_pairs* known,
+                               float* scores, int64_t* ids, int32_t* err, void* stream) {
+    return gn_distmult_topk_ranged_f32(z, ld_z, n, f, d, ld_d, R, u, et, Q, k, known, scores, ids, err, stream, nullptr);
 }
 
 }  // extern "C"

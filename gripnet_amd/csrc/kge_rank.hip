@@ -32,7 +32,11 @@
 //   * top-k: one list per query in LDS ([k] sorted + a buffer of kDistCap = 128), its length, fill and threshold in lane j;
 //     a candidate that beats the threshold takes a slot from the ballot's prefix count; a buffer that the next stage could
 //     overflow (> 64 entries) is merged by merge_row's rank counting - no float atomics, the same bits in every run;
-//   * filter: per window of 2,048 columns a [8][64]-word bitmap per wave (bitmap_set of rank_engine.cuh).
+//   * filter: per window of 2,048 columns a [8][64]-word bitmap per wave (bitmap_set of rank_engine.cuh);
+//   * candidate ranges (RANGED; the _ranged entry points): lane j keeps the range (lo, hi) of query j's relation next to
+//     its filter row, the workgroup scans the stages that hold a candidate of the union of its queries' ranges and a
+//     candidate is admitted per query iff lo <= v < hi; a score does not depend on where the scan starts, so the result is
+//     the full scan's restricted to the range, bit for bit.
 // Budget at the widest row (EW = 128, head side): registers 128 (row) + ~40; LDS 33 KB stage + 32 KB queries
 // (4 waves x 8 x 256 floats) + 8 KB bitmaps + (top-k) 4 x 8 x (k + 128) x 8 B <= 48 KB: 121 KB of the CU's 160, one
 // workgroup per CU, one wave per SIMD.  At the driver's H = 32 (RotatE: EW = 64): 16.6 + 16 + 8 + 35 KB.
@@ -52,6 +56,7 @@ struct DistArgs {
     const float* rel; const float* rel_im; int64_t ld_rel; int R;   // TransE: the table; RotatE: cos and sin of its phases
     const int64_t* fixed; const int64_t* truth; const int64_t* et; int64_t Q;
     const int32_t* rowptr; const int32_t* partners;                 // null: no filter
+    const int64_t* cand_range;                                       // [R][2] candidate range per relation; null: (0, n)
     float gamma;
     int32_t* greater; int32_t* ties;                                // rank
     float* scores; int64_t* ids; int k;                             // top-k
@@ -95,7 +100,9 @@ __device__ __forceinline__ float scan_score(const float* q, const float (&row)[D
     return finish<M>(acc, gamma);
 }
 
-template <int M, int SIDE, bool TOPK, int W>
+// RANGED: a.cand_range gives every query a candidate range; without it the range test is `v < n` and the scan runs over
+// [0, n), the kernel as it was before the ranges (a template parameter for the reason given at rank_engine.cuh's rank_scan).
+template <int M, int SIDE, bool TOPK, int W, bool RANGED>
 __global__ __launch_bounds__(256) void k_kge_dist(DistArgs a) {
     using Sh = DistShape<M, SIDE, W>;
     constexpr int P = Sh::P, EW = Sh::EW, QF = Sh::QF, STRIDE = Sh::STRIDE, QW = kDistQueries;
@@ -112,13 +119,14 @@ __global__ __launch_bounds__(256) void k_kge_dist(DistArgs a) {
     const int n = a.n, h = a.h;
     const bool filter = a.rowptr != nullptr;
 
-    // lane j < QW keeps query qb + j: its ids, its filter row, its counters or its list's state
-    int fx = 0, rl = 0, tr = 0, f_lo = 0, f_hi = 0;
+    // lane j < QW keeps query qb + j: its ids, its filter row, its candidate range, its counters or its list's state
+    int fx = 0, rl = 0, tr = 0, f_lo = 0, f_hi = 0, c_lo = 0, c_hi = 0;
     bool ok = false;
     if (lane < QW && qb + lane < a.Q) {
         const int64_t ff = a.fixed[qb + lane], rr = a.et[qb + lane];
         const int64_t tt = TOPK ? 0 : a.truth[qb + lane];
         ok = (uint64_t)ff < (uint64_t)n && (uint64_t)rr < (uint64_t)a.R && (uint64_t)tt < (uint64_t)n;
+        if constexpr (RANGED) ok = ok && query_range(a.cand_range, (int)rr, n, c_lo, c_hi);
         if (ok) {
             fx = (int)ff; rl = (int)rr; tr = (int)tt;
             if (filter) {
@@ -129,6 +137,9 @@ __global__ __launch_bounds__(256) void k_kge_dist(DistArgs a) {
             atomicOr(a.err, 1);
         }
     }
+    const uint32_t c_w = ok ? (uint32_t)(c_hi - c_lo) : 0u;  // RANGED: candidate v of query j iff (uint32_t)(v - c_lo) < c_w; none for a bad query
+    int wlo = 0, whi = n;                                    // the candidates this workgroup scans (the stage is not written before the loop's first barrier)
+    if constexpr (RANGED) workgroup_range(reinterpret_cast<int*>(zs), wave, lane, ok ? c_lo : 0x7fffffff, ok ? c_hi : 0, wlo, whi);
 
     // the queries' operand planes
     for (int j = 0; j < QW; ++j) {
@@ -196,31 +207,40 @@ __global__ __launch_bounds__(256) void k_kge_dist(DistArgs a) {
         }
     };
 
+    // the stages that hold a candidate of [wlo, whi); RANGED: the first may lie inside a bitmap window, which is built from its start
     int window = 0;
-    for (int c0 = 0; c0 < n; c0 += kDistStage) {
-        if (filter && c0 % kChunk == 0) {
-            window = c0;
+    const int c_first = RANGED ? wlo & ~(kDistStage - 1) : 0;
+    for (int c0 = c_first; c0 < (RANGED ? whi : n); c0 += kDistStage) {
+        if (filter && (c0 % kChunk == 0 || (RANGED && c0 == c_first))) {
+            window = RANGED ? c0 - c0 % kChunk : c0;
             __syncthreads();                                 // (the previous window is no longer read)
             bitmap_clear(bits, QW * kChunkWords, lane);
             __syncthreads();
             for (int j = 0; j < QW; ++j)
-                bitmap_set(bits + j * kChunkWords, a.partners, __shfl(f_lo, j), __shfl(f_hi, j), c0, lane, 64);
+                bitmap_set(bits + j * kChunkWords, a.partners, __shfl(f_lo, j), __shfl(f_hi, j), window, lane, 64);
         }
         __syncthreads();                                     // the previous stage is consumed (and the bitmap is complete)
         for (int idx = threadIdx.x; idx < kDistStage * EW; idx += 256) {
             const int c = idx / EW, fi = idx - c * EW;
             const int p = fi / W, k = fi - p * W;
-            zs[c * STRIDE + fi] = (c0 + c < n && k < h) ? a.ent[(int64_t)(c0 + c) * a.ld_ent + p * h + k] : 0.f;
+            zs[c * STRIDE + fi] = ((!RANGED || c0 + c >= wlo) && c0 + c < (RANGED ? whi : n) && k < h) ? a.ent[(int64_t)(c0 + c) * a.ld_ent + p * h + k] : 0.f;
         }
         __syncthreads();
 #pragma unroll
         for (int fi = 0; fi < EW; ++fi) row[fi] = zs[lane * STRIDE + fi];
         const int v = c0 + lane;                             // this lane's candidate
-        const bool inr = v < n;
+        const bool inr = RANGED || v < n;
         for (int j = 0; j < QW; ++j) {
             const float s = scan_score<M, SIDE, W>(qs + j * QF, row, a.gamma);
             const bool known = filter && bitmap_test(bits + j * kChunkWords, v - window) != 0u;
-            const bool okj = __shfl((int)ok, j) != 0;         // (every shuffle with the whole wave: none inside a condition)
+            bool okj;                                         // (every shuffle with the whole wave: none inside a condition)
+            if constexpr (RANGED) {                           // a valid query that admits v
+                const int lo_j = __shfl(c_lo, j);
+                const uint32_t w_j = __shfl(c_w, j);
+                okj = (uint32_t)(v - lo_j) < w_j;
+            } else {
+                okj = __shfl((int)ok, j) != 0;
+            }
             if constexpr (!TOPK) {
                 const float sj = __shfl(st, j);
                 const int vj = __shfl(tr, j);
@@ -277,10 +297,11 @@ gn_status launch_dist_w(const DistArgs& a, hipStream_t st) {
                (size_t)kWaves * kDistQueries * kChunkWords * 4 + (TOPK ? (size_t)kWaves * kDistQueries * (k + kDistCap) * 8 : 0);
     };
     const size_t lds = lds_of(a.k);
+    auto kernel = a.cand_range ? &k_kge_dist<M, SIDE, TOPK, W, true> : &k_kge_dist<M, SIDE, TOPK, W, false>;
     if (lds > 64 * 1024)                                      // (the opt-in is made once per kernel: for the largest k)
-        GN_OK_OR_RETURN(gn::allow_large_lds(reinterpret_cast<const void*>(k_kge_dist<M, SIDE, TOPK, W>), (int)lds_of(kMaxK)));
+        GN_OK_OR_RETURN(gn::allow_large_lds(reinterpret_cast<const void*>(kernel), (int)lds_of(kMaxK)));
     const unsigned grid = (unsigned)gn::ceil_div(a.Q, (int64_t)kWaves * kDistQueries);
-    k_kge_dist<M, SIDE, TOPK, W><<<grid, 256, lds, st>>>(a);
+    kernel<<<grid, 256, lds, st>>>(a);
     GN_LAUNCH_CHECK();
     return GN_OK;
 }
@@ -348,7 +369,7 @@ struct Call {
     int model, side;
     const float* ent; int64_t ld_ent, n; const float* rel; int64_t ld_rel, R, h;
     const int64_t* fixed; const int64_t* truth; const int64_t* et; int64_t Q;
-    float gamma, divisor; const gn_known_pairs* known;
+    float gamma, divisor; const gn_known_pairs* known; const int64_t* cand_range;
     int32_t* greater; int32_t* ties; float* scores; int64_t* ids; int k;
     int32_t* err; void* ws; size_t ws_bytes; hipStream_t st;
 };
@@ -384,7 +405,7 @@ gn_status run(const Call& c) {
         GN_LAUNCH_CHECK();
         RankArgs a;
         int S = 0;
-        GN_OK_OR_RETURN(fill_args(a, c.ent, c.ld_ent, c.n, de, nullptr, de, c.R, c.fixed, c.et, c.Q, c.known, c.err, S));
+        GN_OK_OR_RETURN(fill_args(a, c.ent, c.ld_ent, c.n, de, nullptr, de, c.R, c.fixed, c.et, c.Q, c.known, c.cand_range, c.err, S));
         a.q = qa.q; a.ld_q = de;
         a.v = c.truth; a.greater = c.greater; a.ties = c.ties; a.scores = c.scores; a.ids = c.ids; a.k = c.k;
         return launch<TOPK, true>(a, S, c.st);
@@ -395,6 +416,7 @@ gn_status run(const Call& c) {
     a.rel = t.rel; a.rel_im = t.rel_im; a.ld_rel = t.ld_rel; a.R = (int)t.r;
     a.fixed = c.fixed; a.truth = c.truth; a.et = c.et; a.Q = c.Q;
     if (c.known) { a.rowptr = c.known->rowptr.p; a.partners = c.known->partners.p; }
+    a.cand_range = c.cand_range;
     a.gamma = c.gamma; a.greater = c.greater; a.ties = c.ties; a.scores = c.scores; a.ids = c.ids; a.k = c.k; a.err = c.err;
     return launch_dist_model<TOPK>(c.model, c.side, a, c.st);
 }
@@ -408,25 +430,41 @@ size_t gn_kge_rank_workspace_bytes(int model, int64_t r, int64_t h, int64_t q) {
     return trig_bytes(model, r, h) + query_bytes(model, h, q);
 }
 
+gn_status gn_kge_rank_ranged_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t n, const float* rel, int64_t ld_rel,
+                                 int64_t r, int64_t h, const int64_t* fixed, const int64_t* truth, const int64_t* et, int64_t q,
+                                 float gamma, float phase_divisor, const gn_known_pairs* known, int32_t* greater, int32_t* ties,
+                                 int32_t* err, void* workspace, size_t workspace_bytes, void* stream, const int64_t* cand_range) {
+    GN_REQUIRE(q <= 0 || (truth && greater && ties), "operand pointer is null");
+    const Call c = {model, side, ent, ld_ent, n, rel, ld_rel, r, h, fixed, truth, et, q, gamma, phase_divisor, known, cand_range,
+                    greater, ties, nullptr, nullptr, 0, err, workspace, workspace_bytes, gn::as_stream(stream)};
+    return run<false>(c);
+}
+
 gn_status gn_kge_rank_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t n, const float* rel, int64_t ld_rel,
                           int64_t r, int64_t h, const int64_t* fixed, const int64_t* truth, const int64_t* et, int64_t q,
                           float gamma, float phase_divisor, const gn_known_pairs* known, int32_t* greater, int32_t* ties,
                           int32_t* err, void* workspace, size_t workspace_bytes, void* stream) {
-    GN_REQUIRE(q <= 0 || (truth && greater && ties), "operand pointer is null");
-    const Call c = {model, side, ent, ld_ent, n, rel, ld_rel, r, h, fixed, truth, et, q, gamma, phase_divisor, known,
-                    greater, ties, nullptr, nullptr, 0, err, workspace, workspace_bytes, gn::as_stream(stream)};
-    return run<false>(c);
+    return gn_kge_rank_ranged_f32(model, side, ent, ld_ent, n, rel, ld_rel, r, h, fixed, truth, et, q, gamma, phase_divisor, known,
+                                  greater, ties, err, workspace, workspace_bytes, stream, nullptr);
+}
+
+gn_status gn_kge_topk_ranged_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t n, const float* rel, int64_t ld_rel,
+                                 int64_t r, int64_t h, const int64_t* fixed, const int64_t* et, int64_t q, int64_t k, float gamma,
+                                 float phase_divisor, const gn_known_pairs* known, float* scores, int64_t* ids, int32_t* err,
+                                 void* workspace, size_t workspace_bytes, void* stream, const int64_t* cand_range) {
+    GN_REQUIRE(k >= 1 && k <= kMaxK, "k must be in [1, %d], got %lld", kMaxK, (long long)k);
+    GN_REQUIRE(q <= 0 || (scores && ids), "operand pointer is null");
+    const Call c = {model, side, ent, ld_ent, n, rel, ld_rel, r, h, fixed, nullptr, et, q, gamma, phase_divisor, known, cand_range,
+                    nullptr, nullptr, scores, ids, (int)k, err, workspace, workspace_bytes, gn::as_stream(stream)};
+    return run<true>(c);
 }
 
 gn_status gn_kge_topk_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t n, const float* rel, int64_t ld_rel,
                           int64_t r, int64_t h, const int64_t* fixed, const int64_t* et, int64_t q, int64_t k, float gamma,
                           float phase_divisor, const gn_known_pairs* known, float* scores, int64_t* ids, int32_t* err,
                           void* workspace, size_t workspace_bytes, void* stream) {
-    GN_REQUIRE(k >= 1 && k <= kMaxK, "k must be in [1, %d], got %lld", kMaxK, (long long)k);
-    GN_REQUIRE(q <= 0 || (scores && ids), "operand pointer is null");
-    const Call c = {model, side, ent, ld_ent, n, rel, ld_rel, r, h, fixed, nullptr, et, q, gamma, phase_divisor, known,
-                    nullptr, nullptr, scores, ids, (int)k, err, workspace, workspace_bytes, gn::as_stream(stream)};
-    return run<true>(c);
+    return gn_kge_topk_ranged_f32(model, side, ent, ld_ent, n, rel, ld_rel, r, h, fixed, et, q, k, gamma, phase_divisor, known,
+                                  scores, ids, err, workspace, workspace_bytes, stream, nullptr);
 }
 
 }  // extern "C"

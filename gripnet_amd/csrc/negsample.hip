@@ -321,11 +321,14 @@ __global__ void k_advance_step(uint64_t* step) { *step += 1; }
 // The [B, K] candidate block of a KGE mini-batch: element (b, k) is an entity drawn uniformly (with replacement) from those
 // that are not partners of the known-pairs row (edge_type[b], fixed[b]); rowptr == nullptr: no filter, attempt 0 is taken.
 // The typed sampler's rejection form on its stream (the draw is documented in include/gripnet_hip.h: the tests rebuild it):
-//   base = mix64(seed ^ (b * K + k) * 0xD6E8FEB86659FD93),  attempt a: h = mix64(base + a), c = (low32(h) * n) >> 32.
-// A positive whose fixed entity or relation lies outside its table gets a row of -1 (bit 0 of *err) and reads no rowptr.
+//   base = mix64(seed ^ (b * K + k) * 0xD6E8FEB86659FD93),  attempt a: h = mix64(base + a), c = lo + ((low32(h) * m) >> 32)
+// with (lo, hi) the candidate range of the positive's relation (cand_range's row; nullptr: (0, n), the documented draw of
+// the unranged entry point) and m = hi - lo.  A positive whose fixed entity or relation lies outside its table, or whose
+// range is no sub-range of [0, n], gets a row of -1 (bit 0 of *err) and reads no rowptr; an empty range a row of -1 and bit 1.
 __global__ __launch_bounds__(256) void k_kge_candidates(const int64_t* __restrict__ fixed, const int64_t* __restrict__ et, int64_t B, int64_t K,
                                                         uint32_t n, int64_t R, const int32_t* __restrict__ rowptr,
-                                                        const int32_t* __restrict__ partners, uint64_t seed, const uint64_t* __restrict__ seed_step,
+                                                        const int32_t* __restrict__ partners, const int64_t* __restrict__ cand_range,
+                                                        uint64_t seed, const uint64_t* __restrict__ seed_step,
                                                         int64_t* __restrict__ cand, int64_t ld, int32_t* __restrict__ err) {
     if (seed_step) seed += *seed_step;                       // read, not advanced: the caller's step += 1 is an op of its own
     const int64_t total = B * K;
@@ -337,13 +340,23 @@ __global__ __launch_bounds__(256) void k_kge_candidates(const int64_t* __restric
             if (k == 0 && err) atomicOr(err, 1);
             continue;
         }
+        uint32_t first = 0, m = n;                            // the candidate range [first, first + m)
+        if (cand_range) {
+            const int64_t rlo = cand_range[2 * r], rhi = cand_range[2 * r + 1];
+            if (rlo < 0 || rlo > rhi || rhi > (int64_t)n || rlo == rhi) {
+                cand[b * ld + k] = -1;
+                if (k == 0 && err) atomicOr(err, rlo == rhi && rlo >= 0 && rhi <= (int64_t)n ? 2 : 1);
+                continue;
+            }
+            first = (uint32_t)rlo; m = (uint32_t)(rhi - rlo);
+        }
         int lo0 = 0, hi0 = 0;
         if (rowptr) { lo0 = rowptr[r * n + f]; hi0 = rowptr[r * n + f + 1]; }
         const uint64_t base = mix64(seed ^ (uint64_t)i * 0xD6E8FEB86659FD93ull);
         uint32_t c = 0;
         bool found = false;
         for (int a = 0; a < kMaxAttempts && !found; ++a) {
-            c = __umulhi((uint32_t)mix64(base + (uint64_t)a), n);
+            c = first + __umulhi((uint32_t)mix64(base + (uint64_t)a), m);
             int lo = lo0, hi = hi0;                           // is `c` a partner of this row?
             while (lo < hi) {
                 const int mid = (lo + hi) >> 1;
@@ -351,7 +364,7 @@ __global__ __launch_bounds__(256) void k_kge_candidates(const int64_t* __restric
             }
             found = !(lo < hi0 && partners[lo] == (int32_t)c);
         }
-        if (!found && err) atomicOr(err, 2);                  // the row's partners are (nearly) all n entities
+        if (!found && err) atomicOr(err, 2);                  // the row's partners are (nearly) all entities of the range
         cand[b * ld + k] = (int64_t)c;
     }
 }
@@ -537,9 +550,9 @@ gn_status gn_known_pairs_create(const int64_t* u, const int64_t* v, const int64_
 
 void gn_known_pairs_destroy(gn_known_pairs* k) { delete k; }
 
-gn_status gn_kge_candidates_sample(const int64_t* fixed, const int64_t* edge_type, int64_t B, int64_t K, int64_t num_entities,
-                                   int64_t num_relations, const gn_known_pairs* known, uint64_t seed, const uint64_t* step,
-                                   int64_t* cand, int64_t ld_cand, int32_t* error_flag, void* stream) {
+gn_status gn_kge_candidates_sample_ranged(const int64_t* fixed, const int64_t* edge_type, int64_t B, int64_t K, int64_t num_entities,
+                                          int64_t num_relations, const gn_known_pairs* known, uint64_t seed, const uint64_t* step,
+                                          int64_t* cand, int64_t ld_cand, int32_t* error_flag, void* stream, const int64_t* cand_range) {
     GN_REQUIRE(B >= 0 && K >= 0 && ld_cand >= K, "bad candidate block (B=%lld, K=%lld, ld=%lld)", (long long)B, (long long)K, (long long)ld_cand);
     GN_REQUIRE(num_entities >= 1 && num_entities < (1ll << 31) && num_relations >= 1, "bad table size (n=%lld, R=%lld): 1 <= n < 2^31, R >= 1",
                (long long)num_entities, (long long)num_relations);
@@ -552,9 +565,16 @@ gn_status gn_kge_candidates_sample(const int64_t* fixed, const int64_t* edge_typ
     GN_REQUIRE(B <= (1ll << 62) / K, "B * K overflows");
     k_kge_candidates<<<gn::stream_grid(B * K, 256), 256, 0, gn::as_stream(stream)>>>(
         fixed, edge_type, B, K, (uint32_t)num_entities, num_relations, known ? known->rowptr.p : nullptr, known ? known->partners.p : nullptr,
-        seed, step, cand, ld_cand, error_flag);
+        cand_range, seed, step, cand, ld_cand, error_flag);
     GN_LAUNCH_CHECK();
     return GN_OK;
+}
+
+gn_status gn_kge_candidates_sample(const int64_t* fixed, const int64_t* edge_type, int64_t B, int64_t K, int64_t num_entities,
+                                   int64_t num_relations, const gn_known_pairs* known, uint64_t seed, const uint64_t* step,
+                                   int64_t* cand, int64_t ld_cand, int32_t* error_flag, void* stream) {
+    return gn_kge_candidates_sample_ranged(fixed, edge_type, B, K, num_entities, num_relations, known, seed, step, cand, ld_cand,
+                                           error_flag, stream, nullptr);
 }
 
 }  // extern "C"

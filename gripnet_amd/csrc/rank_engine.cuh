@@ -24,6 +24,7 @@ struct RankArgs {
     const float* q; int64_t ld_q;                        // PREPARED: the A rows [Q, f] as they stand (d unused)
     const int64_t* u; const int64_t* v; const int64_t* et; int64_t Q;
     const int32_t* rowptr; const int32_t* partners;      // null: no filter
+    const int64_t* cand_range;                            // [R][2] candidate range (lo, hi) per relation; null: (0, n)
     int32_t* greater; int32_t* ties;                      // rank
     float* scores; int64_t* ids; int k;                   // top-k
     int32_t* err;
@@ -57,6 +58,32 @@ __device__ __forceinline__ void bitmap_set(uint32_t* row_bits, const int32_t* __
 }
 
 __device__ __forceinline__ uint32_t bitmap_test(const uint32_t* row_bits, int w) { return (row_bits[w >> 5] >> (w & 31)) & 1u; }
+
+// The candidate range of a query of relation r: cand_range's row (lo, hi), or (0, n) without a table.  False for a row
+// that is no sub-range of [0, n] (the caller treats the query as one with an id out of range); then lo = hi = 0.
+__device__ __forceinline__ bool query_range(const int64_t* __restrict__ cand_range, int r, int n, int& lo, int& hi) {
+    lo = 0; hi = n;
+    if (cand_range == nullptr) return true;
+    const int64_t l = cand_range[2 * (int64_t)r], h = cand_range[2 * (int64_t)r + 1];
+    const bool good = l >= 0 && l <= h && h <= (int64_t)n;
+    lo = good ? (int)l : 0;
+    hi = good ? (int)h : 0;
+    return good;
+}
+
+// The union [wlo, whi) of the candidate ranges of a workgroup's valid queries (a lane without one passes lo = INT_MAX,
+// hi = 0), agreed on by its four waves through `slots` (LDS, 2 kWaves ints) behind one barrier: every wave runs the same
+// number of stages, the scan loop holds __syncthreads.  `slots` may be reused once another barrier has passed.  Without a
+// valid query wlo > whi: no stage runs.
+__device__ __forceinline__ void workgroup_range(int* slots, int wave, int lane, int lo, int hi, int& wlo, int& whi) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { lo = min(lo, __shfl_xor(lo, off)); hi = max(hi, __shfl_xor(hi, off)); }
+    if (lane == 0) { slots[2 * wave] = lo; slots[2 * wave + 1] = hi; }
+    __syncthreads();
+    wlo = slots[0]; whi = slots[1];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) { wlo = min(wlo, slots[2 * w]); whi = max(whi, slots[2 * w + 1]); }
+}
 
 // Top-k: merge row q's list (cs/ci[0, len)) and buffer ([k, k + cnt)) into the list, run by the row's 16 lanes (lanes
 // 16 kq + c16).  Every candidate's rank is the number of candidates better than it (ranks are unique: the order is total),
@@ -104,8 +131,10 @@ __device__ __forceinline__ void merge_row(float* cs, int* ci, int k, int kq, int
 }
 
 // The scan of one workgroup.  PREPARED: the A rows are read from a.q as they stand (k_query_rank); otherwise they are
-// z[u] * D[r], formed on load (k_dm_rank: the decoder).
-template <int S, bool TOPK, bool PREPARED>
+// z[u] * D[r], formed on load (k_dm_rank: the decoder).  RANGED: a.cand_range gives every query a candidate range (the
+// _ranged kernels); without it the range test is the parent `v < n` and the scan runs over [0, n) - a template parameter
+// because the per-row test and the two range registers per row cost the unranged call 2 - 7 %, measured.
+template <int S, bool TOPK, bool PREPARED, bool RANGED>
 __device__ __forceinline__ void rank_scan(const RankArgs& a) {
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr int KP = 4 * S;                               // padded features
@@ -122,15 +151,18 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
 
     // this lane's A row: query qb + col
     const int64_t qa = qb + col;
-    int ua = 0, ra = 0, va = 0;
+    int ua = 0, ra = 0, va = 0, loa = 0, hia = 0;             // (loa, hia): the query's candidate range
     bool oka = false;
     if (qa < a.Q) {
         const int64_t uu = a.u[qa], rr = a.et[qa];
         const int64_t vv = TOPK ? 0 : a.v[qa];
         oka = (uint64_t)uu < (uint64_t)n && (uint64_t)rr < (uint64_t)a.R && (uint64_t)vv < (uint64_t)n;
+        if constexpr (RANGED) oka = oka && query_range(a.cand_range, (int)rr, n, loa, hia);
         if (oka) { ua = (int)uu; ra = (int)rr; va = (int)vv; }
         else if (kq == 0 && a.err) atomicOr(a.err, 1);
     }
+    int wlo = 0, whi = n;                                    // the columns this workgroup scans
+    if constexpr (RANGED) workgroup_range(reinterpret_cast<int*>(zs), wave, lane, oka ? loa : 0x7fffffff, oka ? hia : 0, wlo, whi);
     float av[S];
     {
         const float* zu = PREPARED ? a.q + qa * a.ld_q : a.z + (int64_t)ua * a.ld_z;
@@ -144,12 +176,22 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
     }
     // the output rows of this lane: 4 kq + j
     bool okr[4];
-    int vt[4];
+    int vt[4], lor[4] = {0, 0, 0, 0};
+    uint32_t wr[4] = {0u, 0u, 0u, 0u};                       // RANGED: candidate v of row j iff (uint32_t)(v - lor[j]) < wr[j]; none for a bad query
+    const int wa = oka ? hia - loa : 0;                      // (every shuffle with the whole wave: none inside a condition)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         okr[j] = __shfl((int)oka, 4 * kq + j) != 0;
         vt[j] = __shfl(va, 4 * kq + j);
+        if constexpr (RANGED) {
+            lor[j] = __shfl(loa, 4 * kq + j);
+            wr[j] = (uint32_t)__shfl(wa, 4 * kq + j);
+        }
     }
+    auto admitted = [&](int v, int j) {
+        if constexpr (RANGED) return (uint32_t)(v - lor[j]) < wr[j];
+        else return v < n;
+    };
 
     float st[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (!TOPK) {
@@ -173,29 +215,31 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
     for (int j = 0; j < 4; ++j) { ts[j] = -__builtin_inff(); tv[j] = -1; }
 
     const bool filter = a.rowptr != nullptr;
-    int window = 0;
-    for (int c0 = 0; c0 < n; c0 += kStage) {
-        if (filter && c0 % kChunk == 0) {
-            // this wave's bitmap of columns [c0, c0 + kChunk): the known partners of its 16 rows
-            window = c0;
+    // the stages that hold a column of [wlo, whi); RANGED: the first may lie inside a bitmap window, which is built from its start
+    int window = RANGED ? -kChunk : 0;
+    for (int c0 = RANGED ? wlo & ~(kStage - 1) : 0; c0 < whi; c0 += kStage) {
+        if (filter && (RANGED ? c0 - window >= kChunk : c0 % kChunk == 0)) {
+            // this wave's bitmap of columns [window, window + kChunk): the known partners of its 16 rows
+            window = c0 - c0 % kChunk;
             __syncthreads();                                 // (the previous window is no longer read)
             bitmap_clear(bits, kRows * kChunkWords, lane);
             __syncthreads();
             if (oka) {
                 const int64_t row = (int64_t)ra * n + ua;
                 const int lo = a.rowptr[row], hi = a.rowptr[row + 1];
-                bitmap_set(bits + col * kChunkWords, a.partners, lo, hi, c0, kq, 4);
+                bitmap_set(bits + col * kChunkWords, a.partners, lo, hi, window, kq, 4);
             }
         }
         __syncthreads();                                     // the previous stage is consumed (and the bitmap is complete)
         for (int idx = threadIdx.x; idx < kStage * KP; idx += 256) {
             const int c = idx / KP, fi = idx - c * KP;
-            zs[c * STRIDE + fi] = (c0 + c < n && fi < a.f) ? a.z[(int64_t)(c0 + c) * a.ld_z + fi] : 0.f;
+            zs[c * STRIDE + fi] = ((!RANGED || c0 + c >= wlo) && c0 + c < whi && fi < a.f) ? a.z[(int64_t)(c0 + c) * a.ld_z + fi] : 0.f;
         }
         __syncthreads();
 #pragma unroll
         for (int t = 0; t < kStage / 16; t += 2) {
-            if (c0 + 16 * t >= n) break;
+            if (c0 + 16 * t >= whi) break;
+            if (RANGED && c0 + 16 * (t + 2) <= wlo) continue; // (both tiles in front of every range)
             f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
             const float* b0 = zs + (16 * t + col) * STRIDE + kq * S;
             const float* b1 = b0 + 16 * STRIDE;
@@ -224,7 +268,7 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
                 if constexpr (!TOPK) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const bool cand = v < n && v != vt[j] && !known[j];
+                        const bool cand = admitted(v, j) && v != vt[j] && !known[j];
                         gt[j] += (cand && acc[h][j] > st[j]) ? 1 : 0;
                         tie[j] += (cand && acc[h][j] == st[j]) ? 1 : 0;
                     }
@@ -233,7 +277,7 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const float s = acc[h][j];
-                        const bool pass = v < n && !known[j] && better(s, v, ts[j], tv[j]);
+                        const bool pass = admitted(v, j) && !known[j] && better(s, v, ts[j], tv[j]);
                         const uint64_t m = __ballot(pass);
                         const uint32_t g = (uint32_t)(m >> (16 * kq)) & 0xFFFFu;
                         if (pass) {
@@ -299,14 +343,22 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
 }
 
 template <int S, bool TOPK>
-__global__ __launch_bounds__(256) void k_dm_rank(RankArgs a) { rank_scan<S, TOPK, false>(a); }
+__global__ __launch_bounds__(256) void k_dm_rank(RankArgs a) { rank_scan<S, TOPK, false, false>(a); }
 
 template <int S, bool TOPK>
-__global__ __launch_bounds__(256) void k_query_rank(RankArgs a) { rank_scan<S, TOPK, true>(a); }
+__global__ __launch_bounds__(256) void k_query_rank(RankArgs a) { rank_scan<S, TOPK, true, false>(a); }
+
+template <int S, bool TOPK>
+__global__ __launch_bounds__(256) void k_dm_rank_ranged(RankArgs a) { rank_scan<S, TOPK, false, true>(a); }
+
+template <int S, bool TOPK>
+__global__ __launch_bounds__(256) void k_query_rank_ranged(RankArgs a) { rank_scan<S, TOPK, true, true>(a); }
 
 template <int S, bool TOPK, bool PREPARED>
 gn_status launch_s(const RankArgs& a, size_t lds, size_t lds_max, hipStream_t st) {
-    auto kernel = [] { if constexpr (PREPARED) return &k_query_rank<S, TOPK>; else return &k_dm_rank<S, TOPK>; }();
+    auto plain = [] { if constexpr (PREPARED) return &k_query_rank<S, TOPK>; else return &k_dm_rank<S, TOPK>; }();
+    auto ranged = [] { if constexpr (PREPARED) return &k_query_rank_ranged<S, TOPK>; else return &k_dm_rank_ranged<S, TOPK>; }();
+    auto kernel = a.cand_range ? ranged : plain;
     if (lds > 64 * 1024) {                                   // (the opt-in is made once per kernel: for the largest k)
         const gn_status ls = gn::allow_large_lds(reinterpret_cast<const void*>(kernel), (int)lds_max);
         if (ls != GN_OK) return ls;
@@ -332,7 +384,8 @@ gn_status launch(const RankArgs& a, int S, hipStream_t st) {
 }
 
 gn_status fill_args(RankArgs& a, const float* z, int64_t ld_z, int64_t n, int64_t f, const float* d, int64_t ld_d, int64_t R,
-                    const int64_t* u, const int64_t* et, int64_t Q, const gn_known_pairs* known, int32_t* err, int& S) {
+                    const int64_t* u, const int64_t* et, int64_t Q, const gn_known_pairs* known, const int64_t* cand_range,
+                    int32_t* err, int& S) {
     GN_REQUIRE(n >= 0 && f >= 1 && R >= 0 && Q >= 0, "bad size (n=%lld, features=%lld, R=%lld, queries=%lld)",
                (long long)n, (long long)f, (long long)R, (long long)Q);
     GN_REQUIRE(n < (1ll << 31) && R < (1ll << 31) && Q < (1ll << 40), "table too large");
@@ -343,7 +396,7 @@ gn_status fill_args(RankArgs& a, const float* z, int64_t ld_z, int64_t n, int64_
                           (long long)known->num_nodes, (long long)known->num_relations, (long long)n, (long long)R);
     a = RankArgs{};
     a.z = z; a.ld_z = ld_z; a.n = (int)n; a.f = (int)f; a.d = d; a.ld_d = ld_d; a.R = (int)R;
-    a.u = u; a.et = et; a.Q = Q; a.err = err;
+    a.u = u; a.et = et; a.Q = Q; a.err = err; a.cand_range = cand_range;
     if (known) { a.rowptr = known->rowptr.p; a.partners = known->partners.p; }
     S = (int)((f + 15) / 16) * 4;
     return GN_OK;

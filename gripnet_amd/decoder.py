@@ -175,7 +175,7 @@ class multiRelaInnerProductDecoder(Module):
             raise ValueError("expected {} features, got shape {}".format(self.in_dim, tuple(z.shape)))
         return _hip.f32_rows(z.detach()), self.weight.detach()
 
-    def rank(self, z, edge_index, edge_type, known=None):
+    def rank(self, z, edge_index, edge_type, known=None, candidates=None):
         """Filtered ranking of the pairs (u, v, r) = (edge_index[0], edge_index[1], edge_type) against every candidate
         partner: ``(greater, ties)``, int32 [E] each, the candidates v' != v whose (r, u, v') is not in `known` (a
         KnownPairs, None: no filter) with logit s(u, v', r) > s(u, v, r) and == s(u, v, r).  Logits, not sigmoids (fp32
@@ -184,21 +184,29 @@ class multiRelaInnerProductDecoder(Module):
         flipped list (``edge_index.flip(0)``) - with the bidirectional pose lists, both sides are already in the list.
         No autograd, no host synchronisation: an id out of range gives -1 / -1 and the IndexError at the next check
         (``utils.ranking_metrics`` / ``_hip.raise_if_index_errors``).  ``utils.ranking_metrics`` turns the counts into
-        MRR and Hits@k."""
+        MRR and Hits@k.  `candidates`: an int64 [num_et, 2] tensor on the device, row r = (lo, hi): a pair of relation r
+        is ranked against the partners lo <= v' < hi only, on top of the rules above (``utils.candidate_ranges``; when
+        `z` holds the nodes of every type, a relation's valid partners are one type's id range).  The true partner may
+        lie outside; an empty range gives 0 / 0; a range outside [0, n] or with lo > hi is found on the device: -1 / -1
+        and the IndexError.  The counts are the unranged call's over the range, bit for bit.  Wrong shape, dtype or
+        device: ValueError."""
+        candidates = _hip.candidate_table(candidates, self.weight.shape[0], self.weight.device)
         z, w = self._eval_operands(z, edge_index, edge_type)
         with torch.no_grad():
-            return _hip.distmult_rank(z, edge_index, edge_type, w, known)
+            return _hip.distmult_rank(z, edge_index, edge_type, w, known, candidates)
 
-    def top_k(self, z, nodes, edge_type, k, known=None):
+    def top_k(self, z, nodes, edge_type, k, known=None, candidates=None):
         """The `k` (1..64) best partners v of every query (u, r) = (nodes[q], edge_type[q]) that are not in `known`:
         ``(scores, partners)``, fp32 logits [Q, k] and int64 ids [Q, k], by logit descending then id ascending, padded
         with -inf / -1 when fewer than k candidates remain.  No autograd, no host synchronisation (ids out of range:
-        NaN / -1 and the IndexError at the next check)."""
+        NaN / -1 and the IndexError at the next check).  `candidates` as for ``rank``: only the partners in the
+        relation's range enter the list (empty range: a row of padding; invalid: NaN / -1 and the IndexError)."""
+        candidates = _hip.candidate_table(candidates, self.weight.shape[0], self.weight.device)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
             raise ValueError("k must be an integer in [1, 64], got {!r}".format(k))
         z, w = self._eval_operands(z, nodes, edge_type)
         with torch.no_grad():
-            return _hip.distmult_topk(z, nodes, edge_type, w, int(k), known)
+            return _hip.distmult_topk(z, nodes, edge_type, w, int(k), known, candidates)
 
     def reset_parameters(self):
         self.weight.data.normal_(std=1 / np.sqrt(self.in_dim))                   # decoder.py:25-26

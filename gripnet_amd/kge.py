@@ -68,7 +68,7 @@ def negative_sampling_loss(positive_score, negative_score, adversarial_temperatu
     return KgeNegativeSamplingLossFn.apply(positive_score, negative_score, subsampling_weight, temperature)
 
 
-def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0, step=None, out=None):
+def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0, step=None, out=None, candidates=None):
     """int64 [B, K]: K candidate entities per positive (positive[0, b], et[b], positive[1, b]) for the batch modes of
     ``KGEModel.forward`` / ``.score``, drawn on the device (gn_kge_candidates_sample) uniformly, with replacement, from the
     entities that are not known partners.  `side` and `known` as for ``rank`` / ``top_k``: ``side="tail"`` fixes the head
@@ -81,7 +81,12 @@ def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0,
     captured mini-batch draws anew at every replay.  `out`: an int64 [B, K] tensor to fill (unit inner stride; a column
     view of a wider matrix is written in place).  No host synchronisation: a positive with an id outside its table gets a
     row of -1 (NaN scores) and a row that knows every entity keeps its last draw; both raise at the next synchronising check
-    (``_hip.raise_if_index_errors``)."""
+    (``_hip.raise_if_index_errors``).  `candidates`: an int64 [R, 2] tensor on the device, row r = (lo, hi) the entities a
+    positive of relation r draws from - the valid tails for ``side="tail"``, the valid heads for ``side="head"``
+    (``utils.candidate_ranges``; R is `known`'s relation count, or with ``known=None`` the table's own, and a relation id
+    beyond it then gets a row of -1).  The draw becomes ``lo + ((low32(h) * (hi - lo)) >> 32)``; with (0, nentity) it is
+    the unranged draw element for element.  An empty range gives a row of -1 and the "no entity to draw" RuntimeError, a
+    range outside [0, nentity] or with lo > hi a row of -1 and the IndexError, both at the next check."""
     if side not in _hip.KGE_SIDES:
         raise ValueError("side must be 'tail' or 'head', got {!r}".format(side))
     if positive.dim() != 2 or positive.shape[0] != 2:
@@ -105,11 +110,12 @@ def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0,
     if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (b, K) or out.device != positive.device or
                             (K > 1 and out.stride(1) != 1) or (b > 1 and out.stride(0) < K)):
         raise ValueError("`out` must be an int64 [{}, {}] tensor with a unit inner stride on {}".format(b, K, positive.device))
+    candidates = _hip.candidate_table(candidates, None if known is None else known.num_et, positive.device)
     _hip.require_gpu(positive, et)
     if out is None:
         out = torch.empty((b, K), dtype=torch.int64, device=positive.device)
     fixed = positive[0] if side == "tail" else positive[1]
-    return _hip.kge_candidates_sample(fixed, et, K, nentity, known, seed, step, out)
+    return _hip.kge_candidates_sample(fixed, et, K, nentity, known, seed, step, out, candidates)
 
 
 class KGEModel(nn.Module):
@@ -224,7 +230,7 @@ class KGEModel(nn.Module):
         _hip.require_gpu(ent, rel, *index)
         return _hip.f32_rows(ent.detach()), _hip.f32_rows(rel.detach())
 
-    def rank(self, sample, et, side="tail", known=None):
+    def rank(self, sample, et, side="tail", known=None, candidates=None):
         """Filtered ranking of the triples (h, r, t) = (sample[0], et, sample[1]) against every candidate entity:
         ``(greater, ties)``, int32 [E] each.  ``side="tail"``: the candidates t' != t whose (r, h, t') is not in `known`
         (a KnownPairs, None: no filter) with score s(h, r, t') > s(h, r, t) and == s(h, r, t).  ``side="head"``: the
@@ -235,22 +241,31 @@ class KGEModel(nn.Module):
         autograd, no host synchronisation: an id out of range gives -1 / -1 and the IndexError at the next check
         (``utils.ranking_metrics`` / ``_hip.raise_if_index_errors``); ``utils.ranking_metrics`` turns the counts into MRR
         and Hits@k.  Entity rows of at most 128 floats (hidden_dim <= 128 for TransE and DistMult, <= 64 for ComplEx and
-        RotatE): ValueError beyond, there is no torch fallback."""
+        RotatE): ValueError beyond, there is no torch fallback.  `candidates`: an int64 [nrelation, 2] tensor on the
+        device, row r = (lo, hi): a query of relation r is ranked against the candidates lo <= c < hi only (on top of the
+        rules above) - the valid tails for ``side="tail"``, the valid heads for ``side="head"``
+        (``utils.candidate_ranges``).  The true partner may lie outside its range; an empty range gives 0 / 0; a range
+        outside [0, nentity] or with lo > hi is found on the device and gives -1 / -1 and the IndexError.  The counts are
+        those of the unranged call over the range, bit for bit; queries sorted by relation scan only their range.
+        Wrong shape, dtype or device: ValueError."""
+        candidates = _hip.candidate_table(candidates, self.relation_embedding.shape[0], self.entity_embedding.device)
         ent, rel = self._eval_operands(sample, et)
         gamma, divisor = self._constants()
         with torch.no_grad():
-            return _hip.kge_rank(self.model_name, ent, rel, sample, et, gamma, divisor, side, known)
+            return _hip.kge_rank(self.model_name, ent, rel, sample, et, gamma, divisor, side, known, candidates)
 
-    def top_k(self, entities, et, k, side="tail", known=None):
+    def top_k(self, entities, et, k, side="tail", known=None, candidates=None):
         """The `k` (1..64) best partners of every query (entities[q], et[q]) that are not in `known`: the tails of
         (entities[q], r, .) for ``side="tail"``, the heads of (., r, entities[q]) for ``side="head"`` (`known` keyed as for
         ``rank``: built from the flipped lists for the head side).  ``(scores, ids)``: fp32 raw scores [Q, k] and int64
         ids [Q, k], by score descending then id ascending, padded with -inf / -1 when fewer than k candidates remain.  No
         autograd, no host synchronisation (ids out of range: NaN / -1 and the IndexError at the next check).  Width limit
-        as for ``rank``."""
+        as for ``rank``.  `candidates` as for ``rank``: only the entities of the relation's range enter the list (an empty
+        range: a row of padding; an invalid one: NaN / -1 and the IndexError)."""
+        candidates = _hip.candidate_table(candidates, self.relation_embedding.shape[0], self.entity_embedding.device)
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 64:
             raise ValueError("k must be an integer in [1, 64], got {!r}".format(k))
         ent, rel = self._eval_operands(entities, et)
         gamma, divisor = self._constants()
         with torch.no_grad():
-            return _hip.kge_topk(self.model_name, ent, rel, entities, et, int(k), gamma, divisor, side, known)
+            return _hip.kge_topk(self.model_name, ent, rel, entities, et, int(k), gamma, divisor, side, known, candidates)

@@ -278,6 +278,32 @@ def ranking_metrics(greater: torch.Tensor, ties: torch.Tensor, edge_type: torch.
     return out
 
 
+def candidate_ranges(num_relations: int, num_nodes: int, spans=(), device=None) -> torch.Tensor:
+    """The per-relation candidate table of ``rank`` / ``top_k`` (``KGEModel``, ``multiRelaInnerProductDecoder``) and
+    ``kge.sample_candidates``: int64 [num_relations, 2] on `device`, every row (0, num_nodes), then each
+    ``(first_relation, last_relation_exclusive, lo, hi)`` of `spans` overwrites its rows with (lo, hi), in order.  On a
+    homogenised heterogeneous graph a node type is a contiguous id range, so "the tails of the drug-drug relations are
+    drugs" is one span.  Checked on the host: ValueError for lo > hi, for lo or hi outside [0, num_nodes] and for
+    relations outside [0, num_relations] (the kernels check the table they are given on the device)."""
+    integer = (int, np.integer)
+    for value, what in ((num_relations, "num_relations"), (num_nodes, "num_nodes")):
+        if isinstance(value, bool) or not isinstance(value, integer) or int(value) < 0:
+            raise ValueError("{} must be a non-negative integer, got {!r}".format(what, value))
+    table = torch.zeros((int(num_relations), 2), dtype=torch.int64)
+    table[:, 1] = int(num_nodes)
+    for span in spans:
+        if len(span) != 4 or any(isinstance(x, bool) or not isinstance(x, integer) for x in span):
+            raise ValueError("a span is (first_relation, last_relation_exclusive, lo, hi) in integers, got {!r}".format(span))
+        first, last, lo, hi = (int(x) for x in span)
+        if not 0 <= first <= last <= num_relations:
+            raise ValueError("span {!r}: relations [{}, {}) outside [0, {}]".format(span, first, last, num_relations))
+        if not 0 <= lo <= hi <= num_nodes:
+            raise ValueError("span {!r}: candidates [{}, {}) are no range inside [0, {}]".format(span, lo, hi, num_nodes))
+        table[first:last, 0] = lo
+        table[first:last, 1] = hi
+    return table if device is None else table.to(device)
+
+
 def link_loss(pos_score: torch.Tensor, neg_score: torch.Tensor, eps: float = EPS) -> torch.Tensor:
     """``-log(pos + EPS).mean() - log(1 - neg + EPS).mean()``: the training loss of GripNet-pose.py:140-142 as one launch
     forward and one backward (gn_link_loss_*), differentiable.  The reference spells the expression out with torch ops

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 170 /* 0.1.64 */
+#define GN_VERSION 171 /* 0.1.65 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -842,6 +842,27 @@ GN_API gn_status gn_distmult_topk_f32(const float* z, int64_t ld_z, int64_t num_
                                int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* edge_type, int64_t num_queries,
                                int64_t k, const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids,
                                int32_t* error_flag, void* stream);
+/* Per-relation candidate ranges (type-constrained candidates: on a homogenised heterogeneous graph a relation's partners are
+ * one node type, a contiguous id range).  cand_range: int64 [num_relations, 2] in device memory, row r = (lo_r, hi_r); a
+ * candidate v' of a query of relation r is admitted iff lo_r <= v' < hi_r, on top of every rule above (not the true partner,
+ * not a known pair, v' < num_nodes).  The table is per side, as `known` is.  The true partner may lie outside its
+ * relation's range (it is never a candidate); greater / ties then count the admitted candidates.  An empty range
+ * (lo == hi) is valid: 0 / 0, or a row of -inf / -1.  A row with lo < 0, hi > num_nodes or lo > hi is read on the device
+ * (no host synchronisation) and makes its relation's queries queries with an id out of range: -1 / -1 or NaN / -1 and
+ * bit 0 of *error_flag.  A workgroup scans the stages that hold a column of its queries' ranges only, so queries sorted by
+ * relation are scanned against their own ranges; a score does not depend on where the scan starts, so the results are
+ * those of the unranged call restricted to the range, bit for bit.  cand_range == NULL: the unranged call itself (which is
+ * this call with NULL). */
+GN_API gn_status gn_distmult_rank_ranged_f32(const float* z, int64_t ld_z, int64_t num_nodes, int64_t num_features, const float* d,
+                               int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* v, const int64_t* edge_type,
+                               int64_t num_queries, const gn_known_pairs* known /* nullable */, int32_t* greater, int32_t* ties,
+                               int32_t* error_flag, void* stream,
+                               const int64_t* cand_range /* nullable, device, [num_relations, 2] */);
+GN_API gn_status gn_distmult_topk_ranged_f32(const float* z, int64_t ld_z, int64_t num_nodes, int64_t num_features, const float* d,
+                               int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* edge_type, int64_t num_queries,
+                               int64_t k, const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids,
+                               int32_t* error_flag, void* stream,
+                               const int64_t* cand_range /* nullable, device, [num_relations, 2] */);
 
 /* ---------------------------------------------------------------------------------------
  * Filtered ranking and top-k retrieval for the knowledge-graph-embedding scorers (GN_KGE_*; tables, gamma and
@@ -874,6 +895,22 @@ GN_API gn_status gn_kge_topk_f32(int model, int side, const float* ent, int64_t 
                           const int64_t* edge_type, int64_t num_queries, int64_t k, float gamma, float phase_divisor,
                           const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids, int32_t* error_flag,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* The same with per-relation candidate ranges: cand_range as for gn_distmult_rank_ranged_f32 (int64 [num_relations, 2] on
+ * the device, row r = (lo_r, hi_r); candidate c admitted iff lo_r <= c < hi_r on top of the rules above; the valid tails
+ * for GN_KGE_SIDE_TAIL, the valid heads for GN_KGE_SIDE_HEAD; empty range: 0 / 0 or padding; invalid row: its queries get
+ * -1 / -1 or NaN / -1 and bit 0; NULL: the unranged call). */
+GN_API gn_status gn_kge_rank_ranged_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                          int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                          const int64_t* truth, const int64_t* edge_type, int64_t num_queries, float gamma,
+                          float phase_divisor, const gn_known_pairs* known /* nullable */, int32_t* greater, int32_t* ties,
+                          int32_t* error_flag, void* workspace, size_t workspace_bytes, void* stream,
+                          const int64_t* cand_range /* nullable, device, [num_relations, 2] */);
+GN_API gn_status gn_kge_topk_ranged_f32(int model, int side, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                          int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                          const int64_t* edge_type, int64_t num_queries, int64_t k, float gamma, float phase_divisor,
+                          const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids, int32_t* error_flag,
+                          void* workspace, size_t workspace_bytes, void* stream,
+                          const int64_t* cand_range /* nullable, device, [num_relations, 2] */);
 
 /* The candidate block of a KGE mini-batch: cand[b * ld_cand + k] (int64, ld_cand >= K), K entities per positive
  * (fixed[b], edge_type[b]) drawn uniformly, with replacement, from the entities that are NOT partners of the row
@@ -898,6 +935,20 @@ GN_API gn_status gn_kge_candidates_sample(const int64_t* fixed, const int64_t* e
                                    const gn_known_pairs* known /* nullable */, uint64_t seed,
                                    const uint64_t* step /* nullable, device */, int64_t* cand, int64_t ld_cand,
                                    int32_t* error_flag, void* stream);
+/* The same draw from per-relation candidate ranges (cand_range as for gn_kge_rank_ranged_f32: int64 [num_relations, 2] on
+ * the device, the valid tails or heads of each relation; num_relations is then the table's row count, also without
+ * `known`).  THE RANGED DRAW IS PART OF THIS INTERFACE.  With (lo, hi) the row of edge_type[b] and m = hi - lo, base as above:
+ *   attempt a = 0, 1, ...:   h = mix64(base + a);   c = lo + ((low32(h) * m) >> 32)
+ *   cand[b, k] = the first c that is not a partner of the row
+ * With (0, num_entities) this is the draw above, element for element, and so is cand_range == NULL.  An empty range
+ * (lo == hi) writes -1 into the whole row and sets bit 1 of *error_flag (no entity to draw); a row with lo < 0,
+ * hi > num_entities or lo > hi is read on the device and treated as an id out of range: a row of -1 and bit 0. */
+GN_API gn_status gn_kge_candidates_sample_ranged(const int64_t* fixed, const int64_t* edge_type, int64_t num_positives,
+                                   int64_t num_candidates, int64_t num_entities, int64_t num_relations,
+                                   const gn_known_pairs* known /* nullable */, uint64_t seed,
+                                   const uint64_t* step /* nullable, device */, int64_t* cand, int64_t ld_cand,
+                                   int32_t* error_flag, void* stream,
+                                   const int64_t* cand_range /* nullable, device, [num_relations, 2] */);
 
 /* Independent small products in ONE launch.  Between gn_dense_batch_begin() and gn_dense_batch_end(stream) (per host thread,
  * not nested) the calls that carry GN_GEMM_JOIN_BATCH / GN_XTG_JOIN_BATCH - those of gn_gemm_f32 that take the deep-and-narrow kernel (a single product with at most 64 rows or 32 columns

@@ -10,6 +10,12 @@ The torch formulation: per chunk of queries, scores = (z[u] * D[r]) @ z.T, the k
 and scores) is asserted in the run.  Times: HIP events around `--reps` calls after `--warmup` calls.
 
     python tools/bench_ranking.py [--reps 20] [--warmup 3] [--chunk 16384]
+
+`--typed` measures per-relation candidate ranges instead, on the homogenised graph of the all-nodes baselines (z holds every
+drug and gene: 19,726 rows of 32 features, 964 relations): the three alternating calls, the parities and the options of
+`tools/bench_kge_ranking.py --typed`, for multiRelaInnerProductDecoder.rank / top_k.
+
+    python tools/bench_ranking.py --typed [--parent-lib PATH] [--runs 3] [--reps 9] [--markdown PATH]
 """
 import argparse
 import json
@@ -39,13 +45,65 @@ def timed(fn, reps, warmup):
     return a.elapsed_time(b) / reps, out
 
 
+def typed_mode(args):
+    import bench_kge_ranking as kb
+    from gripnet_amd.synth import make_rgcn_pose
+    dev = torch.device("cuda:0")
+    data = make_rgcn_pose("pose0-syn").to(dev)
+    n, R, f, n_drug = int(data.n_node), int(data.n_edge_type), args.typed_dim, int(data.n_drug)
+    sample, et, table = kb.typed_queries(data, args.queries, dev)
+    parent = kb.ParentLibrary(args.parent_lib)
+    torch.manual_seed(2024)
+    z = torch.randn(n, f, device=dev)
+    dec = multiRelaInnerProductDecoder(f, R).to(dev)
+    lists = [(data.train_idx, data.train_et)]
+    known = KnownPairs(lists, n, R)
+    rest = kb.rest_known(lists, sample[0], et, n, n_drug, R)
+
+    def in_parent(fn):
+        def call():
+            with parent.active():
+                return fn()
+        return call
+
+    ops = {"rank": lambda **kw: dec.rank(z, sample, et, **kw), "top-10": lambda **kw: dec.top_k(z, sample[0], et, 10, **kw)}
+    rows = []
+    for run in range(args.runs):
+        for op, fn in ops.items():
+            with torch.no_grad():
+                ms, got = kb.three_way({"a": in_parent(lambda: fn(known=known)), "b": lambda: fn(known=known),
+                                        "c": lambda: fn(known=known, candidates=table)}, args.reps, args.warmup)
+                assert kb.same_bits(got["a"], got["b"]), (op, "parent and this build differ")
+                assert kb.same_bits(got["c"], fn(known=rest)), (op, "ranged and full scan differ")
+            rows.append(dict(run=run + 1, model="decoder", side="tail", op=op, **ms))
+    _hip.raise_if_index_errors(dev)
+    out = {"workload": "pose0-syn homogenised decoder ranking, typed candidates (n {}, {} drugs, R {}, {} features, {} drug-drug "
+                       "queries sorted by relation)".format(n, n_drug, R, f, sample.shape[1]),
+           "a_is": "the parent commit's build, unranged" if args.parent_lib else "this build, unranged (no parent build given)",
+           "results": kb.summarise(rows), "reps": args.reps, "warmup": args.warmup, "runs": args.runs,
+           "device": torch.cuda.get_device_name(dev)}
+    print(json.dumps(out))
+    if args.markdown:
+        kb.write_typed_markdown(args.markdown, "Decoder ranking and top-10 with per-relation candidate ranges",
+                                "tools/bench_ranking.py --typed --runs {} --reps {} --warmup {} --queries {}".format(
+                                    args.runs, args.reps, args.warmup, args.queries), out, out["results"])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--typed", action="store_true", help="per-relation candidate ranges: parent / unranged / ranged")
+    ap.add_argument("--parent-lib", default=None, help="--typed: the parent commit's libgripnet_hip.so for call (a)")
+    ap.add_argument("--runs", type=int, default=3, help="--typed: repetitions of the whole measurement")
+    ap.add_argument("--queries", type=int, default=2000, help="--typed: drug-drug queries")
+    ap.add_argument("--typed-dim", type=int, default=32, help="--typed: features of z")
+    ap.add_argument("--markdown", default=None, help="--typed: also write the table here")
     ap.add_argument("--chunk", type=int, default=16384, help="queries per chunk of the torch formulation")
     ap.add_argument("--in-dim", type=int, default=80)
     args = ap.parse_args()
+    if args.typed:
+        return typed_mode(args)
     dev = torch.device("cuda:0")
     data = add_pose_test_split(make_pose("pose0-syn")).to(dev)
     n, R, f = int(data.n_d_node), int(data.n_dd_edge_type), args.in_dim
