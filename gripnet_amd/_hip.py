@@ -29,7 +29,7 @@ RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 171                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 172                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -1760,8 +1760,8 @@ def _known_handle(known, z, weight):
 
 
 def distmult_rank(z, edge_index, edge_type, weight, known=None, candidates=None):
-    """(greater, ties) int32 [E]: per pair (u, v, r) the non-known candidates v' != v scored above / equal to (u, v, r)
-    (gn_distmult_rank_ranged_f32).  `z` rows contiguous fp32.  `candidates`: int64 [R, 2] ranges per relation, or None."""
+    """(greater, ties) int32 [E]: per pair (u, v, r) the non-known candidates v' != v scored not below-or-equal / equal to (u, v, r)
+    (gn_distmult_rank_ranged_f32; a NaN on either side counts as greater).  `z` rows contiguous fp32.  `candidates`: int64 [R, 2] ranges per relation, or None."""
     candidates = candidate_table(candidates, weight.shape[0], z.device)
     ei, u, v, e = edge_rows(edge_index)
     et = i64_vec(edge_type)

@@ -2,8 +2,9 @@
 //
 // A query is (fixed entity, relation) and a side: on the tail side the fixed entity is the head and every entity is a
 // candidate tail, on the head side the fixed entity is the tail and every entity is a candidate head.  Per query the
-// raw score of kge.hip against each of the n candidates; rank counts the non-known candidates above and equal to the true
-// partner's score, top-k keeps the k <= 64 best (score descending, id ascending).  Nothing of a [Q, n] score matrix or a
+// raw score of kge.hip against each of the n candidates; rank counts the non-known candidates NOT below-or-equal and equal
+// to the true partner's score (a NaN on either side counts as greater: a non-finite score never flatters the model), top-k
+// keeps the k <= 64 best (score descending, id ascending; NaN and -inf never enter).  Nothing of a [Q, n] score matrix or a
 // [Q, n, D] difference block reaches memory.  The known-pair rows are keyed (relation, fixed entity): for the head side the
 // caller builds the gn_known_pairs from the flipped lists.
 //
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(256) void k_kge_dist(DistArgs a) {
                 const float sj = __shfl(st, j);
                 const int vj = __shfl(tr, j);
                 const bool cand = inr && okj && !known && v != vj;
-                const int g = __popcll(__ballot(cand && s > sj)), e = __popcll(__ballot(cand && s == sj));
+                const int g = __popcll(__ballot(cand && !(s <= sj))), e = __popcll(__ballot(cand && s == sj));   // (NaN on either side counts)
                 if (lane == j) { gt += g; tie += e; }
             } else {
                 const float tsj = __shfl(ts, j);

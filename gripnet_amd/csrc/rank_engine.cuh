@@ -269,7 +269,7 @@ __device__ __forceinline__ void rank_scan(const RankArgs& a) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const bool cand = admitted(v, j) && v != vt[j] && !known[j];
-                        gt[j] += (cand && acc[h][j] > st[j]) ? 1 : 0;
+                        gt[j] += (cand && !(acc[h][j] <= st[j])) ? 1 : 0;   // (NaN on either side counts: never flatters)
                         tie[j] += (cand && acc[h][j] == st[j]) ? 1 : 0;
                     }
                 } else {

@@ -178,7 +178,11 @@ class multiRelaInnerProductDecoder(Module):
     def rank(self, z, edge_index, edge_type, known=None, candidates=None):
         """Filtered ranking of the pairs (u, v, r) = (edge_index[0], edge_index[1], edge_type) against every candidate
         partner: ``(greater, ties)``, int32 [E] each, the candidates v' != v whose (r, u, v') is not in `known` (a
-        KnownPairs, None: no filter) with logit s(u, v', r) > s(u, v, r) and == s(u, v, r).  Logits, not sigmoids (fp32
+        KnownPairs, None: no filter) with NOT (s(u, v', r) <= s(u, v, r)) and with s(u, v', r) == s(u, v, r) - a
+        non-finite logit never flatters the model: a NaN true logit puts every admitted candidate into `greater` (the
+        true pair ranks last, ties = 0), a NaN candidate counts as greater than any true logit, -inf and +inf compare as
+        numbers (equal infinities tie, a -inf candidate is greater than nothing), the filter is applied before the
+        comparison, and non-finite logits set no bit of the error word.  Logits, not sigmoids (fp32
         sigmoid saturates to 1.0 above ~17 and would manufacture ties).  The true pair's logit is the scan's own value for
         column v.  Tail side; DistMult is symmetric, so the head-side ranks of a list are the tail-side ranks of the
         flipped list (``edge_index.flip(0)``) - with the bidirectional pose lists, both sides are already in the list.
@@ -198,7 +202,9 @@ class multiRelaInnerProductDecoder(Module):
     def top_k(self, z, nodes, edge_type, k, known=None, candidates=None):
         """The `k` (1..64) best partners v of every query (u, r) = (nodes[q], edge_type[q]) that are not in `known`:
         ``(scores, partners)``, fp32 logits [Q, k] and int64 ids [Q, k], by logit descending then id ascending, padded
-        with -inf / -1 when fewer than k candidates remain.  No autograd, no host synchronisation (ids out of range:
+        with -inf / -1 when fewer than k candidates remain.  A NaN or -inf logit never enters, +inf enters, equal logits
+        order by ascending id; a query whose whole candidate row is NaN (a NaN z[u]) gets a full row of padding, not the
+        NaN / -1 of an id out of range.  No autograd, no host synchronisation (ids out of range:
         NaN / -1 and the IndexError at the next check).  `candidates` as for ``rank``: only the partners in the
         relation's range enter the list (empty range: a row of padding; invalid: NaN / -1 and the IndexError)."""
         candidates = _hip.candidate_table(candidates, self.weight.shape[0], self.weight.device)

@@ -233,7 +233,12 @@ class KGEModel(nn.Module):
     def rank(self, sample, et, side="tail", known=None, candidates=None):
         """Filtered ranking of the triples (h, r, t) = (sample[0], et, sample[1]) against every candidate entity:
         ``(greater, ties)``, int32 [E] each.  ``side="tail"``: the candidates t' != t whose (r, h, t') is not in `known`
-        (a KnownPairs, None: no filter) with score s(h, r, t') > s(h, r, t) and == s(h, r, t).  ``side="head"``: the
+        (a KnownPairs, None: no filter) with NOT (s(h, r, t') <= s(h, r, t)) and with s(h, r, t') == s(h, r, t) - a
+        non-finite score never flatters the model: a NaN true score puts every admitted candidate into `greater` (the
+        true triple ranks last, ties = 0), a NaN candidate counts as greater than any true score, -inf and +inf compare
+        as numbers (equal infinities tie, a -inf candidate is greater than nothing), the filter is applied before the
+        comparison, and non-finite scores set no bit of the error word (``ranking_metrics`` returns numbers: a table that
+        went to NaN reports an MRR near 0, not 1).  ``side="head"``: the
         candidates h' != h of (., r, t), filtered by a KnownPairs whose rows are keyed (r, t) - one built from the FLIPPED
         lists, ``KnownPairs([(ei.flip(0), et), ...], nentity, nrelation)``; the filter given for the tail side does not
         serve the head side (TransE, ComplEx and RotatE are not symmetric; neither are their known pairs).  Raw scores
@@ -258,7 +263,11 @@ class KGEModel(nn.Module):
         """The `k` (1..64) best partners of every query (entities[q], et[q]) that are not in `known`: the tails of
         (entities[q], r, .) for ``side="tail"``, the heads of (., r, entities[q]) for ``side="head"`` (`known` keyed as for
         ``rank``: built from the flipped lists for the head side).  ``(scores, ids)``: fp32 raw scores [Q, k] and int64
-        ids [Q, k], by score descending then id ascending, padded with -inf / -1 when fewer than k candidates remain.  No
+        ids [Q, k], by score descending then id ascending, padded with -inf / -1 when fewer than k candidates remain.  A
+        NaN or -inf score never enters, +inf enters, equal scores order by ascending id; a query whose whole candidate
+        row is NaN (a NaN fixed entity) gets a full row of padding, not the NaN / -1 of an id out of range.  ComplEx on
+        the head side scores the relation and tail folded into one row first (the header says which kind of value an
+        infinite entry then gives).  No
         autograd, no host synchronisation (ids out of range: NaN / -1 and the IndexError at the next check).  Width limit
         as for ``rank``.  `candidates` as for ``rank``: only the entities of the relation's range enter the list (an empty
         range: a row of padding; an invalid one: NaN / -1 and the IndexError)."""

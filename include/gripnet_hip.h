@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 171 /* 0.1.65 */
+#define GN_VERSION 172 /* 0.1.66 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -826,18 +826,26 @@ GN_API gn_status gn_known_pairs_create(const int64_t* u, const int64_t* v, const
                                 int64_t num_nodes, int64_t num_relations, void* stream, gn_known_pairs** known);
 GN_API void gn_known_pairs_destroy(gn_known_pairs* known);
 /* Per query e = (u[e], v[e], edge_type[e]): greater[e] / ties[e] = the candidates v' != v[e] whose (r, u, v') is not a
- * known pair (known may be NULL: no filter) with s(v') > s(v[e]) / s(v') == s(v[e]).  The true score is the scan's own
- * value for column v[e] (same operands, same fp32 FMA order on the matrix cores).  No [Q, n] buffer, no float atomics,
+ * known pair (known may be NULL: no filter) with NOT (s(v') <= s(v[e])) / s(v') == s(v[e]).  The true score is the scan's
+ * own value for column v[e] (same operands, same fp32 FMA order on the matrix cores).  No [Q, n] buffer, no float atomics,
  * no host synchronisation.  A query with an id out of range gets -1 / -1 and sets bit 0 of *error_flag.  num_features
- * <= 128; `known` must have been built for the same num_nodes and num_relations. */
+ * <= 128; `known` must have been built for the same num_nodes and num_relations.
+ * NON-FINITE SCORES never flatter the model.  greater[e] counts the admitted candidates c with NOT (s(c) <= s(true)),
+ * ties[e] those with s(c) == s(true): a NaN true score puts every admitted candidate into `greater` (the true pair ranks
+ * last, ties = 0), and a NaN candidate counts as greater than any true score.  -inf and +inf follow ordinary comparison:
+ * equal infinities tie, a -inf candidate is greater than nothing.  "Admitted" is applied before the comparison (not the
+ * true partner, not a known pair, inside the relation's range, < num_nodes): a known or out-of-range candidate never counts
+ * whatever its score.  Non-finite scores set NO bit of *error_flag.  (The library is built without any fast-math option;
+ * the rule depends on it.) */
 GN_API gn_status gn_distmult_rank_f32(const float* z, int64_t ld_z, int64_t num_nodes, int64_t num_features, const float* d,
                                int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* v, const int64_t* edge_type,
                                int64_t num_queries, const gn_known_pairs* known /* nullable */, int32_t* greater, int32_t* ties,
                                int32_t* error_flag, void* stream);
 /* Per query e = (u[e], edge_type[e]): the k (1..64) best candidates that are not known pairs, by logit descending then id
  * ascending: scores[e * k + j] (fp32 logits) and ids[e * k + j]; padded with -inf / -1 when fewer than k candidates with a
- * score above -inf remain (NaN scores never enter).  A query with an id out of range gets NaN / -1 and sets bit 0 of
- * *error_flag. */
+ * score above -inf remain.  A NaN or -inf score never enters; +inf enters, and equal scores (equal infinities too) order by
+ * ascending id.  A query whose whole candidate row is NaN (a NaN z[u], say) gets a full row of padding -inf / -1 and sets
+ * no bit of *error_flag; a query with an id out of range gets NaN / -1 and sets bit 0 of *error_flag. */
 GN_API gn_status gn_distmult_topk_f32(const float* z, int64_t ld_z, int64_t num_nodes, int64_t num_features, const float* d,
                                int64_t ld_d, int64_t num_relations, const int64_t* u, const int64_t* edge_type, int64_t num_queries,
                                int64_t k, const gn_known_pairs* known /* nullable */, float* scores, int64_t* ids,
@@ -871,9 +879,26 @@ GN_API gn_status gn_distmult_topk_ranged_f32(const float* z, int64_t ld_z, int64
  * GN_KGE_SIDE_HEAD - fixed is the tail, the candidates are the heads h' of (h', r, fixed).  `known` (nullable) filters the
  * candidates whose (relation, fixed, candidate) is a known pair: its rows are keyed (relation, fixed entity), so for the
  * head side it is built from the FLIPPED lists (u = tail, v = head).
- *   rank:  greater[e] / ties[e] = the non-known candidates c != truth[e] with s(c) > s(truth[e]) / s(c) == s(truth[e]);
+ *   rank:  greater[e] / ties[e] = the non-known candidates c != truth[e] with NOT (s(c) <= s(truth[e])) / s(c) == s(truth[e]);
  *   top-k: the k (1..64) best non-known candidates, score descending then id ascending: scores[e * k + j], ids[e * k + j],
  *          padded with -inf / -1.
+ * NON-FINITE SCORES never flatter the model (the rules of gn_distmult_rank_f32 / gn_distmult_topk_f32).  rank: greater[e] =
+ * the admitted candidates c with NOT (s(c) <= s(true)), ties[e] = those with s(c) == s(true): a NaN true score puts every
+ * admitted candidate into `greater` (the true triple ranks last, ties = 0), a NaN candidate counts as greater than any true
+ * score; -inf and +inf follow ordinary comparison (equal infinities tie, a -inf candidate is greater than nothing).
+ * "Admitted" (not the true partner, not a known pair, inside the relation's range, < num_entities) is applied before the
+ * comparison: a known or out-of-range candidate never counts whatever its score.  top-k: a NaN or -inf score never enters,
+ * +inf enters, equal scores order by ascending id; a query whose whole candidate row is NaN (a NaN fixed entity, say) gets
+ * a full row of padding -inf / -1, not the NaN / -1 of an id out of range.  Non-finite scores set NO bit of *error_flag.
+ * (TransE and RotatE score gamma - distance: never +inf.)
+ * WHICH SCORE.  s is the value the scan computes, and with non-finite rows the formulation matters.  TransE, RotatE and
+ * ComplEx on the tail side evaluate the forward's expression in the forward's order, DistMult a product of three factors
+ * whose kind no order changes (0 * inf and inf - inf give NaN where they do in the forward).  ComplEx on the HEAD side folds the relation and the fixed tail into the query row first:
+ *   s(h') = sum_k (rr tr + ri ti)_k hr'_k + (rr ti - ri tr)_k hi'_k,
+ * the forward's Re((h' r) conj t) regrouped - the same number up to rounding on finite rows, but another KIND of value on a
+ * non-finite one: a candidate head with hr'_k = +inf scores +-inf by the sign of (rr tr + ri ti)_k, where the forward gives
+ * NaN as soon as one of rr, ri, tr, ti is zero in that column or the two products differ in sign.  The rules above hold for
+ * this s (a NaN row still scores NaN; a row with an infinite entry may rank by its infinity instead of last).
  * A candidate's score depends on the query's and the candidate row's bits and a fixed column order only (equal rows tie),
  * and the true score is the scan's own value for that candidate.  DistMult and ComplEx run on the fp32 matrix cores (the
  * engine of gn_distmult_rank_f32, fed with query rows that a small launch prepares), TransE and RotatE on the vector ALU

@@ -73,14 +73,15 @@ def ref_rank(scores, truth, mask):
 
 
 def ref_topk(scores, mask, k):
-    s = scores.to(torch.float64).masked_fill(mask, float("-inf"))
+    s = scores.to(torch.float64)
+    s = s.masked_fill(mask | torch.isnan(s), float("-inf"))            # a NaN score never enters (nor does -inf: padding)
     val, idx = torch.sort(s, dim=1, descending=True, stable=True)      # stable: equal scores keep ascending ids
     val, idx = val[:, :k], idx[:, :k]
     if val.shape[1] < k:
         pad = k - val.shape[1]
         val = torch.cat([val, torch.full((val.shape[0], pad), float("-inf"), dtype=val.dtype, device=val.device)], 1)
         idx = torch.cat([idx, torch.full((idx.shape[0], pad), -1, dtype=idx.dtype, device=idx.device)], 1)
-    idx = torch.where(torch.isinf(val), torch.full_like(idx, -1), idx)
+    idx = torch.where(torch.isneginf(val), torch.full_like(idx, -1), idx)     # (a +inf entry keeps its id)
     return val, idx
 
 
