@@ -32,6 +32,14 @@ always did.
 
     python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3 --negatives 256 --adversarial-temperature 1.0 --filter-negatives
 
+`--shared-negatives G` (with `--negatives K`) shares one list of K candidates among a chunk of the mini-batch's positives, as
+DGL-KE and PyTorch-BigGraph do: the batch is cut into G chunks, gripnet_amd.kge.sample_shared_candidates draws G lists on the
+device and the scorer runs in the 'tail-shared' / 'head-shared' modes - G K entity rows are gathered instead of batch x K, and
+DistMult and ComplEx score on the matrix cores.  A shared list cannot be filtered per positive, so the flag does not combine
+with `--filter-negatives`, `--typed-candidates` or `--torch-loss`; a last, shorter batch takes gcd(its size, G) chunks.
+
+    python examples/train_kge.py --model ComplEx --workload pose0-syn --epochs 3 --negatives 256 --shared-negatives 8
+
 `--typed-candidates` restricts `--rank` and `--negatives K` to the entities that can fill the slot at all (the reference
 draws its evaluation negatives from the drugs only, :277-279): a drug-drug relation's heads and tails are drugs
 [0, n_drug), the gene-gene relation's are genes [n_drug, n_node), the bidirectional gene-drug relation keeps every
@@ -41,6 +49,7 @@ are then sorted by relation, so that a workgroup's queries share a range and the
     python examples/train_kge.py --model RotatE --workload pose0-syn --epochs 3 --rank --typed-candidates
 """
 import argparse
+import math
 import os
 import sys
 import time
@@ -53,7 +62,7 @@ sys.path.insert(0, ROOT)
 
 from gripnet_amd import KGEModel                                      # reference: class KGEModel, :58-235
 from gripnet_amd import _hip
-from gripnet_amd.kge import negative_sampling_loss, sample_candidates, self_adversarial_loss
+from gripnet_amd.kge import negative_sampling_loss, sample_candidates, sample_shared_candidates, self_adversarial_loss
 from gripnet_amd.synth import make_rgcn_pose
 from gripnet_amd.decoder import KnownPairs
 from gripnet_amd.utils import (EPS, candidate_ranges, device_negative_sampler, ranking_metrics, relation_metrics,
@@ -125,6 +134,8 @@ def main():
     ap.add_argument("--filter-negatives", action="store_true", help="never draw a known training triple as a negative")
     ap.add_argument("--subsampling", action="store_true", help="weight a positive by 1 / sqrt(count(r, h) + count(r, t) + 4)")
     ap.add_argument("--torch-loss", action="store_true", help="torch.randint candidates and the loss in torch ops")
+    ap.add_argument("--shared-negatives", type=int, default=None, metavar="G",
+                    help="share one list of K candidates among each of G chunks of a mini-batch ('tail-shared' / 'head-shared')")
     ap.add_argument("--typed-candidates", action="store_true",
                     help="--rank and --negatives take a relation's candidates from the node type that can fill the slot")
     args = ap.parse_args()
@@ -172,11 +183,16 @@ def main():
         auprc, auroc, ap = relation_metrics(pos_score.detach()[:drug_edges].contiguous(), neg_score, drug_ranges)
         return float(loss.detach()), float(auprc.nanmean()), float(auroc.nanmean()), float(ap.nanmean())
 
-    batched = args.negatives is not None or args.adversarial_temperature is not None
+    batched = args.negatives is not None or args.adversarial_temperature is not None or args.shared_negatives is not None
     n_negatives = 256 if args.negatives is None else args.negatives
 
     if args.torch_loss and (args.filter_negatives or args.subsampling or args.typed_candidates):
         ap.error("--torch-loss is the unfiltered, unweighted, untyped formulation")
+    if args.shared_negatives is not None:
+        if args.torch_loss or args.filter_negatives or args.typed_candidates:
+            ap.error("--shared-negatives draws unfiltered, untyped lists and scores them on the HIP path")
+        if not 1 <= args.shared_negatives <= args.batch:
+            ap.error("--shared-negatives G needs 1 <= G <= --batch")
     typed = None
     if args.typed_candidates:                                         # drug-drug relations, then gene-gene, then gene-drug (both ways)
         R, n_drug, n_node = int(data.n_edge_type), int(data.n_drug), int(data.n_node)
@@ -206,7 +222,13 @@ def main():
             positive, et = data.train_idx[:, pick].contiguous(), data.train_et[pick].contiguous()
             mode = "tail-batch" if i % 2 == 0 else "head-batch"
             optimizer.zero_grad()
-            if args.torch_loss:
+            if args.shared_negatives is not None:
+                lists = math.gcd(pick.numel(), args.shared_negatives)
+                mode = mode.replace("batch", "shared")
+                candidates = sample_shared_candidates(lists, n_negatives, data.n_node, seed=(1111 + epoch) * len(starts) + i, device=device)
+                loss = negative_sampling_loss(model.score(positive, et), model.score((positive, candidates), et, mode=mode),
+                                              args.adversarial_temperature, None if weights is None else weights[pick])
+            elif args.torch_loss:
                 candidates = torch.randint(0, data.n_node, (pick.numel(), n_negatives), generator=gen, device=device)
                 loss = self_adversarial_loss(model.score(positive, et), model.score((positive, candidates), et, mode=mode),
                                              args.adversarial_temperature)

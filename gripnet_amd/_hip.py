@@ -29,7 +29,7 @@ RGCN_PATH_NAMES = {code: name for name, code in RGCN_PATHS.items()}
 GN_GEMM_RELU, GN_GEMM_ARITH_FAST, GN_GEMM_B_TRANSPOSED, GN_GEMM_ACCUMULATE, GN_GEMM_A_TRANSPOSED, GN_GEMM_JOIN_BATCH, GN_GEMM_OUT_BF16 = 1, 2, 4, 8, 16, 32, 64                                    # flags of gn_gemm_f32
 GN_DM_TYPES_SORTED = 1                                 # flags of gn_distmult_backward_ex_f32
 GN_DM_TYPE_TASKS = 2
-ABI_VERSION = 172                                       # GN_VERSION of include/gripnet_hip.h this module binds
+ABI_VERSION = 173                                       # GN_VERSION of include/gripnet_hip.h this module binds
 
 _p, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
 
@@ -120,6 +120,10 @@ SIGNATURES = {
     "gn_kge_batch_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_batch_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64, _i64]),
     "gn_kge_batch_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _int, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
+    "gn_kge_shared_forward_workspace_bytes": (_sz, [_int, _i64, _i64]),
+    "gn_kge_shared_forward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _int, C.c_float, C.c_float, _int, _p, _p, _p, _p, _sz, _p]),
+    "gn_kge_shared_backward_workspace_bytes": (_sz, [_int, _i64, _i64, _i64, _i64, _i64, _i64]),
+    "gn_kge_shared_backward_f32": (_int, [_int, _p, _i64, _i64, _p, _i64, _i64, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _int, C.c_float, _p, _p, _p, _i64, _p, _i64, _int, _p, _sz, _p]),
     "gn_kge_ns_loss_workspace_bytes": (_sz, [_i64]),
     "gn_kge_ns_loss_forward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, C.c_float, _p, _p, _p, _p, _sz, _p]),
     "gn_kge_ns_loss_backward_f32": (_int, [_p, _p, _i64, _i64, _i64, _p, _int, C.c_float, _p, _p, _p, _p, _p, _i64, _p]),
@@ -1535,6 +1539,61 @@ def kge_batch_backward(model, ent, rel, fixed, et, cand, side, divisor, grad_out
     return d_ent, d_rel
 
 
+def _kge_shared_operands(model, ent, rel, fixed, et, cand, side):
+    """(model id, hidden size, side id, fixed, edge_type, candidate lists as the kernels read them, B, G, K) of a
+    shared-list call, shapes checked: `cand` [G, K] int64 with 1 <= G <= B and B % G == 0 (a row stride above K is kept,
+    any other layout is copied); entity rows of at most KGE_SHARED_MAX_ROW floats."""
+    m, h = _kge_hidden(model, ent, rel)
+    if side not in KGE_SIDES:
+        raise ValueError("side must be 'tail' or 'head', got {!r}".format(side))
+    if ent.shape[1] > KGE_SHARED_MAX_ROW:
+        raise ValueError("{}: the shared-list kernels take entity rows of at most {} floats (hidden_dim <= {}), got {}".format(
+            model, KGE_SHARED_MAX_ROW, KGE_SHARED_MAX_ROW * h // ent.shape[1], ent.shape[1]))
+    fixed, types = i64_vec(fixed), i64_vec(et)
+    if fixed.dim() != 1 or types.dim() != 1 or types.numel() != fixed.numel():
+        raise ValueError("fixed entities {} and edge_type {} must be two vectors of one length".format(
+            tuple(fixed.shape), tuple(types.shape)))
+    b = int(fixed.numel())
+    if cand.dtype != torch.int64:
+        raise TypeError("indices must be int64 (torch.long), got {}".format(cand.dtype))
+    if cand.dim() != 2 or not 1 <= cand.shape[0] <= max(b, 1) or b % cand.shape[0] != 0:
+        raise ValueError("shared candidates must have shape [G, K] with G dividing the {} positives, got {}".format(
+            b, tuple(cand.shape)))
+    g, k = int(cand.shape[0]), int(cand.shape[1])
+    if (k > 1 and cand.stride(1) != 1) or (g > 1 and cand.stride(0) < k):
+        cand = cand.contiguous()
+    return m, h, KGE_SIDES[side], fixed, types, cand, b, g, k
+
+
+def kge_shared_forward(model, ent, rel, fixed, et, cand, side, gamma, divisor, log_sigmoid, out, raw=None):
+    """gn_kge_shared_forward_f32: out[b, k] (fp32 [B, K], contiguous) = the score of (fixed[b], et[b], cand[g, k]) for
+    `side` "tail", of (cand[g, k], et[b], fixed[b]) for "head", g = b // (B // G) (with `log_sigmoid`: its log-sigmoid,
+    the raw scores into `raw`).  Ids outside the tables: NaN (a bad fixed entity or relation: the whole row; a bad
+    candidate: its column of its chunk) and the device's error flag (raise_if_index_errors)."""
+    m, h, sd, fixed, types, cand, b, g, k = _kge_shared_operands(model, ent, rel, fixed, et, cand, side)
+    need = int(load().gn_kge_shared_forward_workspace_bytes(m, rel.shape[0], h))
+    ws = torch.empty((need,), dtype=torch.uint8, device=ent.device) if need else None
+    _call("gn_kge_shared_forward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(fixed), ptr(types),
+          ptr(cand), ld(cand), b, g, k, sd, float(gamma), float(divisor), int(bool(log_sigmoid)), ptr(out), ptr(raw),
+          ptr(error_flag(ent.device)), ptr(ws), need, stream_ptr(ent.device))
+    return out
+
+
+def kge_shared_backward(model, ent, rel, fixed, et, cand, side, divisor, grad_out, raw, d_ent, d_rel, types_sorted=None):
+    """gn_kge_shared_backward_f32: d_ent / d_rel (overwritten) from the gradient [B, K] of kge_shared_forward's output;
+    `raw`: the raw scores when that output was the log-sigmoid.  `types_sorted` None: looked up (once per edge_type tensor
+    and version)."""
+    m, h, sd, fixed, types, cand, b, g, k = _kge_shared_operands(model, ent, rel, fixed, et, cand, side)
+    if types_sorted is None:
+        types_sorted = b < 2 or _non_decreasing(et)
+    need = int(load().gn_kge_shared_backward_workspace_bytes(m, ent.shape[0], rel.shape[0], h, b, g, k))
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=ent.device)
+    _call("gn_kge_shared_backward_f32", m, ptr(ent), ld(ent), ent.shape[0], ptr(rel), ld(rel), rel.shape[0], h, ptr(fixed), ptr(types),
+          ptr(cand), ld(cand), b, g, k, sd, float(divisor), ptr(grad_out), ptr(raw), ptr(d_ent), ld(d_ent), ptr(d_rel), ld(d_rel),
+          GN_DM_TYPES_SORTED if types_sorted else 0, ptr(ws), need, stream_ptr(ent.device))
+    return d_ent, d_rel
+
+
 def kge_ns_block(pos, neg):
     """(B, K) of a score block of the negative-sampling loss: pos fp32 [B] contiguous, neg fp32 [B, K] with unit inner
     stride and a row stride of at least K (what KgeNegativeSamplingLossFn hands on)."""
@@ -1790,6 +1849,7 @@ def distmult_topk(z, nodes, edge_type, weight, k, known=None, candidates=None):
     return scores, ids
 
 
+KGE_SHARED_MAX_ROW = 128                                                       # floats of an entity row the shared-list kernels take (the ranking limit)
 KGE_SIDES = {"tail": 0, "head": 1}                                             # GN_KGE_SIDE_* of include/gripnet_hip.h
 KGE_RANK_MAX_ROW = 128                                                         # floats of an entity row the ranking kernels take
 

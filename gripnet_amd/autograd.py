@@ -548,6 +548,31 @@ class KgeBatchScoreFn(torch.autograd.Function):
         return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None, None
 
 
+class KgeSharedScoreFn(torch.autograd.Function):
+    """The scores [B, K] of the B positives (fixed[b], et[b]) against SHARED candidate lists cand [G, K] - positive b reads
+    the list of its chunk g = b // (B // G) - under one of the KGE baselines, or their log-sigmoid: the 'tail-shared' /
+    'head-shared' modes of KGEModel.forward (csrc/kge_shared.hip).  `side` as for KgeBatchScoreFn; saves what it saves."""
+
+    @staticmethod
+    def forward(ctx, entity, relation, fixed, et, cand, side, model, gamma, divisor, log_sigmoid):
+        ent, rel = _hip.f32_rows(entity.detach()), _hip.f32_rows(relation.detach())
+        shape = (fixed.shape[0], cand.shape[1])
+        out = torch.empty(shape, dtype=torch.float32, device=ent.device)
+        raw = torch.empty(shape, dtype=torch.float32, device=ent.device) if log_sigmoid else None
+        _hip.kge_shared_forward(model, ent, rel, fixed, et, cand, side, gamma, divisor, log_sigmoid, out, raw)
+        ctx.model, ctx.divisor, ctx.side = model, divisor, side
+        ctx.save_for_backward(ent, rel, fixed, et, cand, raw)  # (sigma(-s) of the log-sigmoid is applied where the upstream is read)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ent, rel, fixed, et, cand, raw = ctx.saved_tensors
+        g = g.contiguous().to(torch.float32)
+        d_ent, d_rel = torch.empty_like(ent), torch.empty_like(rel)
+        _hip.kge_shared_backward(ctx.model, ent, rel, fixed, et, cand, ctx.side, ctx.divisor, g, raw, d_ent, d_rel)
+        return (d_ent if ctx.needs_input_grad[0] else None), (d_rel if ctx.needs_input_grad[1] else None), None, None, None, None, None, None, None, None
+
+
 class KgeNegativeSamplingLossFn(torch.autograd.Function):
     """The negative-sampling loss of a KGE mini-batch on raw scores pos [B] and neg [B, K] (csrc/kge_loss.hip), one launch
     forward and one backward: ``loss = f(pos, neg, weight, temperature)`` with `weight` [B] or None (subsampling weights,

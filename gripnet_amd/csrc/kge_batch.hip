@@ -20,8 +20,9 @@
 //      k = slot, slot + S, ... in that order, the S slots are folded in slot order - into one partial row per positive and role;
 //   3. two seg_pass calls over B records keyed by fixed[b] and et[b] add those rows (RowTerm: the term is the partial row
 //      itself, g = 1: the fused multiply-add by 1 is exact); the entity one accumulates onto the candidate pass.
-// The records of 1 and 3 come from the one builder of kge_rows.cuh (BlockSrc, RowSrc); the checks both backward entry points
-// make, and what their passes hold, are backward_frame / BwdFrame there.
+// The records of 1 and 3 come from the one builder of kge_rows.cuh (BlockSrc here, RowSrc there); RowSrc, RowTerm and the
+// chunk size of the row passes are in kge_rows.cuh, shared with kge_shared.hip; the checks both backward entry points make,
+// and what their passes hold, are backward_frame / BwdFrame there.
 #include "common.h"
 #include "kge_rows.cuh"
 
@@ -133,38 +134,6 @@ struct BlockSrc {
         const float g = upstream(grad_out, raw, e);
         rec = side == kTailSide ? Rec{(uint32_t)ff, (uint32_t)cc, (uint32_t)rr, g} : Rec{(uint32_t)cc, (uint32_t)ff, (uint32_t)rr, g};
         return true;
-    }
-};
-
-// one record per positive for the passes that add the partial rows: h = the positive (its partial row), t = its entity, g = 1
-struct RowSrc {
-    const int64_t* fixed; const int64_t* et;
-    __device__ bool get(int64_t b, const Tables& t, Rec& rec) const {
-        const int64_t ff = fixed[b], rr = et[b];
-        if (!in_tables(t, ff, ff, rr)) return false;
-        rec = {(uint32_t)b, (uint32_t)ff, (uint32_t)rr, 1.0f};
-        return true;
-    }
-};
-
-// Records of a chunk in the passes that add the partial rows.  Most of their rows hold one record or two (a mini-batch's
-// positives rarely share an entity), and a chunk's rows are taken one after the other: 32 rows per workgroup, not 2 048.
-constexpr int kRowChunkRecs = 32;
-
-// A positive's partial row as a contribution: rows [B, P * h], part p at column p * h.
-template <int PARTS>
-struct RowTerm {
-    using Rec = ::Rec;
-    static constexpr int P = PARTS;
-    static constexpr bool kFused = true;
-    const float* rows; int64_t ld; int h;
-    static __device__ __forceinline__ bool skip(const Rec& r) { return r.h == kSkip; }
-    template <int VEC>
-    __device__ __forceinline__ void terms(const Rec& r, int unit, float (&d)[P][VEC]) const {
-#pragma unroll
-        for (int p = 0; p < P; ++p)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) d[p][v] = rows[(int64_t)r.h * ld + (int64_t)p * h + unit * VEC + v];
     }
 };
 
@@ -301,8 +270,6 @@ gn_status row_pass(const BwdCall& c, const gn::SegWs<Rec>& w) {
                        },
                        kRowChunkRecs);
 }
-
-size_t rows_bytes(int64_t b, int64_t d) { return gn::seg_align_up((size_t)b * d * sizeof(float)); }
 
 // The backward's scratch: one reduction's (the B * K candidate records; the B row records reuse it afterwards); in its
 // tail RotatE's cos / sin tables, then the positives' partial rows [B, De] and [B, Dr].

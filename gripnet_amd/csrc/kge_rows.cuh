@@ -6,7 +6,8 @@
 //   * wave_scores and store_score: the forward kernels' wave loop (lane groups, xor fold, transposition) and epilogue;
 //   * dscore, Rec, KgeTerm: the derivative of a column's term per role, the backward's record and its contribution to
 //     seg_reduce.cuh; k_kge_recs: the one record builder, over a source per entry point;
-//   * BwdFrame and backward_frame: what both backward entry points check and hold; launch_seg_reduce: the column-block rule.
+//   * BwdFrame and backward_frame: what both backward entry points check and hold; launch_seg_reduce: the column-block rule;
+//   * RowSrc, RowTerm, kRowChunkRecs: the passes that add partial rows (one per positive, or per shared candidate).
 #pragma once
 
 #include "common.h"
@@ -345,5 +346,41 @@ gn_status record_pass(const BwdFrame& c, const gn::SegWs<Rec>& w, const Src& src
     const int vecw = c.vec ? 4 : 1;
     return gn::seg_pass(w, count, rows, sorted_types, o, c.t.h / vecw, vecw, c.lpe, launch, c.st, chunk);
 }
+
+// ---- partial rows: the passes that add one row per record (kge_batch.hip: a positive's row; kge_shared.hip: also a shared
+// candidate's) ------------------------------------------------------------------------------------------------------------
+// one record per positive for the passes that add the partial rows: h = the positive (its partial row), t = its entity, g = 1
+struct RowSrc {
+    const int64_t* fixed; const int64_t* et;
+    __device__ bool get(int64_t b, const Tables& t, Rec& rec) const {
+        const int64_t ff = fixed[b], rr = et[b];
+        if (!in_tables(t, ff, ff, rr)) return false;
+        rec = {(uint32_t)b, (uint32_t)ff, (uint32_t)rr, 1.0f};
+        return true;
+    }
+};
+
+// Records of a chunk in the passes that add the partial rows.  Most of their rows hold one record or two (a mini-batch's
+// positives rarely share an entity), and a chunk's rows are taken one after the other: 32 rows per workgroup, not 2 048.
+constexpr int kRowChunkRecs = 32;
+
+// A positive's partial row as a contribution: rows [B, P * h], part p at column p * h.
+template <int PARTS>
+struct RowTerm {
+    using Rec = ::Rec;
+    static constexpr int P = PARTS;
+    static constexpr bool kFused = true;
+    const float* rows; int64_t ld; int h;
+    static __device__ __forceinline__ bool skip(const Rec& r) { return r.h == kSkip; }
+    template <int VEC>
+    __device__ __forceinline__ void terms(const Rec& r, int unit, float (&d)[P][VEC]) const {
+#pragma unroll
+        for (int p = 0; p < P; ++p)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) d[p][v] = rows[(int64_t)r.h * ld + (int64_t)p * h + unit * VEC + v];
+    }
+};
+
+inline size_t rows_bytes(int64_t b, int64_t d) { return gn::seg_align_up((size_t)b * d * sizeof(float)); }
 
 }  // namespace

@@ -170,22 +170,30 @@ static __global__ void k_seg_combine(const int32_t* __restrict__ rowptr, const f
 // ---- host side ----------------------------------------------------------------------------------------------------
 // A pass's scratch: keys and records before and behind the sort, the row offsets of up to max_rows rows, the chunks'
 // partials for up to `parts` output parts, a tail that is the caller's (the KGE scorers keep RotatE's cos / sin tables
-// there), rocPRIM's temporary.
+// there), rocPRIM's temporary.  chunk_recs: the smallest chunk any pass over this scratch cuts (the partials hold a slot pair
+// per chunk).  also_sorts: a smaller record count that a later pass sorts in the same scratch (rocPRIM picks its algorithm,
+// and its temporary, by size: the temporary is the larger of the two).
 struct SegLayout { size_t keys, keys_sorted, recs, recs_sorted, rowptr, partial, tail, sort_tmp, total; };
 
 template <typename Rec>
-SegLayout seg_layout(int64_t e, int64_t max_rows, int parts, size_t tail_bytes) {
+SegLayout seg_layout(int64_t e, int64_t max_rows, int parts, size_t tail_bytes, int chunk_recs = kSegChunkRecs, int64_t also_sorts = 0) {
     SegLayout l;
     size_t sort_bytes = 0;
     (void)rocprim::radix_sort_pairs(nullptr, sort_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (Rec*)nullptr, (Rec*)nullptr,
                                     (size_t)e, 0, 32, (hipStream_t)0);
+    if (also_sorts > 0) {
+        size_t other = 0;
+        (void)rocprim::radix_sort_pairs(nullptr, other, (uint32_t*)nullptr, (uint32_t*)nullptr, (Rec*)nullptr, (Rec*)nullptr,
+                                        (size_t)also_sorts, 0, 32, (hipStream_t)0);
+        sort_bytes = std::max(sort_bytes, other);
+    }
     l.keys = 0;
     l.keys_sorted = l.keys + seg_align_up(e * sizeof(uint32_t));
     l.recs = l.keys_sorted + seg_align_up(e * sizeof(uint32_t));
     l.recs_sorted = l.recs + seg_align_up(e * sizeof(Rec));
     l.rowptr = l.recs_sorted + seg_align_up(e * sizeof(Rec));
     l.partial = l.rowptr + seg_align_up((max_rows + 2) * sizeof(int32_t));
-    l.tail = l.partial + seg_align_up((size_t)ceil_div(e, kSegChunkRecs) * 2 * parts * kSegBlockCols * sizeof(float));
+    l.tail = l.partial + seg_align_up((size_t)ceil_div(e, (int64_t)chunk_recs) * 2 * parts * kSegBlockCols * sizeof(float));
     l.sort_tmp = l.tail + seg_align_up(tail_bytes);
     l.total = l.sort_tmp + seg_align_up(sort_bytes);
     return l;

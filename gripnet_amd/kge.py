@@ -11,7 +11,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _hip
-from .autograd import KgeBatchScoreFn, KgeNegativeSamplingLossFn, KgeScoreFn
+from .autograd import KgeBatchScoreFn, KgeNegativeSamplingLossFn, KgeScoreFn, KgeSharedScoreFn
 
 PI = 3.14159265358979323846                                    # the constant the reference divides by (:214)
 
@@ -19,6 +19,7 @@ PI = 3.14159265358979323846                                    # the constant th
 _HALVES = {"TransE": (None, None), "DistMult": (None, None), "ComplEx": (True, True), "RotatE": (True, None)}
 
 _BATCH_SIDES = {"tail-batch": "tail", "head-batch": "head"}    # forward's batch modes -> the side the candidates stand on
+_SHARED_SIDES = {"tail-shared": "tail", "head-shared": "head"}  # forward's shared-list modes -> that side
 
 
 def self_adversarial_loss(positive_score, negative_score, adversarial_temperature=None):
@@ -66,6 +67,20 @@ def negative_sampling_loss(positive_score, negative_score, adversarial_temperatu
     temperature = _loss_block(positive_score, negative_score, adversarial_temperature, subsampling_weight)
     _hip.require_gpu(positive_score, negative_score, subsampling_weight)
     return KgeNegativeSamplingLossFn.apply(positive_score, negative_score, subsampling_weight, temperature)
+
+
+def _shared_block(positive, negatives, et):
+    """The shape checks of the shared-list modes: positive [2, B], et [B], negatives [G, K] with 1 <= G <= B, B % G == 0."""
+    if positive.dim() != 2 or positive.shape[0] != 2 or positive.shape[1] < 1:
+        raise ValueError("positive must have shape [2, B] with B >= 1, got {}".format(tuple(positive.shape)))
+    b = positive.shape[1]
+    if et.dim() != 1 or et.shape[0] != b:
+        raise ValueError("edge_type must have shape [{}], got {}".format(b, tuple(et.shape)))
+    if negatives.dim() != 2 or not 1 <= negatives.shape[0] <= b:
+        raise ValueError("negatives must have shape [G, K] with 1 <= G <= {}, got {}".format(b, tuple(negatives.shape)))
+    if b % negatives.shape[0] != 0:
+        raise ValueError("the {} lists of negatives {} do not divide the {} positives {} into equal chunks".format(
+            negatives.shape[0], tuple(negatives.shape), b, tuple(positive.shape)))
 
 
 def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0, step=None, out=None, candidates=None):
@@ -118,6 +133,47 @@ def sample_candidates(positive, et, K, nentity, side="tail", known=None, seed=0,
     return _hip.kge_candidates_sample(fixed, et, K, nentity, known, seed, step, out, candidates)
 
 
+def sample_shared_candidates(G, K, nentity, seed=0, step=None, out=None, candidates_range=None, device=None):
+    """int64 [G, K]: one list of K candidate entities per chunk of positives for the shared-list modes of
+    ``KGEModel.forward`` / ``.score`` ('tail-shared' / 'head-shared'), drawn on the device uniformly, with replacement, from
+    all `nentity` entities or - with ``candidates_range=(lo, hi)`` - from the entities lo <= c < hi.  It is
+    ``sample_candidates``' unfiltered draw with the chunk index g in the place of the positive b: the same kernel and the same
+    documented stream (include/gripnet_hip.h, gn_kge_candidates_sample), ``base = mix64(seed ^ (g K + k) *
+    0xD6E8FEB86659FD93)``, element for element what ``sample_candidates(known=None)`` gives G positives.  `seed`, `step`
+    and `out` (int64 [G, K], unit inner stride) as there; `device`: where to draw when neither `out` nor `step` says
+    (default: the current GPU).  A list is shared by many positives, so a per-positive `known` filter cannot apply to it:
+    NO false negative is filtered or masked here (a drawn candidate may be a positive's true partner, as in the trainers
+    this scheme comes from); a caller who needs filtered negatives uses ``sample_candidates`` and the block modes.  A range
+    outside [0, nentity] or with lo > hi gives rows of -1 and the IndexError, an empty one rows of -1 and the "no entity to
+    draw" RuntimeError, both at the next synchronising check (``_hip.raise_if_index_errors``)."""
+    for name, value in (("G", G), ("K", K)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or int(value) < 1:
+            raise ValueError("{} must be a positive integer, got {!r}".format(name, value))
+    if isinstance(nentity, bool) or not isinstance(nentity, (int, np.integer)) or not 1 <= int(nentity) < 2 ** 31:
+        raise ValueError("nentity must be an integer in [1, 2^31), got {!r}".format(nentity))
+    G, K, nentity = int(G), int(K), int(nentity)
+    if device is None:
+        device = out.device if out is not None else step.device if step is not None else torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device)
+    if step is not None and (step.dtype != torch.int64 or step.numel() != 1 or step.device != device):
+        raise ValueError("`step` must be a one-element int64 tensor on {}".format(device))
+    if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (G, K) or out.device != device or
+                            (K > 1 and out.stride(1) != 1) or (G > 1 and out.stride(0) < K)):
+        raise ValueError("`out` must be an int64 [{}, {}] tensor with a unit inner stride on {}".format(G, K, device))
+    table = None
+    if candidates_range is not None:
+        try:
+            lo, hi = (int(v) for v in candidates_range)
+        except (TypeError, ValueError):
+            raise ValueError("candidates_range must be a pair (lo, hi) of integers, got {!r}".format(candidates_range)) from None
+        table = torch.tensor([[lo, hi]], dtype=torch.int64, device=device)
+    zeros = torch.zeros(G, dtype=torch.int64, device=device)       # every chunk "fixes" entity 0 under relation 0: never read without a filter
+    _hip.require_gpu(zeros)
+    if out is None:
+        out = torch.empty((G, K), dtype=torch.int64, device=device)
+    return _hip.kge_candidates_sample(zeros, zeros, K, nentity, None, seed, step, out, table)
+
+
 class KGEModel(nn.Module):
     """``KGEModel(model_name, nentity, nrelation, hidden_dim, gamma)``: entity table [nentity, De], relation table
     [nrelation, Dr] with De, Dr = hidden_dim or twice that (ComplEx: both doubled; RotatE: the entities; otherwise as the two
@@ -157,6 +213,8 @@ class KGEModel(nn.Module):
 
     def _score(self, sample, et, log_sigmoid, mode="single"):
         ent, rel = self.entity_embedding, self.relation_embedding
+        if mode in _SHARED_SIDES:
+            return self._score_shared(sample, et, log_sigmoid, mode)
         if mode != "single":
             return self._score_batch(sample, et, log_sigmoid, mode)
         _hip.require_gpu(ent, rel, sample, et)
@@ -188,17 +246,47 @@ class KGEModel(nn.Module):
         return _hip.kge_batch_forward(self.model_name, _hip.f32_rows(ent.detach()), _hip.f32_rows(rel.detach()), fixed, et,
                                       negatives, side, gamma, divisor, log_sigmoid, out)
 
+    def _score_shared(self, sample, et, log_sigmoid, mode):
+        """[B, K]: the candidates negatives[b // (B // G), :] in the place of the positive's tail ('tail-shared') or head."""
+        side = _SHARED_SIDES[mode]
+        positive, negatives = sample
+        _shared_block(positive, negatives, et)
+        ent, rel = self.entity_embedding, self.relation_embedding
+        if ent.shape[1] > _hip.KGE_SHARED_MAX_ROW:
+            raise ValueError("{}: mode {} takes entity rows of at most {} floats (hidden_dim <= {}), got {}".format(
+                self.model_name, mode, _hip.KGE_SHARED_MAX_ROW, _hip.KGE_SHARED_MAX_ROW * self.hidden_dim // ent.shape[1], ent.shape[1]))
+        _hip.require_gpu(ent, rel, positive, negatives, et)
+        gamma, divisor = self._constants()
+        fixed = positive[0] if side == "tail" else positive[1]     # the member the candidates do not replace
+        negatives = negatives.contiguous()
+        if torch.is_grad_enabled() and (ent.requires_grad or rel.requires_grad):
+            return KgeSharedScoreFn.apply(ent, rel, fixed, et, negatives, side, self.model_name, gamma, divisor, log_sigmoid)
+        out = torch.empty((positive.shape[1], negatives.shape[1]), dtype=torch.float32, device=ent.device)
+        return _hip.kge_shared_forward(self.model_name, _hip.f32_rows(ent.detach()), _hip.f32_rows(rel.detach()), fixed, et,
+                                       negatives, side, gamma, divisor, log_sigmoid, out)
+
     def forward(self, sample, et, mode="single"):
         """``mode="single"``: ``logsigmoid(score)`` [E] of the triples (sample[0, e], et[e], sample[1, e]) (:127-187).
         ``mode="tail-batch"`` / ``"head-batch"`` (:127-136, :150-173): `sample` is a pair ``(positive, negatives)`` -
         positive [2, B], negatives int64 [B, K] (made contiguous if it is not), et [B] - and the result is
         ``logsigmoid(score)`` [B, K] of (positive[0, b], et[b], negatives[b, k]) for 'tail-batch', of (negatives[b, k], et[b],
         positive[1, b]) for 'head-batch': K corrupted tails or heads per positive in one launch, every score the same bits
-        as the 'single' mode gives for that triple.  Any other mode raises ``ValueError("mode %s not supported")``; before
-        the batch modes existed every string was accepted and ignored, and no caller in the reference, the examples or the
-        tests passes one.  An id outside its table gives NaN for that triple (a bad positive: its whole row) and raises
-        IndexError at the next synchronising check (``_hip.raise_if_index_errors``, ``utils.relation_metrics``), as the
-        decoders do."""
+        as the 'single' mode gives for that triple.
+        ``mode="tail-shared"`` / ``"head-shared"``: `sample` is ``(positive, negatives)`` with positive [2, B], et [B] and
+        negatives int64 [G, K], 1 <= G <= B and B % G == 0 (``sample_shared_candidates``): the positives are cut into G chunks
+        of B // G consecutive ones, positive b belongs to chunk g = b // (B // G) and is scored against the ONE list
+        negatives[g, :] of its chunk - ``logsigmoid(score)`` [B, K] of (positive[0, b], et[b], negatives[g, k]) for
+        'tail-shared', of (negatives[g, k], et[b], positive[1, b]) for 'head-shared'; G == B is the batch modes' meaning.
+        G K entity rows are gathered instead of B K (csrc/kge_shared.hip).  TransE and RotatE evaluate the 'single' mode's
+        per-column terms and add them in column order; DistMult and ComplEx contract a prepared query row with the
+        candidate rows on the fp32 matrix cores, so for these two bitwise equality with ``mode="single"`` is NOT given (nor
+        required): every score is held to the same per-element bound against float64 (tests/test_gpu_kge_shared.py).  Entity
+        rows of at most 128 floats (the ``rank`` limit), a wrong shape or a G that does not divide B: ValueError with the
+        shapes.  A bad positive id gives NaN in its row, a bad candidate id NaN in its column of its chunk.
+        Any other mode raises ``ValueError("mode %s not supported")``; before the batch modes existed every string was
+        accepted and ignored, and no caller in the reference, the examples or the tests passes one.  An id outside its
+        table gives NaN for that triple (a bad positive: its whole row) and raises IndexError at the next synchronising
+        check (``_hip.raise_if_index_errors``, ``utils.relation_metrics``), as the decoders do."""
         return self._score(sample, et, True, mode)
 
     def score(self, sample, et, mode="single"):
@@ -210,8 +298,19 @@ class KGEModel(nn.Module):
                                subsampling_weight=None):
         """The loss of one mini-batch: ``negative_sampling_loss(self.score(positive, et), self.score((positive, negatives),
         et, mode), adversarial_temperature, subsampling_weight)`` - positive [2, B], et [B], negatives int64 [B, K]
-        (``sample_candidates``) standing for the tails ('tail-batch') or the heads ('head-batch').  The two scorers and one
-        launch for the loss; ``loss.backward()`` is the loss's one launch and the two scorers' own backward."""
+        (``sample_candidates``) standing for the tails ('tail-batch') or the heads ('head-batch'), or - with
+        ``mode="tail-shared"`` / ``"head-shared"`` - negatives int64 [G, K] (``sample_shared_candidates``), one list per
+        chunk of B // G positives.  The two scorers and one launch for the loss; ``loss.backward()`` is the loss's one
+        launch and the two scorers' own backward."""
+        if mode in _SHARED_SIDES:
+            if negatives.dim() == 2 and negatives.shape[1] < 1:
+                raise ValueError("negatives must have shape [G, K] with K >= 1, got {}".format(tuple(negatives.shape)))
+            _shared_block(positive, negatives, et)
+            if subsampling_weight is not None and tuple(subsampling_weight.shape) != (positive.shape[1],):
+                raise ValueError("subsampling_weight must have shape [{}], got {}".format(
+                    positive.shape[1], tuple(subsampling_weight.shape)))
+            return negative_sampling_loss(self.score(positive, et), self.score((positive, negatives), et, mode),
+                                          adversarial_temperature, subsampling_weight)
         if mode not in _BATCH_SIDES:
             raise ValueError("mode %s not supported" % mode)
         if positive.dim() != 2 or positive.shape[0] != 2 or positive.shape[1] < 1:

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define GN_VERSION 172 /* 0.1.66 */
+#define GN_VERSION 173 /* 0.1.67 */
 
 #if defined(GN_BUILDING)
 #define GN_API __attribute__((visibility("default")))
@@ -697,6 +697,66 @@ GN_API gn_status gn_kge_batch_backward_f32(int model, const float* ent, int64_t 
                                     int64_t num_candidates, int side, float phase_divisor, const float* grad_out,
                                     const float* raw_scores /* nullable */, float* d_ent, int64_t ld_dent, float* d_rel,
                                     int64_t ld_drel, int flags, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The scorers on SHARED candidate lists (the 'tail-shared' / 'head-shared' modes of gripnet_amd.KGEModel; no counterpart in
+ * the reference: what DGL-KE and PyTorch-BigGraph do with their negatives).  The B positives (fixed[b], edge_type[b]) are cut
+ * into G = num_lists chunks of B / G consecutive positives (1 <= G <= B, B % G == 0) and chunk g comes with ONE list of K
+ * candidate entities cand[g * ld_cand + k] (int64, ld_cand >= K):
+ *   g = b / (B / G)
+ *   tail side: fixed is the head,  out[b * K + k] = s(fixed[b], edge_type[b], cand[g, k])
+ *   head side: fixed is the tail,  out[b * K + k] = s(cand[g, k], edge_type[b], fixed[b])
+ * or its log-sigmoid; raw_out (nullable, [B, K]) receives s as well.  G == B is gn_kge_batch_forward_f32's meaning.  Tables,
+ * gamma, phase_divisor, models and the workspace (gn_kge_shared_forward_workspace_bytes, 16-byte aligned) are those of
+ * gn_kge_forward_f32; entity rows of at most 128 floats (hidden_dim <= 128 for TransE and DistMult, <= 64 for ComplEx and
+ * RotatE: the ranking limit), GN_ERR_UNSUPPORTED beyond.  G * K entity rows are gathered instead of B * K: a workgroup owns 64
+ * positives of one chunk (16 per wave) and walks the list in stages of 64 candidate rows held in LDS, each gathered once
+ * per workgroup.  The sum over the columns:
+ *   DistMult, ComplEx   the query row q with s = <q, candidate row> is prepared once per positive (h r, the complex product, or
+ *                       for the head side r t and its conjugate form, every product rounded as gn_kge_forward_f32 rounds it)
+ *                       and contracted on v_mfma_f32_16x16x4_f32, each instruction a chain of four fp32 fused multiply-adds:
+ *                       step s = 0 .. S - 1 takes the columns s, S + s, 2 S + s, 3 S + s in that order, S a quarter of the
+ *                       row's length padded to a multiple of 16.  The steps go in groups of four to FOUR partial sums in turn
+ *                       (group i = steps 4 i .. 4 i + 3 to partial i % 4, ascending i within a partial) and the score is
+ *                       (p0 + p1) + (p2 + p3): a row of 128 floats is four chains of 32, not one of 128.  The value is NOT the bits of
+ *                       gn_kge_forward_f32 for that triple (another order, products fused into the sum); it is held to the
+ *                       same per-element bound;
+ *   TransE, RotatE      the per-column terms of gn_kge_forward_f32 (the same operations in the same order), added in ascending
+ *                       column order on the vector ALU, then gamma - sum.  TransE on tables where h + r - t and the sums are
+ *                       exact gives the bits of gn_kge_batch_forward_f32.
+ * A fixed entity or relation outside its table makes the whole row NaN, a candidate outside makes its column of its chunk NaN;
+ * either sets bit 0 of *error_flag; nothing outside a table is read.  B == 0 or K == 0: nothing is written.  16-byte stores
+ * where K % 4 == 0 and out / raw_out are 16-byte aligned.  GN_ERR_INVALID_ARG: a G that does not divide B. */
+GN_API size_t gn_kge_shared_forward_workspace_bytes(int model, int64_t num_relations, int64_t hidden_dim);
+GN_API gn_status gn_kge_shared_forward_f32(int model, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                                    int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                                    const int64_t* edge_type, const int64_t* cand, int64_t ld_cand, int64_t num_positives,
+                                    int64_t num_lists, int64_t num_candidates, int side, float gamma, float phase_divisor,
+                                    int log_sigmoid, float* out, float* raw_out /* nullable */, int32_t* error_flag,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+/* Their backward.  grad_out [B, K] (contiguous) and raw_scores (nullable, [B, K]) as for gn_kge_backward_f32; d_ent and
+ * d_rel are overwritten.  No float atomics, no host synchronisation, the same bits in every call:
+ *   - g[b, k] = grad_out, times sigma(-s) with raw_scores, is formed once;
+ *   - query side: per positive the K contributions g[b, k] ds / d(fixed row) and g[b, k] ds / d(relation row) are summed in
+ *     ascending k, one fused multiply-add each, into one partial row per positive and role (a thread per positive and
+ *     column);
+ *   - candidate side: per list entry (g, k) the B / G contributions g[b, k] ds / d(candidate row) of its chunk's positives
+ *     are summed in ascending b into one partial row per entry (a thread per entry and column);
+ *   - three segmented reductions (chunks of 32 records) add the partial rows: G * K records keyed by cand[g, k] into d_ent,
+ *     B records keyed by fixed[b] onto it, B records keyed by edge_type[b] into d_rel.  A candidate that repeats in a list,
+ *     in several lists or equals a positive's own entity is one more record of its row.
+ * The derivatives are those of gn_kge_backward_f32, per column.  GN_DM_TYPES_SORTED in flags promises a non-decreasing
+ * edge_type [B]: the relation pass skips its sort.  Positives and candidates with an id outside its table contribute nothing;
+ * rows that nothing touched get exact zeros.  B == 0 or K == 0: zero gradients.  Scratch:
+ * gn_kge_shared_backward_workspace_bytes bytes, 256-byte aligned. */
+GN_API size_t gn_kge_shared_backward_workspace_bytes(int model, int64_t num_entities, int64_t num_relations, int64_t hidden_dim,
+                                              int64_t num_positives, int64_t num_lists, int64_t num_candidates);
+GN_API gn_status gn_kge_shared_backward_f32(int model, const float* ent, int64_t ld_ent, int64_t num_entities, const float* rel,
+                                     int64_t ld_rel, int64_t num_relations, int64_t hidden_dim, const int64_t* fixed,
+                                     const int64_t* edge_type, const int64_t* cand, int64_t ld_cand, int64_t num_positives,
+                                     int64_t num_lists, int64_t num_candidates, int side, float phase_divisor,
+                                     const float* grad_out, const float* raw_scores /* nullable */, float* d_ent,
+                                     int64_t ld_dent, float* d_rel, int64_t ld_drel, int flags, void* workspace,
+                                     size_t workspace_bytes, void* stream);
 
 /* The negative-sampling loss of a KGE mini-batch on RAW scores, and its gradient: pos [B] (gn_kge_forward_f32 without the
  * log-sigmoid), neg [B, K] with a leading dimension ld_neg >= K (gn_kge_batch_forward_f32 likewise), weight [B] (nullable: 1;
